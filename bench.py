@@ -16,6 +16,11 @@ Multi-GPU: one process per GPU (torchrun); frames are sharded (each rank process
 own K frames, weak scaling); the only collective is an RCCL all-gather of the
 detection lists at the end (inside the timed region).
 
+A plain run sets up, warms up, times the steps and prints the headline fields.  ``--full``
+adds the secondary legs after the timed region (roofline leg with the quoted PMC traffic,
+stream-copy probe, CPU baseline); ``--dump-outputs DIR`` writes the last timed step's
+outputs as .npy files (seeded inputs: the same arguments give the same files).
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -71,6 +76,17 @@ def parse(argv=None):
                          'spawns N ranks through torch.distributed.run and relays rank 0\'s line')
     ap.add_argument('--steps', type=int, default=500)
     ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the secondary legs and put them in the line: the roofline '
+                         'leg (isolated launches of every stage, the PMC traffic quoted beside them), the stream-copy '
+                         'probe and the CPU baseline.  Without it a run only sets up, warms up, times the steps and '
+                         'prints the headline fields')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last timed step returned to its caller as DIR/<name>.npy '
+                         '(float64): final_targets = the packed rows (frame_idx, Range, Velocity, Angle, Power) of the '
+                         'last batch; with --want-rdm also a fixed seeded sample of the last frame\'s complex RD map; '
+                         '--config music5: peaks, n_peaks and the eigenvalues / spectrum asked for.  The inputs are '
+                         'seeded, so the same arguments give the same files from run to run')
     ap.add_argument('--config', default='x2')
     ap.add_argument('--precision', default='c128', choices=['c128', 'c64'],
                     help="c128: complex double, the reference's MATLAB arithmetic (default); c64: complex single")
@@ -207,7 +223,27 @@ def validate_args(a):
     if a.per_call and (a.config == 'music5' or a.e2e or a.want_rdm or a.frames_total or a.gpus != 1):
         return ('--per-call times single synchronous frames of the radar chain on one GPU: it takes none of '
                 '--config music5, --e2e, --want-rdm, --frames-total, --gpus N')
+    if a.stage_timing and not a.full:
+        return '--stage-timing reports its spans in the roofline stages: add --full'
     return None
+
+
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: array} as path/<name>.npy, float64 (complex arrays as [..., 2] re/im)."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, arr in arrays.items():
+        arr = np.asarray(arr)
+        if np.iscomplexobj(arr):
+            arr = np.ascontiguousarray(arr.astype(np.complex128)).view(np.float64).reshape(arr.shape + (2,))
+        arr = np.ascontiguousarray(arr, dtype=np.float64)
+        total += arr.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise ValueError('--dump-outputs: %s brings the files to %d bytes > %d' % (name, total, DUMP_MAX_BYTES))
+        np.save(os.path.join(path, name + '.npy'), arr)
 
 
 def spawn_ranks(gpus, argv):
@@ -434,6 +470,26 @@ def main_music(a):
     census = rank_census(dist, dev) if dist is not None else None
     out = None
     if rank == 0:
+        out = {'metric': 'MUSIC_1D DOA instances/sec, 64ch x 1024 snapshots (BASELINE config #5)' +
+                         (', all N eigenvalues returned (full eigensolver)' if a.want_eig else
+                          (', pseudo-spectrum returned' if a.want_spectrum else '')),
+               'value': I * a.steps * world / el, 'unit': 'instances/s', 'n_gpus': world, 'steps': a.steps,
+               'warmup': a.warmup, 'ms_per_step': el / a.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak',
+               'vs_baseline': None, 'dtype': 'fp64 (complex128)' if f64 else 'fp32 (complex64)',
+               'data': 'synthetic (device Philox snapshots, MUSIC_1D.m scene: -10/-30/60 deg, 10 dB measured)',
+               'config': {'workload': 'BASELINE config #5: N=64 K=1024 M=3 scan=200, %d instances per step' % I +
+                                      ('; eigenvalues (N per instance) and peaks returned' if a.want_eig else
+                                       ('; P_dB (200 per instance) and peaks returned' if a.want_spectrum else
+                                        '; peak indices returned')),
+                          'parallelism': 'instance-sharded x%d' % world}}
+        if a.dump_outputs:   # the last timed step's arrays, before the profile leg reuses them
+            arrays = {'peaks': peaks, 'n_peaks': npk}
+            if a.want_eig:
+                arrays['eigenvalues'] = eig
+            if a.want_spectrum:
+                arrays['spectrum_dB'] = spec
+            dump_outputs(a.dump_outputs, arrays)
+    if rank == 0 and a.full:
         pr = plan.profile(ring[0], I, iters=a.profile_iters,
                           what='eigenvalues' if a.want_eig else ('spectrum' if a.want_spectrum else 'peaks'))
         n_fast = plan.fast_count()   # instances of the profiled launch on the fast path (0 with --want-eig)
@@ -462,18 +518,7 @@ def main_music(a):
         dom = max(stages, key=lambda st: st['ms_per_launch'])
         mtraffic = music_traffic(a.precision, I)
         eig_tf = stages[1]['ref_eig_equiv_TFLOPs']
-        out = {'metric': 'MUSIC_1D DOA instances/sec, 64ch x 1024 snapshots (BASELINE config #5)' +
-                         (', all N eigenvalues returned (full eigensolver)' if a.want_eig else
-                          (', pseudo-spectrum returned' if a.want_spectrum else '')),
-               'value': I * a.steps * world / el, 'unit': 'instances/s', 'n_gpus': world, 'steps': a.steps,
-               'warmup': a.warmup, 'ms_per_step': el / a.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak',
-               'vs_baseline': None, 'dtype': 'fp64 (complex128)' if f64 else 'fp32 (complex64)',
-               'data': 'synthetic (device Philox snapshots, MUSIC_1D.m scene: -10/-30/60 deg, 10 dB measured)',
-               'config': {'workload': 'BASELINE config #5: N=64 K=1024 M=3 scan=200, %d instances per step' % I +
-                                      ('; eigenvalues (N per instance) and peaks returned' if a.want_eig else
-                                       ('; P_dB (200 per instance) and peaks returned' if a.want_spectrum else
-                                        '; peak indices returned')),
-                          'parallelism': 'instance-sharded x%d' % world},
+        out.update({
                'roofline': {'bound': 'mfma' if dom is stages[0] else 'valu', 'kernel': dom['stage'],
                             'achieved': dom['achieved_TFLOPs'] if dom is stages[0] else eig_tf,
                             'peak': mfma_peak if dom is stages[0] else valu_peak, 'unit': 'TFLOP/s',
@@ -489,9 +534,9 @@ def main_music(a):
                                         pr['eig_ms'], eig_tf / valu_peak),
                             'stages': stages},
                'cpu_baseline': music_cpu_baseline(scene, scan, dl, N, K, M) if (world == 1 and not a.no_cpu_baseline)
-               else None}
-        if census is not None:
-            out['distributed'] = census
+               else None})
+    if out is not None and census is not None:
+        out['distributed'] = census
     for d in ring:
         plan.device_free(d)
     plan.close()
@@ -544,18 +589,10 @@ def main_per_call(a):
         n_targets += o.n_targets
     el = time.perf_counter() - t_all
     ms = np.array(times) * 1e3
-    # the device stages of one frame in isolation (HIP events, F = 1), for the roofline object
-    d_cube = plan.device_alloc(plan.cube_bytes)
-    plan.synthesize_device(d_cube, targets, frame_idx=1)
-    plan.sync()
-    prof = plan.profile_stages([d_cube], iters=a.profile_iters)
-    # the call's own S4 + S4.1 synthesis (fsf:45-88) is a device stage of the call too
-    prof = [plan.profile_synthesis(d_cube, targets, iters=a.profile_iters)] + prof
-    plan.device_free(d_cube)
-    stages = [{'stage': pr['stage'], 'ms_per_launch': pr['ms'], 'frames_per_launch': pr['frames'],
-               'alg_bytes_per_launch': pr['bytes'], 'achieved_GBps': pr['bytes'] / (pr['ms'] * 1e-3) / 1e9}
-              for pr in prof]
-    dom = max(stages, key=lambda s: s['ms_per_launch'])
+    if a.dump_outputs:   # the last timed call's final targets
+        dump_outputs(a.dump_outputs, {'final_targets': np.array(
+            [[a.warmup + a.steps, t.Range, t.Velocity, t.Angle, t.Power] for t in tbuf[:o.n_targets]],
+            np.float64).reshape(-1, 5)})
     cells = sz.B * sz.G * sz.P
     cfg_no = {'x2': '2', 'x4': '4', 'plumbing': '1'}.get(a.config, '-')
     out = {'metric': 'per-call latency of rsp_process_targets (one synchronous fun_process_single_frame frame), '
@@ -572,14 +609,30 @@ def main_per_call(a):
                cfg_no, a.config, sz.C, sz.B, sz.N, sz.P, sz.G), 'frames_per_call': 1,
                'used_samples': sz.used_samples, 'targets_reported': n_targets,
                'call': 'rsp_process_targets(plan, targets, nt, frame_idx, seed, 1.0, out) -- the C call of '
-                       'rsp_mex(\'frame\', ...) (matlab/rsp_mex.c)'},
-           'roofline': {'bound': 'hbm', 'kernel': dom['stage'], 'achieved': dom['achieved_GBps'],
-                        'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': dom['achieved_GBps'] / HBM_PEAK_GBS,
-                        'traffic': None, 'kernel_ms': dom['ms_per_launch'],
-                        'alg_bytes_per_launch': dom['alg_bytes_per_launch'], 'frames_per_launch': 1,
-                        'timing': '%d isolated one-frame launches per stage, HIP events on the kernel stream'
-                                  % a.profile_iters, 'stages': stages,
-                        'device_ms_per_frame': sum(s['ms_per_launch'] for s in stages)}}
+                       'rsp_mex(\'frame\', ...) (matlab/rsp_mex.c)'}}
+    if not a.full:
+        plan.close()
+        print(json.dumps(out))
+        return 0
+    # the device stages of one frame in isolation (HIP events, F = 1), for the roofline object
+    d_cube = plan.device_alloc(plan.cube_bytes)
+    plan.synthesize_device(d_cube, targets, frame_idx=1)
+    plan.sync()
+    prof = plan.profile_stages([d_cube], iters=a.profile_iters)
+    # the call's own S4 + S4.1 synthesis (fsf:45-88) is a device stage of the call too
+    prof = [plan.profile_synthesis(d_cube, targets, iters=a.profile_iters)] + prof
+    plan.device_free(d_cube)
+    stages = [{'stage': pr['stage'], 'ms_per_launch': pr['ms'], 'frames_per_launch': pr['frames'],
+               'alg_bytes_per_launch': pr['bytes'], 'achieved_GBps': pr['bytes'] / (pr['ms'] * 1e-3) / 1e9}
+              for pr in prof]
+    dom = max(stages, key=lambda s: s['ms_per_launch'])
+    out['roofline'] = {'bound': 'hbm', 'kernel': dom['stage'], 'achieved': dom['achieved_GBps'],
+                       'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': dom['achieved_GBps'] / HBM_PEAK_GBS,
+                       'traffic': None, 'kernel_ms': dom['ms_per_launch'],
+                       'alg_bytes_per_launch': dom['alg_bytes_per_launch'], 'frames_per_launch': 1,
+                       'timing': '%d isolated one-frame launches per stage, HIP events on the kernel stream'
+                                 % a.profile_iters, 'stages': stages,
+                       'device_ms_per_frame': sum(s['ms_per_launch'] for s in stages)}
     if dom['stage'] == 'k_synth':
         out['roofline']['note'] = ('k_synth is bound by its f64 VALU work (Box-Muller log/sqrt/sincos and Philox per '
                                    'sample), not by HBM: frac is its cube store rate against the HBM peak')
@@ -723,7 +776,54 @@ def main():
     fps = frames / el
     cells = sz.B * sz.G * sz.P
     out = None
+    esz = sz.elem_bytes
     if rank == 0:
+        if a.dump_outputs:   # what the last timed batch returned: its frames' packed rows, in the order received
+            nlast = (len(ring) - 1) % a.fpl + 1 if a.frames_total else a.fpl
+            last_id = f0 + len(ring) if a.frames_total else a.steps * a.fpl
+            arrays = {'final_targets': rows[rows[:, 0] > last_id - nlast]}
+            if a.want_rdm:   # the last frame's complex RD map: a fixed seeded sample of its elements
+                n_all = len(ring) if a.frames_total else a.steps * a.fpl
+                m = plan.device_download(rdm_ring[(n_all - 1) % len(rdm_ring)], sz.rdm_elems, plan.cdtype)
+                pick = np.sort(np.random.default_rng(20250101).choice(m.size, min(m.size, 1 << 20), replace=False))
+                arrays['rdm_sample_index'] = pick
+                arrays['rdm_sample'] = m[pick]
+            dump_outputs(a.dump_outputs, arrays)
+        frame_alg_bytes = sz.C * sz.N * sz.P * esz + cells * esz   # SURVEY 8(d): cube read + RD map write
+        metric = 'frames/sec + range-Doppler cells/sec, %dch×%dbeam×%dsamp×%dpulse' % (sz.C, sz.B, sz.N, sz.P)
+        cfg_no = {'x2': '2', 'x4': '4', 'plumbing': '1'}.get(a.config, '-')
+        if a.frames_total:
+            metric += ', batch of %d independent frames sharded over %d GPU(s)' % (a.frames_total, world)
+            cfg_no = '3'
+        if a.e2e:
+            metric += ', end to end (host cubes in pinned memory -> H2D of the used samples -> chain)'
+        if a.want_rdm:
+            metric += ', complex range-Doppler map of every frame written to HBM (rsp_enqueue_device_rdm)'
+        steps = (a.frames_total + a.fpl - 1) // a.fpl if a.frames_total else a.steps
+        out = {
+            'metric': metric,
+            'value': fps, 'unit': 'frames/s', 'n_gpus': world, 'steps': steps, 'warmup': a.warmup,
+            'warmup_effective': warm_batches,   # untimed batches that actually ran (>= WARM_MIN)
+            'ms_per_step': el / steps * 1e3, 'higher_is_better': True,
+            'scaling': 'strong' if a.frames_total else 'weak',
+            'vs_baseline': None,
+            'dtype': 'fp64 (complex128)' if a.precision == 'c128' else 'fp32 (complex64)',
+            'data': 'synthetic (device Philox noise + v8_2 targets)',
+            'cells_per_s': fps * cells,
+            'achieved_GBps_frame': fps * frame_alg_bytes / 1e9,   # SURVEY 8(d) bytes: cube read + RD map write
+            'rdm_written': bool(a.want_rdm),
+            'config': {'workload': 'BASELINE config #%s: %s C=%d B=%d N=%d P=%d G=%d' % (
+                cfg_no, a.config, sz.C, sz.B, sz.N, sz.P, sz.G), 'frames_per_launch': a.fpl, 'frames_per_step': a.fpl,
+                'ring': len(hring) if a.e2e else len(ring),
+                'parallelism': 'frame-sharded x%d' % world, 'used_samples': sz.used_samples,
+                'targets_reported': n_targets_all},
+        }
+        if a.e2e:
+            out['e2e_h2d_bytes_per_frame'] = sz.C * sz.used_samples * sz.P * esz
+            out['e2e_h2d_GBps'] = fps * out['e2e_h2d_bytes_per_frame'] / 1e9
+        if census is not None:   # what RCCL / gloo actually joined: world size, backend, each rank's GPU
+            out['distributed'] = census
+    if rank == 0 and a.full:
         # Roofline leg (after the timed region): each stage re-launched `profile_iters` times on
         # the same F-frame batch with HIP events on the kernel's stream, chip otherwise idle.  In the
         # timed region consecutive batches overlap on the device (lanes), so a kernel's span there
@@ -758,38 +858,10 @@ def main():
         if tr is not None:   # scaled from the PMC passes' frames per launch to this run's
             traffic = tr * dom['frames_per_launch'] / float(tf_fpl or 4)
             dom['pmc_traffic_bytes'] = traffic
-        esz = sz.elem_bytes
-        frame_alg_bytes = sz.C * sz.N * sz.P * esz + cells * esz   # SURVEY 8(d): cube read + RD map write
-        metric = 'frames/sec + range-Doppler cells/sec, %dch×%dbeam×%dsamp×%dpulse' % (sz.C, sz.B, sz.N, sz.P)
-        cfg_no = {'x2': '2', 'x4': '4', 'plumbing': '1'}.get(a.config, '-')
-        if a.frames_total:
-            metric += ', batch of %d independent frames sharded over %d GPU(s)' % (a.frames_total, world)
-            cfg_no = '3'
-        if a.e2e:
-            metric += ', end to end (host cubes in pinned memory -> H2D of the used samples -> chain)'
-        if a.want_rdm:
-            metric += ', complex range-Doppler map of every frame written to HBM (rsp_enqueue_device_rdm)'
-        steps = (a.frames_total + a.fpl - 1) // a.fpl if a.frames_total else a.steps
-        out = {
-            'metric': metric,
-            'value': fps, 'unit': 'frames/s', 'n_gpus': world, 'steps': steps, 'warmup': a.warmup,
-            'warmup_effective': warm_batches,   # untimed batches that actually ran (>= WARM_MIN)
-            'ms_per_step': el / steps * 1e3, 'higher_is_better': True,
-            'scaling': 'strong' if a.frames_total else 'weak',
-            'vs_baseline': None,
-            'dtype': 'fp64 (complex128)' if a.precision == 'c128' else 'fp32 (complex64)',
-            'data': 'synthetic (device Philox noise + v8_2 targets)',
-            'cells_per_s': fps * cells,
-            'achieved_GBps_frame': fps * frame_alg_bytes / 1e9,   # SURVEY 8(d) bytes: cube read + RD map write
+        out.update({
             # the algorithmic bytes this run's kernels actually move per frame (K1 + K2 + K3 stage
             # bytes; without --want-rdm the complex RD map is not written, only |RDM|)
             'alg_bytes_moved_per_frame': sum(st['alg_bytes_per_launch'] for st in stages) / dom['frames_per_launch'],
-            'rdm_written': bool(a.want_rdm),
-            'config': {'workload': 'BASELINE config #%s: %s C=%d B=%d N=%d P=%d G=%d' % (
-                cfg_no, a.config, sz.C, sz.B, sz.N, sz.P, sz.G), 'frames_per_launch': a.fpl, 'frames_per_step': a.fpl,
-                'ring': len(hring) if a.e2e else len(ring),
-                'parallelism': 'frame-sharded x%d' % world, 'used_samples': sz.used_samples,
-                'targets_reported': n_targets_all},
             'roofline': {'bound': 'hbm', 'kernel': dom['stage'], 'achieved': achieved, 'peak': HBM_PEAK_GBS,
                          'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic,
                          'traffic_source': traffic_src,
@@ -799,7 +871,7 @@ def main():
                                    '(tools/rocprof_split.py separates them from the timed region in the rocprof '
                                    'trace)' % a.profile_iters,
                          'stages': stages},
-        }
+        })
         # the box's measured stream-copy rate beside the datasheet peak
         import ctypes as ct
         from rsp import _abi
@@ -811,15 +883,10 @@ def main():
         if best > 0:
             out['roofline']['stream_copy_GBps'] = best
             out['roofline']['frac_of_stream_copy'] = achieved / best
-        if a.e2e:
-            out['e2e_h2d_bytes_per_frame'] = sz.C * sz.used_samples * sz.P * esz
-            out['e2e_h2d_GBps'] = fps * out['e2e_h2d_bytes_per_frame'] / 1e9
         if world == 1 and not a.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(cfg, cfar, clus, W, ang, k, targets, nframes=a.cpu_frames, name=a.config)
         else:
             out['cpu_baseline'] = None
-        if census is not None:   # what RCCL / gloo actually joined: world size, backend, each rank's GPU
-            out['distributed'] = census
     for p in ring + rdm_ring:
         plan.device_free(p)
     for h in hring:

@@ -170,3 +170,33 @@ def test_k3_stage_bytes_match_pmc_traffic(prec, rb):
     # a window other than the reference's reads whole maps
     wide = dict(cfar, refCells_R=6)
     assert bench.k3_map_bytes(sc['prtNum'], G, sc['beam_num'], wide, rb) == sc['beam_num'] * sc['prtNum'] * G * rb
+
+
+def test_stage_timing_needs_full():
+    """--stage-timing reports its spans in the roofline stages, which only --full builds."""
+    r = _run(['--stage-timing'])
+    assert r.returncode == 2 and '--stage-timing' in r.stderr and '--full' in r.stderr
+    assert r.stdout == ''
+
+
+def test_plain_run_defaults():
+    """--full and --dump-outputs are off unless asked for."""
+    a = bench.parse(['--gpus', '1', '--steps', '20', '--warmup', '5'])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (20, 5)
+    assert bench.parse(['--full', '--dump-outputs', 'd']).dump_outputs == 'd'
+
+
+def test_dump_outputs_writes_float64_npy(tmp_path):
+    """--dump-outputs files: one .npy per name, float64, complex as [..., 2] re/im, bounded in all."""
+    import numpy as np
+    d = tmp_path / 'out' / 'deeper'
+    rows = np.array([[1, 2.5, -3, 0.25, 9], [1, np.nan, np.nan, np.nan, np.nan]])
+    bench.dump_outputs(str(d), {'final_targets': rows, 'peaks': np.arange(6, dtype=np.int32).reshape(2, 3),
+                                'rdm_sample': np.array([1 + 2j, 3 - 4j], np.complex64)})
+    got = np.load(d / 'final_targets.npy')
+    assert got.dtype == np.float64 and np.array_equal(got, rows, equal_nan=True)
+    assert np.array_equal(np.load(d / 'peaks.npy'), np.arange(6.0).reshape(2, 3))
+    assert np.array_equal(np.load(d / 'rdm_sample.npy'), [[1, 2], [3, -4]])
+    assert sorted(p.name for p in d.iterdir()) == ['final_targets.npy', 'peaks.npy', 'rdm_sample.npy']
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(d), {'big': np.broadcast_to(np.float64(0), (bench.DUMP_MAX_BYTES // 8 + 1,))})

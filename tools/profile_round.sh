@@ -17,9 +17,9 @@ step() {  # name timeout cmd...
   echo "=== $name rc=$rc"; tail -n 4 $out/$name.log
   if [ $rc -ne 0 ]; then exit $rc; fi
 }
-step bench 240 python3 bench.py --config $cfg --precision $prec "$@"
+step bench 240 python3 bench.py --full --config $cfg --precision $prec "$@"
 cp $out/bench.log $out/bench.json
-step trace 240 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- python3 bench.py --config $cfg --precision $prec --no-cpu-baseline "$@"
+step trace 240 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o run -- python3 bench.py --full --config $cfg --precision $prec --no-cpu-baseline "$@"
 step fetch 90 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch -o run -- python3 tools/prof_stages.py $cfg 10 8 $prec
 step write 90 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/write -o run -- python3 tools/prof_stages.py $cfg 10 8 $prec
 python3 tools/pmc_traffic.py $out/fetch $out/write $out/pmc_traffic_${cfg}_${prec}.json $cfg 10 8 > /dev/null

@@ -1,6 +1,6 @@
-"""Split a rocprofv3 kernel trace of `bench.py` into its two legs and summarise each.
+"""Split a rocprofv3 kernel trace of `bench.py --full` into its two legs and summarise each.
 
-bench.py runs (1) the throughput queue -- warm-up + the timed region, consecutive batches
+bench.py --full runs (1) the throughput queue -- warm-up + the timed region, consecutive batches
 overlapping on the device -- and then (2) the roofline leg: rsp_profile_stages launches each
 stage once untimed and then `iters` timed times, one stage after the other, chip otherwise idle.
 The last `iters` dispatches of each hot-path kernel are therefore the roofline leg; every earlier
