@@ -186,6 +186,30 @@ int32_t rsp_plan_create(const rsp_sig_config* cfg, const rsp_cfar_params* cfar,
 int32_t rsp_plan_destroy(rsp_plan* plan);
 int32_t rsp_query_sizes(const rsp_plan* plan, rsp_sizes* out);
 
+/* Which slow-time transform the plan runs (read-only; the decision is the one the launchers
+ * take, for prtNum, beam_num, channel_num, the precision and RSP_PLAN_K1_TILED).  Tests assert
+ * it, so that a change of the plan's heuristics cannot silently move a case off the kernel it
+ * is there to cover. */
+#define RSP_K1_KERNEL_TILED 0                 /* k1_dbf_mtd: one tile per workgroup            */
+#define RSP_K1_KERNEL_PERSISTENT 1            /* k1p_dbf_mtd: power-of-two P, double-buffered  */
+#define RSP_K1_KERNEL_PERSISTENT_FACTORED 2   /* k1q_dbf_mtd: P = R Q                          */
+#define RSP_K1_TRANSFORM_STOCKHAM 0           /* out-of-place radix passes                     */
+#define RSP_K1_TRANSFORM_DIF 1                /* in-place decimation in frequency              */
+#define RSP_K1_TRANSFORM_FACTORED 2           /* P = R Q: radix-R stage + folded Q-point DFT   */
+#define RSP_K1_TRANSFORM_DIRECT 3             /* O(P^2) DFT                                    */
+typedef struct rsp_k1_route {
+    int32_t kernel;           /* RSP_K1_KERNEL_*                                               */
+    int32_t transform;        /* RSP_K1_TRANSFORM_*                                            */
+    int32_t R, Q;             /* the factored transform's P = R Q; 0, 0 otherwise              */
+    int32_t NT;               /* fast-time samples per tile                                    */
+    int32_t Ppad;             /* LDS stride of a tile column (>= P)                            */
+    int32_t tiles_per_wave;   /* MFMA sub-tiles a wave loads per tile in the persistent
+                                 kernels; 0 for the tiled kernel                               */
+    int32_t stage2_lgp;       /* rsp_process_stage2's column transform: log2 P for the FFT
+                                 instantiations (P = 16 .. 512), 0 for the direct DFT          */
+} rsp_k1_route;
+int32_t rsp_query_k1_route(const rsp_plan* plan, rsp_k1_route* out);
+
 /* Cube-in path: S5..S11 of fun_process_single_frame on one host cube
  * (layout RSP_LAYOUT_PNC, dtype RSP_C64 or RSP_C128; converted to the plan's precision
  * only if they differ).  Synchronous.  out->cfar_maps, when requested, is the map K3

@@ -174,6 +174,23 @@ struct SynthTargets {         // by value in the kernel arguments (2 KiB): no up
 
 // Frequencies per wave-uniform set of the factored slow-time DFT's Q-point stage (k1_dft_rq)
 #define RQ_RK 6
+// Complex LDS entries of k1_dft_rq's tables, twQ | W_P^i.  Pass 2 prefetches the table rows of
+// the step after its last one: up to 2 RQ_RK entries past a frequency set's rows, which for the
+// last set lie in W_P^i.  P < 2 RQ_RK (P = 6: Q = 3) would end them past W_P^i, so the request
+// is never smaller than the prefetch reaches (P >= 12: exactly twq_elems + P).
+inline int rq_table_elems(int twq_elems, int P) { return twq_elems + (P > 2 * RQ_RK ? P : 2 * RQ_RK); }
+
+// The slow-time transform of a plan: which K1 kernel launch_k1 starts in `mode`, the transform it
+// runs, the sub-tiles per wave of the persistent kernels (0: tiled) and the k_mtd_cols
+// instantiation of the stage-2 path.  The one decision: launch_k1, launch_mtd_cols and
+// rsp_query_k1_route all read it.  kernel / transform use the values of rsp.h's RSP_K1_KERNEL_* /
+// RSP_K1_TRANSFORM_*.
+enum { K1K_TILED = 0, K1K_PERSISTENT = 1, K1K_PERSISTENT_FACTORED = 2 };
+enum { K1X_STOCKHAM = 0, K1X_DIF = 1, K1X_FACTORED = 2, K1X_DIRECT = 3 };
+struct K1Route {
+    int kernel, transform, tpw, lgp2;
+};
+K1Route k1_route(const Geometry& g, int mode);
 
 // Launchers (rsp_kernels.hip).  `mode` bits for K1: 1 = apply DBF, 2 = apply MTD.
 hipError_t launch_k1(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, int mode, hipStream_t s);

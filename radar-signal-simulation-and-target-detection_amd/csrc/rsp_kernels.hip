@@ -874,8 +874,13 @@ __device__ __forceinline__ void k1_dft_rq(V* buf, int rs, int ncols, int Q, cons
             }
             // software-pipelined: step n + 1's operands are read while step n computes, so one LDS
             // latency is exposed per step instead of one per (cos, sin) pair.  The reads past the
-            // last step (s_(Qh+1), d_Qh, the next table row) stay inside the LDS tile / tables and
-            // are never used.  Pointer steps keep every address a base plus an immediate offset.
+            // last step are never used and stay inside the workgroup's LDS: s and d at most two
+            // slots on (index Qh + 2 <= Q of the subsequence: at worst the first slot of the next
+            // one, or of the tables after the last column); the table one row pair on, RQ_RK
+            // (Qh even) or 2 RQ_RK (Qh odd) entries past the frequency set's rows, which for the
+            // last set is the head of W_P^i -- the launchers request at least 2 RQ_RK entries
+            // there (rq_table_elems: P = 6 has only 6).  Pointer steps keep every address a base
+            // plus an immediate offset.
             // Two register sets alternate: the reads of the step after next go out before this
             // step's FMAs (the scheduling barriers keep that order), so a read has a whole step of
             // FMAs to land.  Steps are taken in pairs; the second step of the last pair exists only
@@ -2720,7 +2725,7 @@ static int k1q_tpw(const Geometry& g) {
     return need <= 4 ? need : 0;
 }
 static size_t k1q_lds(const Geometry& g) {   // tile | twQ | W_P^i | Atab (MB x NJ x 2 x 64 <= 1024 reals: CP <= 16)
-    return ((size_t)g.B * g.NT * g.Ppad + g.twq_elems + g.P) * cplx_bytes(g) + (size_t)1024 * (cplx_bytes(g) / 2);
+    return ((size_t)g.B * g.NT * g.Ppad + rq_table_elems(g.twq_elems, g.P)) * cplx_bytes(g) + (size_t)1024 * (cplx_bytes(g) / 2);
 }
 static bool k1q_fits(const Geometry& g) {
     return !g.pow2P && g.rqQ > 0 && k1q_tpw(g) > 0 && k1q_lds(g) <= 160 * 1024 && g.ncu > 0 && !g.k1_tiled;
@@ -2732,15 +2737,46 @@ bool k1_persistent_fits(const Geometry& g) {
            g.B * g.NT * g.P <= pts * K1_THREADS && g.ncu > 0 && !g.k1_tiled;
 }
 
+// The route launch_k1 takes in `mode` (3 = DBF + MTD, the frame chain; 0 = transpose only, the
+// stage-2 path, always the tiled kernel) -- see K1Route.  CP / BMAX / TPW as launch_k1_t's template
+// arguments derive them.
+K1Route k1_route(const Geometry& g, int mode) {
+    const int cp = g.C <= 8 ? 8 : (g.C <= 16 ? 16 : 32), nj = cp / 4, tpw = k1_tpw(g);
+    K1Route r;
+    r.lgp2 = g.pow2P ? g.logP : 0;   // k_mtd_cols<T, LGP>: the Stockham passes for P = 16 .. 512, else the direct DFT
+    r.kernel = K1K_TILED;
+    r.tpw = 0;
+    r.transform = g.pow2P ? (k1_dif(g.logP, cp) ? K1X_DIF : K1X_STOCKHAM) : (g.rqQ > 0 ? K1X_FACTORED : K1X_DIRECT);
+    if (mode == 3 && k1_persistent_fits(g)) {
+        // 2 TPW sub-tiles per wave only where their loads stay within 16 16-B registers per lane
+        // and 4 sub-tiles (x4: 2 x 8 channels); otherwise (no instantiation: it would spill) the
+        // tiled kernel
+        const bool twice = k1p_tpw(g) == 2 * tpw, twice_ok = 2 * tpw * nj <= 16 && 2 * tpw <= 4;
+        if (!twice || twice_ok) {
+            r.kernel = K1K_PERSISTENT;
+            r.tpw = twice ? 2 * tpw : tpw;
+            return r;
+        }
+    }
+    // the persistent factored-DFT K1 for C <= 16 when one load round of at most 16 16-B cube loads
+    // per lane covers a tile (register budget: no scratch); otherwise the tiled kernel
+    if (cp <= 16 && mode == 3 && k1q_fits(g) && k1q_tpw(g) * nj <= 16) {
+        r.kernel = K1K_PERSISTENT_FACTORED;
+        r.tpw = k1q_tpw(g);
+    }
+    return r;
+}
+
 template <class T, int BMAX, int CP>
 static hipError_t launch_k1_t(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, int mode,
                               hipStream_t s) {
-    if (mode == 3 && k1_persistent_fits(g)) {
+    const K1Route rt = k1_route(g, mode);
+    if (rt.kernel == K1K_PERSISTENT) {
         // one FFT size per instantiation keeps the prefetch registers + FFT under 256 VGPRs
         const size_t ldsp = k1p_lds(g);
         const int grid = std::min(g.ncu, nf * g.ntiles);
         constexpr int NJ = CP / 4, MB = BMAX <= 8 ? 1 : 2, TPW = (16 / NJ) / MB > 0 ? (16 / NJ) / MB : 1;
-        const bool twice = k1p_tpw(g) == 2 * TPW;
+        const bool twice = rt.tpw == 2 * TPW;
 #define K1P_LAUNCH(LGP, TW)                                                                                      \
     do {                                                                                                         \
         hipError_t e = allow_lds(k1p_dbf_mtd<T, BMAX, CP, LGP, TW>, ldsp);                                       \
@@ -2748,25 +2784,20 @@ static hipError_t launch_k1_t(const Geometry& g, const DevConsts& k, const Frame
         hipLaunchKernelGGL((k1p_dbf_mtd<T, BMAX, CP, LGP, TW>), dim3(grid), dim3(K1_THREADS), ldsp, s, g, k, fp, nf); \
         return hipGetLastError();                                                                                \
     } while (0)
-        // 2 TPW sub-tiles per wave only where their loads stay within 16 16-B registers per lane
-        // and 4 sub-tiles (x4: 2 x 8 channels); otherwise (no instantiation: it would spill) the
-        // tiled kernel below
+        // the 2 TPW instantiations exist only where k1_route may choose them (its twice_ok)
         constexpr bool TWICE_OK = 2 * TPW * NJ <= 16 && 2 * TPW <= 4;
-        if (!twice || TWICE_OK) {
-            switch (g.logP) {
-                case 6: if constexpr (TWICE_OK) { if (twice) K1P_LAUNCH(6, 2 * TPW); } K1P_LAUNCH(6, TPW);
-                case 7: if constexpr (TWICE_OK) { if (twice) K1P_LAUNCH(7, 2 * TPW); } K1P_LAUNCH(7, TPW);
-                case 8: if constexpr (TWICE_OK) { if (twice) K1P_LAUNCH(8, 2 * TPW); } K1P_LAUNCH(8, TPW);
-                default: break;
-            }
+        if (twice && !TWICE_OK) return hipErrorInvalidValue;
+        switch (g.logP) {
+            case 6: if constexpr (TWICE_OK) { if (twice) K1P_LAUNCH(6, 2 * TPW); } K1P_LAUNCH(6, TPW);
+            case 7: if constexpr (TWICE_OK) { if (twice) K1P_LAUNCH(7, 2 * TPW); } K1P_LAUNCH(7, TPW);
+            case 8: if constexpr (TWICE_OK) { if (twice) K1P_LAUNCH(8, 2 * TPW); } K1P_LAUNCH(8, TPW);
+            default: return hipErrorInvalidValue;
         }
 #undef K1P_LAUNCH
     }
-    // the persistent factored-DFT K1 for C <= 16 when one load round of at most 16 16-B cube loads
-    // per lane covers a tile (register budget: no scratch); otherwise the tiled kernel
     if constexpr (CP <= 16) {
         constexpr int NJ = CP / 4;
-        if (mode == 3 && k1q_fits(g) && k1q_tpw(g) * NJ <= 16) {
+        if (rt.kernel == K1K_PERSISTENT_FACTORED) {
             const size_t ldsq = k1q_lds(g);
             const int grid = std::min(g.ncu, nf * g.ntiles);
             hipError_t e;
@@ -2775,7 +2806,7 @@ static hipError_t launch_k1_t(const Geometry& g, const DevConsts& k, const Frame
         if ((e = allow_lds(k1q_dbf_mtd<T, BMAX, CP, TW>, ldsq)) != hipSuccess) return e;                           \
         hipLaunchKernelGGL((k1q_dbf_mtd<T, BMAX, CP, TW>), dim3(grid), dim3(K1_THREADS), ldsq, s, g, k, fp, nf); \
     } while (0)
-            switch (k1q_tpw(g)) {
+            switch (rt.tpw) {
                 case 1: K1Q_LAUNCH(1); break;
                 case 2: K1Q_LAUNCH(2); break;
                 case 3: K1Q_LAUNCH(3); break;
@@ -2785,8 +2816,9 @@ static hipError_t launch_k1_t(const Geometry& g, const DevConsts& k, const Frame
             return hipGetLastError();
         }
     }
-    const bool rq = (mode & 2) && !g.pow2P && g.rqQ > 0;
-    const size_t lds = ((size_t)g.B * g.NT * g.Ppad + g.P + (rq ? g.twq_elems : 0)) * sizeof(cx<T>);
+    if (rt.kernel != K1K_TILED) return hipErrorInvalidValue;
+    const bool rq = (mode & 2) && rt.transform == K1X_FACTORED;
+    const size_t lds = ((size_t)g.B * g.NT * g.Ppad + (rq ? rq_table_elems(g.twq_elems, g.P) : g.P)) * sizeof(cx<T>);
     hipError_t e;
     if (rq) {
         if ((e = allow_lds(k1_dbf_mtd<T, BMAX, CP, true>, lds)) != hipSuccess) return e;
@@ -2898,7 +2930,7 @@ static hipError_t launch_mtd_t(const Geometry& g, const DevConsts& k, const void
 
 template <class T>
 static hipError_t launch_mtd_p(const Geometry& g, const DevConsts& k, const void* pc, void* rdm, hipStream_t s) {
-    switch (g.pow2P ? g.logP : 0) {
+    switch (k1_route(g, 0).lgp2) {
         case 4: return launch_mtd_t<T, 4>(g, k, pc, rdm, s);
         case 5: return launch_mtd_t<T, 5>(g, k, pc, rdm, s);
         case 6: return launch_mtd_t<T, 6>(g, k, pc, rdm, s);

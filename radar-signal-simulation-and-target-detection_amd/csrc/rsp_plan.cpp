@@ -431,7 +431,12 @@ int build_fft_segment(SegDesc& s, const double* mf_fft, int Nfft, int N, int ga,
         const double cost = (double)nb * M * (std::log2((double)M) + 2);
         if (cost < best * 0.999) { best = cost; bestM = M; }
     }
-    if (!bestM) return fail(RSP_ERR_UNSUPPORTED, "%s filter length %d exceeds the 2048-point block", name, Lh);
+    if (!bestM) {
+        int maxM = 0;
+        for (int M : cand) maxM = std::max(maxM, M);
+        return fail(RSP_ERR_UNSUPPORTED, "%s filter length %d exceeds the largest overlap-save block (%d points)", name, Lh,
+                    maxM);
+    }
     const int M = bestM;
     const bool mix = !is_pow2(M);
     s.M = M; s.logM = mix ? 0 : ilog2i(M); s.V = M - Lh + 1;
@@ -989,7 +994,7 @@ int32_t rsp_plan_create_ex(const rsp_sig_config* cfg, const rsp_cfar_params* cfa
         while (P % (2 * R) == 0) R *= 2;
         const int Q = P / R, Qh = (Q - 1) / 2;
         const int twq = (Qh + 1 + RQ_RK - 1) / RQ_RK * Qh * RQ_RK;
-        if (R <= 4 && Q >= 3 && ((size_t)B * (P + 15) + twq + P) * esz <= 160 * 1024) {
+        if (R <= 4 && Q >= 3 && ((size_t)B * (P + 15) + rq_table_elems(twq, P)) * esz <= 160 * 1024) {
             g.rqR = R;
             g.rqQ = Q;
             g.twq_elems = twq;
@@ -1000,7 +1005,7 @@ int32_t rsp_plan_create_ex(const rsp_sig_config* cfg, const rsp_cfar_params* cfa
     g.Ppad = g.pow2P ? P + P / 16 : (g.rqQ ? rq_pick_stride(g.rqR, g.rqQ, B) : P + 4);
     const int max_pts = f64 ? 4096 : 8192;
     const size_t tile_cap = f64 ? 72 * 1024 : 80 * 1024;
-    const size_t tab_bytes = g.rqQ ? ((size_t)g.twq_elems + P) * esz : 0;   // k1_dft_rq's LDS tables
+    const size_t tab_bytes = g.rqQ ? (size_t)rq_table_elems(g.twq_elems, P) * esz : 0;   // k1_dft_rq's LDS tables
     g.NT = 8;
     while (g.NT > 1 && ((size_t)B * g.NT * g.Ppad * esz > tile_cap || (g.pow2P && B * g.NT * P > max_pts) ||
                         (size_t)B * g.NT * g.Ppad * esz + tab_bytes > 160 * 1024))
@@ -1233,6 +1238,26 @@ int32_t rsp_query_sizes(const rsp_plan* p, rsp_sizes* s) {
     s->n_stages = 3;
     s->precision = g.prec == RSP_PREC_F64 ? RSP_C128 : RSP_C64;
     s->elem_bytes = (int32_t)p->esz;
+    return RSP_OK;
+}
+
+int32_t rsp_query_k1_route(const rsp_plan* p, rsp_k1_route* out) {
+    if (!p || !out) return fail(RSP_ERR_INVALID, "null argument");
+    static_assert(K1K_TILED == RSP_K1_KERNEL_TILED && K1K_PERSISTENT == RSP_K1_KERNEL_PERSISTENT &&
+                      K1K_PERSISTENT_FACTORED == RSP_K1_KERNEL_PERSISTENT_FACTORED &&
+                      K1X_STOCKHAM == RSP_K1_TRANSFORM_STOCKHAM && K1X_DIF == RSP_K1_TRANSFORM_DIF &&
+                      K1X_FACTORED == RSP_K1_TRANSFORM_FACTORED && K1X_DIRECT == RSP_K1_TRANSFORM_DIRECT,
+                  "K1Route's values are rsp.h's");
+    const Geometry& g = p->g;
+    const K1Route r = k1_route(g, 3);   // the frame chain's launch (launch_k1 mode 3)
+    out->kernel = r.kernel;
+    out->transform = r.transform;
+    out->R = g.rqR;
+    out->Q = g.rqQ;
+    out->NT = g.NT;
+    out->Ppad = g.Ppad;
+    out->tiles_per_wave = r.tpw;
+    out->stage2_lgp = r.lgp2;
     return RSP_OK;
 }
 

@@ -71,6 +71,16 @@ class Sizes(ct.Structure):
                 ('precision', ct.c_int32), ('elem_bytes', ct.c_int32)]
 
 
+K1_KERNELS = ('tiled', 'persistent', 'persistent_factored')   # RSP_K1_KERNEL_*
+K1_TRANSFORMS = ('stockham', 'dif', 'factored', 'direct')     # RSP_K1_TRANSFORM_*
+
+
+class K1Route(ct.Structure):
+    _fields_ = [('kernel', ct.c_int32), ('transform', ct.c_int32), ('R', ct.c_int32), ('Q', ct.c_int32),
+                ('NT', ct.c_int32), ('Ppad', ct.c_int32), ('tiles_per_wave', ct.c_int32),
+                ('stage2_lgp', ct.c_int32)]
+
+
 RSP_PLAN_K1_TILED = 1
 RSP_PLAN_MONOPULSE_COMPLEX = 2
 
@@ -141,6 +151,7 @@ PROTOTYPES = {
     'rsp_plan_options_default': (ct.c_int32, [ct.POINTER(PlanOptions)]),
     'rsp_plan_destroy': (ct.c_int32, [_P]),
     'rsp_query_sizes': (ct.c_int32, [_P, ct.POINTER(Sizes)]),
+    'rsp_query_k1_route': (ct.c_int32, [_P, ct.POINTER(K1Route)]),
     'rsp_process_cube': (ct.c_int32, [_P, _P, ct.c_int32, ct.c_int32, ct.c_int32, ct.POINTER(FrameOut)]),
     'rsp_process_targets': (ct.c_int32, [_P, ct.POINTER(TargetIn), ct.c_int32, ct.c_int32, ct.c_uint64,
                                          ct.c_double, ct.POINTER(FrameOut)]),

@@ -112,6 +112,17 @@ class Plan:
         except Exception:
             pass
 
+    def k1_route(self):
+        """The slow-time transform this plan runs (rsp_query_k1_route): ``kernel`` ('tiled',
+        'persistent', 'persistent_factored'), ``transform`` ('stockham', 'dif', 'factored',
+        'direct'), ``R``, ``Q`` (P = R Q of the factored transform, else 0), ``NT``, ``Ppad``,
+        ``tiles_per_wave`` (0 for the tiled kernel) and ``stage2_lgp`` (process_stage2's
+        column transform: log2 P, or 0 for the direct DFT)."""
+        r = _abi.K1Route()
+        check(lib().rsp_query_k1_route(self.h, ct.byref(r)))
+        return dict(kernel=_abi.K1_KERNELS[r.kernel], transform=_abi.K1_TRANSFORMS[r.transform], R=r.R, Q=r.Q,
+                    NT=r.NT, Ppad=r.Ppad, tiles_per_wave=r.tiles_per_wave, stage2_lgp=r.stage2_lgp)
+
     # ---- synchronous frame paths ---------------------------------------------------------
     def _frame_out(self, want_rdm, want_cfar):
         o = _abi.FrameOut()

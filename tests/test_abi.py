@@ -46,7 +46,7 @@ STRUCTS = {'rsp_sig_config': _abi.SigConfig, 'rsp_cfar_params': _abi.CfarParams,
            'rsp_frame_out': _abi.FrameOut, 'rsp_sizes': _abi.Sizes, 'rsp_music_config': _abi.MusicConfig,
            'rsp_music_scene': _abi.MusicScene, 'rsp_music_out': _abi.MusicOut, 'rsp_track_point': _abi.TrackPoint,
            'rsp_inter_frame_params': _abi.InterFrameParams, 'rsp_track': _abi.Track,
-           'rsp_plan_options': _abi.PlanOptions}
+           'rsp_plan_options': _abi.PlanOptions, 'rsp_k1_route': _abi.K1Route}
 
 
 def test_struct_layouts_match_header():
@@ -70,11 +70,22 @@ def test_struct_layouts_match_header():
             assert int(got['%s.%s' % (cname, fname)]) == getattr(py, fname).offset, (cname, fname)
 
 
+def test_k1_route_names_mirror_the_header():
+    """rsp._abi's names of rsp_k1_route.kernel / .transform are the header's RSP_K1_* values."""
+    vals = dict(re.findall(r'#define (RSP_K1_(?:KERNEL|TRANSFORM)_[A-Z_]+) +(\d+)', open(HEADER).read()))
+    assert len(vals) == len(_abi.K1_KERNELS) + len(_abi.K1_TRANSFORMS) == 7
+    for i, n in enumerate(_abi.K1_KERNELS):
+        assert int(vals['RSP_K1_KERNEL_' + n.upper()]) == i
+    for i, n in enumerate(_abi.K1_TRANSFORMS):
+        assert int(vals['RSP_K1_TRANSFORM_' + n.upper()]) == i
+
+
 def test_null_arguments_are_rejected():
     lib = _abi.lib()
     assert lib.rsp_plan_create(None, None, None, None, 0, 1, None) == _abi.RSP_ERR_INVALID
     assert b'null' in lib.rsp_last_error()
     assert lib.rsp_query_sizes(None, None) == _abi.RSP_ERR_INVALID
+    assert lib.rsp_query_k1_route(None, None) == _abi.RSP_ERR_INVALID
     assert lib.rsp_drain(None) == _abi.RSP_ERR_INVALID
     assert lib.rsp_process_cube(None, None, 1, 0, 0, None) == _abi.RSP_ERR_INVALID
     assert lib.rsp_stage_name(99) == b'?'

@@ -29,12 +29,12 @@ import pytest
 from oracle import chain
 from rsp.plan import Plan
 
-from _scen import scenario, targets_for, noisy_cube, device_cube, SEED
+import _parity
+from _parity import MAP_TOL, map_close as _map_close
+from _scen import scenario, targets_for, noisy_cube, device_cube, SEED, ROUTE_CASES
 
 pytestmark = pytest.mark.gpu
 
-MAP_TOL = {'c128': 1e-12, 'c64': 2e-5}
-MARGIN = 1e-4
 LARGE = ('x4', 'reference')   # inputs synthesised on the device (numpy synthesis takes ~30 s)
 CASES = [('small', 'c128'), ('small', 'c64'), ('x2', 'c128'), ('x2', 'c64'), ('p256', 'c128'), ('p256', 'c64'),
          ('x4', 'c128'), ('x4', 'c64'), ('reference', 'c128'), ('reference', 'c64')]
@@ -74,106 +74,31 @@ def case(request):
     yield dict(name=name, prec=prec, s=s, tg=tg, fin=fin, st=st, gpu=gpu, gpu_mag=gpu_mag)
 
 
-def _map_close(a, b, tol):
-    scale = np.abs(b).max()
-    err = np.abs(a - b).max()
-    assert err <= tol * scale, 'max err %.3g vs scale %.3g (tol %g)' % (err, scale, tol)
-    if tol > 1e-9:
-        rl2 = np.linalg.norm((a - b).ravel()) / np.linalg.norm(b.ravel())
-        assert rl2 <= 1e-5, 'rel L2 %.3g' % rl2
-
-
 def test_rdm_parity(case):
-    _map_close(case['gpu']['rdm'], case['st']['rdm'], MAP_TOL[case['prec']])
+    _parity.check_rdm(case)
 
 
 def test_cfar_map_parity(case):
     """rdm_for_cfar_all as produced on the device (K3's S tile), not recomputed on the host."""
-    _map_close(case['gpu']['cfar_maps'], case['st']['S_all'], MAP_TOL[case['prec']])
+    _parity.check_cfar_map(case)
 
 
 def test_cfar_map_without_rdm(case):
     """K2 without the complex RD map stores the same magnitudes: the CFAR maps and the detection
     list are bit-identical to the run that also writes the RDM."""
-    a, b = case['gpu_mag'], case['gpu']
-    assert np.array_equal(a['cfar_maps'], b['cfar_maps']), 'max diff %g' % np.abs(a['cfar_maps'] - b['cfar_maps']).max()
-    assert [(d['v_idx'], d['r_idx'], d['pair_idx']) for d in a['detections']] == \
-        [(d['v_idx'], d['r_idx'], d['pair_idx']) for d in b['detections']]
-
-
-def _keys(dets):
-    return [(int(d[0]), int(d[1]), int(d[2])) for d in dets]
+    _parity.check_cfar_map_without_rdm(case)
 
 
 def test_detection_sets(case):
-    o = set(_keys(case['st']['dets']))
-    g = {(d['v_idx'], d['r_idx'], d['pair_idx']) for d in case['gpu']['detections']}
-    assert len(o) > 0
-    if case['prec'] == 'c128':
-        assert o == g, 'CFAR decisions differ: oracle-only %r, device-only %r' % (sorted(o - g)[:8], sorted(g - o)[:8])
-        return
-    mg = chain.cfar_margin(case['st']['rdm'], case['s']['cfar'])
-    for (v, r, p) in o ^ g:
-        assert mg[v - 1, r - 1, p - 1] < MARGIN, 'CFAR decision differs at (v=%d r=%d pair=%d)' % (v, r, p)
+    _parity.check_detection_sets(case)
 
 
 def test_detection_order_and_estimates(case):
-    pre = case['s']['pre_o']
-    od = {k: (d, e) for k, d, e in zip(_keys(case['st']['dets']), case['st']['dets'], case['st']['par'])}
-    gd = case['gpu']['detections']
-    keys = [(d['v_idx'], d['r_idx'], d['pair_idx']) for d in gd]
-    assert keys == sorted(keys, key=lambda k: (k[2], k[1], k[0])), 'not in fsf find() order'
-    if case['prec'] == 'c128':
-        assert keys == _keys(case['st']['dets'])
-        for d in gd:
-            raw, est = od[(d['v_idx'], d['r_idx'], d['pair_idx'])]
-            assert d['amp'] == pytest.approx(raw[3], rel=1e-12)
-            for f in ('Range', 'Velocity', 'Angle'):
-                assert d[f] == pytest.approx(est[f], abs=1e-9), f
-        return
-    moved = 0
-    n = 0
-    for d in gd:
-        k = (d['v_idx'], d['r_idx'], d['pair_idx'])
-        if k not in od:
-            continue
-        n += 1
-        raw, est = od[k]
-        assert d['amp'] == pytest.approx(raw[3], rel=1e-4)
-        assert d['Angle'] == pytest.approx(est['Angle'], abs=1e-3)
-        dr, dv = abs(d['Range'] - est['Range']), abs(d['Velocity'] - est['Velocity'])
-        if dr > 1e-6 * max(1.0, abs(est['Range'])) or dv > 1e-6:
-            assert dr <= pre['deltaR'] / 8 + 1e-6 and dv <= pre['deltaV'] / 4 + 1e-9
-            moved += 1
-    assert n > 0
-    assert moved <= max(1, 0.02 * n)
+    _parity.check_detection_order_and_estimates(case)
 
 
 def test_final_targets(case):
-    fg = case['gpu']['final_targets']
-    if case['prec'] == 'c128':
-        fo = case['fin']
-        assert len(fo) == len(fg)
-        for a, b in zip(fo, fg):
-            for f in ('Range', 'Velocity', 'Angle', 'Power'):
-                assert b[f] == pytest.approx(a[f], rel=1e-9, abs=1e-9), f
-        return
-    o = set(_keys(case['st']['dets']))
-    g = {(d['v_idx'], d['r_idx'], d['pair_idx']) for d in case['gpu']['detections']}
-    pre = case['s']['pre_o']
-    if o == g:
-        fo = case['fin']
-        tol = dict(Range=pre['deltaR'] / 8, Velocity=pre['deltaV'] / 4, Angle=2e-3)
-    else:   # near-threshold cells flipped: the clustering of the device's own detections
-        par = [dict(Range=d['Range'], Velocity=d['Velocity'], Angle=d['Angle'], Power=d['amp'])
-               for d in case['gpu']['detections']]
-        fo = chain.cluster_stage2(chain.cluster_stage1(par, case['s']['clus']), case['s']['clus'])
-        tol = dict(Range=1e-9, Velocity=1e-9, Angle=1e-9)
-    assert len(fo) == len(fg)
-    for a, b in zip(fo, fg):
-        for f, t in tol.items():
-            assert b[f] == pytest.approx(a[f], abs=t), f
-        assert b['Power'] == pytest.approx(a['Power'], rel=1e-4)
+    _parity.check_final_targets(case)
 
 
 def test_targets_found(case):
@@ -271,10 +196,14 @@ def test_process_targets_equals_cube_path():
     assert len(a['final_targets']) == len(b['final_targets'])
 
 
-@pytest.mark.parametrize('prec', ['c128', 'c64'])
-def test_queue_matches_sync_path(prec):
-    s = scenario('small')
-    tg = targets_for('small')
+# the route cases (_scen.ROUTE_CASES) whose default K1 is a persistent kernel, in the precisions they run
+PERSISTENT_ROUTES = [(n, p) for n, rc in ROUTE_CASES.items() for p in rc['precs']
+                     if rc['route'][p]['kernel'] != 'tiled']
+
+
+def _queue_matches_sync(name, prec):
+    s = scenario(name)
+    tg = targets_for(name)
     plan = Plan(s['cfg'], s['cfar'], s['clus'], s['pre_p'], frames_per_launch=3, precision=prec)
     ptrs = [plan.device_alloc(plan.cube_bytes) for _ in range(4)]
     try:
@@ -296,6 +225,17 @@ def test_queue_matches_sync_path(prec):
         for p in ptrs:
             plan.device_free(p)
         plan.close()
+
+
+@pytest.mark.parametrize('prec', ['c128', 'c64'])
+def test_queue_matches_sync_path(prec):
+    _queue_matches_sync('small', prec)
+
+
+@pytest.mark.parametrize('name,prec', PERSISTENT_ROUTES, ids=['%s-%s' % c for c in PERSISTENT_ROUTES])
+def test_queue_matches_sync_path_routes(name, prec):
+    """The same through the persistent factored K1 at every sub-tile count it is instantiated for."""
+    _queue_matches_sync(name, prec)
 
 
 @pytest.mark.parametrize('prec', ['c128', 'c64'])
@@ -333,8 +273,10 @@ def test_profile_stages_reports_three_kernels():
     assert st[2]['bytes'] == st[2]['frames'] * bench.k3_map_bytes(sc['prtNum'], G, sc['beam_num'], s['cfar'], 8)
 
 
-@pytest.mark.parametrize('prec', ['c128', 'c64'])
-@pytest.mark.parametrize('name', ['small', 'x2', 'p256', 'reference'])
+_BITID = [(n, p) for n in ('small', 'x2', 'p256', 'reference') for p in ('c128', 'c64')] + PERSISTENT_ROUTES
+
+
+@pytest.mark.parametrize('name,prec', _BITID, ids=['%s-%s' % c for c in _BITID])
 def test_persistent_k1_bit_identical_to_tiled_k1(name, prec):
     """The persistent software-pipelined K1 (k1p_dbf_mtd for power-of-two P; k1q_dbf_mtd for the
     factored DFT of the reference frame's P = 332) and the one-tile-per-workgroup K1
@@ -346,6 +288,9 @@ def test_persistent_k1_bit_identical_to_tiled_k1(name, prec):
     outs, queued = [], []
     for tiled in (False, True):
         plan = Plan(s['cfg'], s['cfar'], s['clus'], s['pre_p'], frames_per_launch=8, precision=prec, k1_tiled=tiled)
+        if name in ROUTE_CASES:   # the two plans do run different kernels
+            want = 'tiled' if tiled else ROUTE_CASES[name]['route'][prec]['kernel']
+            assert plan.k1_route()['kernel'] == want
         outs.append(plan.process_cube(cube, frame_idx=1, want_rdm=True))
         ptrs = [plan.device_alloc(plan.cube_bytes) for _ in range(3)]
         try:
