@@ -210,6 +210,14 @@ typedef struct rsp_k1_route {
 } rsp_k1_route;
 int32_t rsp_query_k1_route(const rsp_plan* plan, rsp_k1_route* out);
 
+/* What rsp_plan_create_ex would build for these arguments on a device of `ncu` compute units,
+ * without a device: the same checks (opt->device aside), refusals and messages, and the values
+ * rsp_query_sizes and rsp_query_k1_route report for the created plan.  `sizes` / `route` may be
+ * NULL.  No HIP call is made, so it runs on a machine without a GPU. */
+int32_t rsp_plan_describe(const rsp_sig_config* cfg, const rsp_cfar_params* cfar,
+                          const rsp_cluster_params* cluster, const rsp_precomputed* pre,
+                          const rsp_plan_options* opt, int32_t ncu, rsp_sizes* sizes, rsp_k1_route* route);
+
 /* Cube-in path: S5..S11 of fun_process_single_frame on one host cube
  * (layout RSP_LAYOUT_PNC, dtype RSP_C64 or RSP_C128; converted to the plan's precision
  * only if they differ).  Synchronous.  out->cfar_maps, when requested, is the map K3

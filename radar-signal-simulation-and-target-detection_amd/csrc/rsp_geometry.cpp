@@ -1,0 +1,725 @@
+// rsp_geometry.cpp -- plan geometry, K1 routing and host tables of librsp (rsp_geometry.h): the
+// analysis of the reference's precomputed_data that rsp_plan_create_ex runs before it touches the
+// device, and rsp_plan_describe, which runs it alone.  Plain C++ (built and sanitized without HIP).
+#include "rsp_geometry.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <utility>
+
+__attribute__((visibility("hidden"))) int rsp_set_error(int code, const char* fmt, ...);   // rsp_host.cpp
+
+namespace {
+
+template <class... A>
+int fail(int code, const char* fmt, A... a) { return rsp_set_error(code, fmt, a...); }
+
+using cd = std::complex<double>;
+
+bool is_pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
+int ilog2i(int x) { int l = 0; while ((1 << l) < x) ++l; return l; }
+size_t cplx_bytes(const Geometry& g) { return g.prec == RSP_PREC_F64 ? 16 : 8; }
+
+// In-place double FFT (sign -1 forward, +1 inverse, unscaled); O(n^2) DFT if n is not 2^k.
+void fft_d(std::vector<cd>& a, int sign) {
+    const int n = (int)a.size();
+    if (!is_pow2(n)) {
+        std::vector<cd> o(n);
+        for (int k = 0; k < n; ++k) {
+            cd s = 0;
+            for (int t = 0; t < n; ++t) s += a[t] * std::polar(1.0, sign * 2.0 * M_PI * ((double)((int64_t)t * k % n)) / n);
+            o[k] = s;
+        }
+        a.swap(o);
+        return;
+    }
+    for (int i = 1, j = 0; i < n; ++i) {
+        int bit = n >> 1;
+        for (; j & bit; bit >>= 1) j ^= bit;
+        j ^= bit;
+        if (i < j) std::swap(a[i], a[j]);
+    }
+    for (int len = 2; len <= n; len <<= 1) {
+        for (int i = 0; i < n; i += len) {
+            for (int k = 0; k < len / 2; ++k) {
+                const cd w = std::polar(1.0, sign * 2.0 * M_PI * k / len);
+                const cd u = a[i + k], v = a[i + k + len / 2] * w;
+                a[i + k] = u + v;
+                a[i + k + len / 2] = u - v;
+            }
+        }
+    }
+}
+
+// Row stride (complex elements, P..P+15) of the factored slow-time DFT's LDS tile: the one whose
+// pass-2 reads (k1_dft_rq: lane = subsequence (column, k2) of the first 64, element n + Q k2 of
+// its column, and its mirror Q - n + Q k2) take the fewest ds_read_b128 cycles by the gfx950
+// bank model (MI355X_MICROARCH.md LDS table: four 16-lane groups, 64 banks of 4 B; identical
+// addresses broadcast).  Smallest stride on ties.  The reference frame (R = 4, Q = 83, B = 13):
+// stride 332 = P itself is conflict-free.
+int rq_pick_stride(int R, int Q, int ncols) {
+    static const int grp_first[4][3][2] = {{{0, 4}, {12, 16}, {20, 28}}, {{4, 12}, {16, 20}, {28, 32}},
+                                           {{32, 36}, {44, 48}, {52, 60}}, {{36, 44}, {48, 52}, {60, 64}}};
+    const int P = R * Q, NS = std::min(ncols * R, 64), Qh = (Q - 1) / 2;
+    int best = P, best_cost = INT32_MAX;
+    for (int rs = P; rs < P + 16; ++rs) {
+        long cost = 0;
+        for (int n = 1; n <= Qh; ++n)
+            for (int mirror = 0; mirror < 2; ++mirror)
+                for (auto& grp : grp_first) {
+                    int addr[16], na = 0;   // distinct 16-B addresses of the group's lanes
+                    for (auto& rg : grp)
+                        for (int l = rg[0]; l < rg[1]; ++l) {
+                            if (l >= NS) continue;
+                            const int c = l / R, k2 = l % R;
+                            const int a = c * rs + Q * k2 + (mirror ? Q - n : n);
+                            bool seen = false;   // a broadcast of the same address is free
+                            for (int j = 0; j < na; ++j) seen = seen || addr[j] == a;
+                            if (!seen) addr[na++] = a;
+                        }
+                    int cnt[16] = {0}, worst = 1;   // a 16-B slot covers 4 banks: slot a & 15
+                    for (int j = 0; j < na; ++j) worst = std::max(worst, ++cnt[addr[j] & 15]);
+                    cost += worst;
+                }
+        if (cost < best_cost) {
+            best_cost = (int)cost;
+            best = rs;
+        }
+    }
+    return best;
+}
+
+// exp(-2 pi i e / n) with e reduced mod n and the angle formed in long double
+cd root_of_unity(long long e, long long n) {
+    e %= n;
+    if (e < 0) e += n;
+    const long double a = -2.0L * 3.141592653589793238462643383279502884L * (long double)e / (long double)n;
+    return cd((double)std::cos(a), (double)std::sin(a));
+}
+
+// Radix sequence for a 2^m-point Stockham FFT: radix 16 passes, remainder as 8/4
+// (never a lone radix-2 pass unless m == 1).  pal: a 3-pass plan with the remainder in the
+// middle (the overlap-save blocks, rad_bits_pal in rsp_kernels.hip).
+void radix_plan(int m, int* nrad, int* rad, bool pal = false) {
+    *nrad = 0;
+    while (m > 0) {
+        const int p = (m == 5) ? 3 : (m >= 4 ? 4 : m);
+        rad[(*nrad)++] = 1 << p;
+        m -= p;
+    }
+    if (pal && *nrad == 3) std::swap(rad[1], rad[2]);
+}
+
+void push_pass_twiddles(std::vector<cd>& out, int Ns, int R, bool cmp) {
+    if (cmp) {
+        for (int r = 1; r < R; r *= 2)
+            for (int k = 0; k < Ns; ++k) out.push_back(root_of_unity((long long)k * r, (long long)Ns * R));
+    } else {
+        for (int k = 0; k < Ns; ++k)
+            for (int r = 1; r < R; ++r) out.push_back(root_of_unity((long long)k * r, (long long)Ns * R));
+    }
+}
+
+// Per-pass Stockham twiddle tables of a 2^m-point FFT (radix order reversed if rev),
+// concatenated: pass q >= 1 owns Ns_q x (R_q - 1) entries T[k][r-1] = exp(-2 pi i k r / (Ns_q R_q))
+// (must match tw_pass_off() in rsp_kernels.hip).  Compact tables (cmp): r = 1, 2, 4, 8 only,
+// stored column-major, [i][k] = T[k][2^i] (load_tw in rsp_kernels.hip).
+// The angle's numerator is reduced modulo the period first, so every entry is the correctly
+// rounded double of the exact root of unity's angle.
+void build_pass_twiddles(int m, std::vector<cd>& out, bool rev = false, bool cmp = false, bool pal = false) {
+    int nrad, rad[8];
+    radix_plan(m, &nrad, rad, pal);
+    if (rev) std::reverse(rad, rad + nrad);
+    int Ns = 1;
+    for (int q = 0; q < nrad; ++q) {
+        const int R = rad[q];
+        if (q > 0) push_pass_twiddles(out, Ns, R, cmp);
+        Ns *= R;
+    }
+}
+
+// Mixed-radix overlap-save block M = 16 x R1 x 16 (k2_fft_job_mix): a palindrome, so the
+// inverse table (reversed radices) is the forward one and only the forward table is stored.
+void build_mix_twiddles(int R0, int R1, std::vector<cd>& out, bool cmp) {
+    const int rad[3] = {R0, R1, R0};
+    int Ns = 1;
+    for (int q = 0; q < 3; ++q) {
+        const int R = rad[q];
+        if (q > 0) push_pass_twiddles(out, Ns, R, cmp);
+        Ns *= R;
+    }
+}
+
+struct Interval { int lo, hi; };
+
+// The overlap-save block sizes whose twiddle tables twM already holds, and their offsets in it
+struct TwiddleSets {
+    std::vector<int> sizes, offs;
+};
+
+// ---- pulse-compression segments (fsf:105-126) ---------------------------------------------
+
+int build_fir_segment(SegDesc& s, const rsp_precomputed* pre, int N, int g1, std::vector<double>& taps) {
+    s.type = 0;
+    s.ga = 0; s.gb = g1;
+    s.seg_lo = pre->seg_start_narrow - 1;
+    if (s.seg_lo < 0 || s.seg_lo >= N) return fail(RSP_ERR_INVALID, "seg_start_narrow out of range");
+    s.Ls = N - s.seg_lo;
+    s.ntaps = pre->n_MF_narrow;
+    s.delay = pre->fir_delay;
+    if (s.ntaps < 1) return fail(RSP_ERR_INVALID, "empty MF_narrow");
+    int lo = INT32_MAX, hi = -1;
+    for (int gg = 0; gg < g1; ++gg) {
+        int kk = (gg + s.delay) % s.Ls;
+        if (kk < 0) kk += s.Ls;
+        const int top = s.seg_lo + kk;
+        const int bot = std::max(s.seg_lo, top - s.ntaps + 1);
+        lo = std::min(lo, bot);
+        hi = std::max(hi, top);
+    }
+    s.lo = lo; s.hi = hi;
+    s.taps_off = (int)taps.size();
+    for (int j = 0; j < s.ntaps; ++j) taps.push_back(pre->MF_narrow[j]);
+    return RSP_OK;
+}
+
+int build_fft_segment(SegDesc& s, const double* mf_fft, int Nfft, int N, int ga, int gb, int seg_lo,
+                      std::vector<cd>& H, std::vector<cd>& twM, TwiddleSets& tw, const char* name) {
+    std::vector<cd> h(Nfft);
+    for (int i = 0; i < Nfft; ++i) h[i] = cd(mf_fft[2 * i], mf_fft[2 * i + 1]);
+    fft_d(h, +1);
+    double hmax = 0;
+    for (auto& v : h) { v /= (double)Nfft; hmax = std::max(hmax, std::abs(v)); }
+    if (hmax == 0) return fail(RSP_ERR_INVALID, "%s matched filter is all zero", name);
+    int Lh = 0;
+    for (int i = 0; i < Nfft; ++i) if (std::abs(h[i]) > 1e-10 * hmax) Lh = i + 1;
+    if (gb > Nfft)
+        return fail(RSP_ERR_INVALID, "%s gates end at %d beyond N_fft %d (fsf:124-125 index out of range)", name, gb, Nfft);
+    const int Ls = std::min(N - seg_lo, Nfft);   // fft(seg, Nfft) truncates or pads
+    if (ga < Lh - 1 && Ls + (Lh - 1 - ga) > Nfft)
+        return fail(RSP_ERR_UNSUPPORTED, "%s segment: circular aliasing reaches kept gates (L_s=%d L_h=%d N_fft=%d)", name, Ls, Lh, Nfft);
+    s.type = 1;
+    s.ga = ga; s.gb = gb; s.seg_lo = seg_lo;
+    s.Lh = Lh;
+    s.lo = std::max(seg_lo, seg_lo + ga - (Lh - 1));
+    s.hi = std::min(seg_lo + Ls - 1, seg_lo + gb - 1);
+    // overlap-save block size M = 2^k <= 2048 (so that a workgroup owns >= 2 adjacent rows:
+    // 128 B contiguous loads of z), the mixed-radix 2560 = 16 x 10 x 16 (one row per workgroup)
+    // or 4096 = 16 x 16 x 16 (one row per 4096-point workgroup: x4's 5 956-gate long segment in
+    // 2 blocks instead of 5 x 2048); cost model blocks * M * (log2 M + 2)
+    const int nout = gb - ga;
+    double best = 1e300;
+    int bestM = 0;
+    const int cand[] = {64, 128, 256, 512, 1024, 2048, 2560, 4096};
+    for (int M : cand) {
+        const int V = M - Lh + 1;
+        if (V < 1) continue;
+        const int nb = (nout + V - 1) / V;
+        const double cost = (double)nb * M * (std::log2((double)M) + 2);
+        if (cost < best * 0.999) { best = cost; bestM = M; }
+    }
+    if (!bestM) {
+        int maxM = 0;
+        for (int M : cand) maxM = std::max(maxM, M);
+        return fail(RSP_ERR_UNSUPPORTED, "%s filter length %d exceeds the largest overlap-save block (%d points)", name, Lh,
+                    maxM);
+    }
+    const int M = bestM;
+    const bool mix = !is_pow2(M);
+    s.M = M; s.logM = mix ? 0 : ilog2i(M); s.V = M - Lh + 1;
+    s.nblocks = (nout + s.V - 1) / s.V;
+    // spectrum of h zero-padded to M, natural order, 1/M folded in
+    std::vector<cd> hm(M, 0.0);
+    for (int i = 0; i < Lh; ++i) hm[i] = h[i];
+    fft_d(hm, -1);
+    s.H_off = (int)H.size();
+    for (auto& v : hm) H.push_back(v / (double)M);
+    int ti = -1;
+    for (size_t q = 0; q < tw.sizes.size(); ++q) if (tw.sizes[q] == M) ti = (int)q;
+    if (ti < 0) {
+        tw.sizes.push_back(M);
+        tw.offs.push_back((int)twM.size());
+        if (mix) {
+            build_mix_twiddles(16, M / 256, twM, true);
+        } else {
+            build_pass_twiddles(s.logM, twM, false, true, true);   // forward FFT (compact rows, palindromic plan)
+            build_pass_twiddles(s.logM, twM, true, true, true);    // inverse FFT (reversed radices)
+        }
+        ti = (int)tw.sizes.size() - 1;
+    }
+    s.tw_off = tw.offs[ti];
+    return RSP_OK;
+}
+
+// The segments of the stitched row with their taps, spectra and twiddles; the K2 workgroup size
+// and each segment's rows per workgroup; the union U of the sample windows the segments read and
+// each segment's offset into the compacted samples (K1 processes only these).
+int derive_segments(const rsp_sig_config* cfg, const rsp_precomputed* pre, PlanHost& h, std::vector<Interval>& U) {
+    Geometry& g = h.g;
+    const int N = cfg->point_PRT;
+    const int g1 = pre->N_gate_narrow, g2 = pre->N_gate_medium, g3 = pre->N_gate_long, G = pre->N_total_gate;
+    const bool f64 = g.prec == RSP_PREC_F64;
+    TwiddleSets tw;
+    int rc;
+    if (g1 > 0) {
+        SegDesc s{};
+        if ((rc = build_fir_segment(s, pre, N, g1, h.taps))) return rc;
+        h.segs.push_back(s);
+    }
+    if (g2 > 0) {
+        SegDesc s{};
+        if ((rc = build_fft_segment(s, pre->MF_medium_fft, pre->N_fft_med, N, g1, g1 + g2, pre->seg_start_medium - 1, h.H,
+                                    h.twM, tw, "medium")))
+            return rc;
+        h.segs.push_back(s);
+    }
+    if (g3 > 0) {
+        SegDesc s{};
+        if ((rc = build_fft_segment(s, pre->MF_long_fft, pre->N_fft_long, N, g1 + g2, G, pre->seg_start_long - 1, h.H, h.twM,
+                                    tw, "long")))
+            return rc;
+        h.segs.push_back(s);
+    }
+    // K2 workgroup size in LDS points: a complex-double plan with a 2560-point block sizes every
+    // workgroup for it (40 KB of LDS, no pads: 4 per CU, k2_pc's 128-VGPR budget), power-of-two
+    // blocks then holding 2048 / M rows; otherwise RSP_K2_POINTS (4096: 2 per CU in complex double)
+    g.k2_pts = RSP_K2_POINTS;
+    for (auto& s : h.segs)
+        if (f64 && s.type == 1 && s.M == 2560) g.k2_pts = RSP_K2_MIXPTS;
+    for (auto& s : h.segs)   // a 4096-point block needs the 4096-point workgroups (2 per CU)
+        if (s.type == 1 && s.M == 4096) g.k2_pts = RSP_K2_POINTS;
+    // the narrow (direct-FIR) segment stages whole rows in the workgroup's LDS: when its window
+    // does not fit a 2560-point workgroup the plan falls back to RSP_K2_POINTS workgroups (2 per
+    // CU; k2_pc runs the 2560-point block in either sizing)
+    for (auto& s : h.segs)
+        if (s.type == 0 && g.k2_pts != RSP_K2_POINTS) {
+            const int WP = s.hi - s.lo + 1 + s.ntaps - 1;
+            if (WP + (s.ntaps + 1) / 2 > g.k2_pts) g.k2_pts = RSP_K2_POINTS;   // no pads at 2560
+        }
+    std::vector<Interval> need;
+    for (auto& s : h.segs) {
+        if (s.seg_lo < 0 || s.seg_lo >= N) return fail(RSP_ERR_INVALID, "segment start out of range");
+        if (s.hi >= s.lo) need.push_back({s.lo, s.hi});
+        if (s.type == 1) {
+            const int pts = (g.k2_pts == RSP_K2_POINTS) ? RSP_K2_POINTS : 2048;   // k2_pc's PTS
+            s.rows_per_wg = s.M == 2560 ? 1 : std::max(1, pts / s.M);
+        } else {
+            // up to 8 rows per workgroup (measured best of 1/2/4/8 at x2), within the workgroup's
+            // LDS: rows * WP complex + the taps (ntaps reals = ntaps / 2 complex)
+            const int WP = s.hi - s.lo + 1 + s.ntaps - 1;   // staged row: ntaps - 1 leading zeros
+            const int lds_c = g.k2_pts == RSP_K2_POINTS ? k2_lds_data(g.k2_pts, RSP_K2_SH) : g.k2_pts;   // k2_pc's LDS
+            s.rows_per_wg = std::max(1, std::min(8, (lds_c - (s.ntaps + 1) / 2) / WP));
+            if (WP * s.rows_per_wg + (s.ntaps + 1) / 2 > lds_c)
+                return fail(RSP_ERR_UNSUPPORTED, "narrow segment window %d samples too long", s.hi - s.lo + 1);
+        }
+    }
+    // union of needed fast-time windows -> compacted sample list
+    std::sort(need.begin(), need.end(), [](const Interval& a, const Interval& b) { return a.lo < b.lo; });
+    for (auto& iv : need) {
+        if (!U.empty() && iv.lo <= U.back().hi + 1) U.back().hi = std::max(U.back().hi, iv.hi);
+        else U.push_back(iv);
+    }
+    std::vector<int> nof;
+    for (auto& iv : U) for (int n = iv.lo; n <= iv.hi; ++n) nof.push_back(n);
+    g.nU = (int)nof.size();
+    for (auto& s : h.segs) {
+        if (s.hi < s.lo) { s.off = 0; continue; }
+        s.off = (int)(std::lower_bound(nof.begin(), nof.end(), s.lo) - nof.begin());
+    }
+    return RSP_OK;
+}
+
+// ---- K1 tile --------------------------------------------------------------------------------
+// NT samples per [P][NT] slab.  complex64: LDS tile <= 80 KB (2 workgroups per CU for the tiled
+// K1; the persistent K1 double-buffers it) and B*NT*P <= 8192 (16 FFT points per thread);
+// complex128: the same bytes (NT halved) and B*NT*P <= 4096.  Also the slow-time transform's
+// factorisation and row stride, the z layout and the sample intervals U as kernel arguments.
+int derive_k1_tile(Geometry& g, const std::vector<Interval>& U) {
+    const int B = g.B, P = g.P;
+    const bool f64 = g.prec == RSP_PREC_F64;
+    const size_t esz = cplx_bytes(g);
+    g.pow2P = is_pow2(P) && P >= 16 && P <= 512;   // Stockham range of k1_fft; else a DFT
+    // other P = R Q (R = 2 or 4, Q odd >= 3; the reference's 332 = 4 x 83): the factored DFT
+    // when one tile column per beam and its tables fit the LDS; otherwise the direct DFT
+    g.rqR = g.rqQ = g.twq_elems = 0;
+    if (!g.pow2P) {
+        int R = 1;
+        while (P % (2 * R) == 0) R *= 2;
+        const int Q = P / R, Qh = (Q - 1) / 2;
+        const int twq = (Qh + 1 + RQ_RK - 1) / RQ_RK * Qh * RQ_RK;
+        if (R <= 4 && Q >= 3 && ((size_t)B * (P + 15) + rq_table_elems(twq, P)) * esz <= RSP_LDS_BYTES) {
+            g.rqR = R;
+            g.rqQ = Q;
+            g.twq_elems = twq;
+        }
+    }
+    // pow2: + one pad per 16 (K1_SH), see rsp_kernels.hip; factored DFT: the row stride in
+    // P..P+15 whose pass-2 reads are conflict-free (rq_pick_stride)
+    g.Ppad = g.pow2P ? P + P / 16 : (g.rqQ ? rq_pick_stride(g.rqR, g.rqQ, B) : P + 4);
+    const int max_pts = f64 ? 4096 : 8192;
+    const size_t tile_cap = f64 ? 72 * 1024 : 80 * 1024;
+    const size_t tab_bytes = g.rqQ ? (size_t)rq_table_elems(g.twq_elems, P) * esz : 0;   // k1_dft_rq's LDS tables
+    g.NT = 8;
+    while (g.NT > 1 && ((size_t)B * g.NT * g.Ppad * esz > tile_cap || (g.pow2P && B * g.NT * P > max_pts) ||
+                        (size_t)B * g.NT * g.Ppad * esz + tab_bytes > RSP_LDS_BYTES))
+        g.NT >>= 1;
+    if ((size_t)B * g.NT * g.Ppad * esz + tab_bytes > RSP_LDS_BYTES || (g.pow2P && B * g.NT * P > 8192))
+        return fail(RSP_ERR_UNSUPPORTED, "B*P too large for the slow-time FFT tile");
+    g.ntiles = (g.nU + g.NT - 1) / g.NT;
+    // z chunks: NT samples (one K1 tile) per row slab
+    g.NZ = g.NT;
+    g.nzc = (g.nU + g.NZ - 1) / g.NZ;
+    if ((int)U.size() > RSP_MAX_IVL) return fail(RSP_ERR_UNSUPPORTED, "too many sample intervals");
+    g.nivl = (int)U.size();
+    for (int q = 0, st = 0; q < g.nivl; ++q) {
+        g.ivl_lo[q] = U[q].lo;
+        g.ivl_start[q] = st;
+        st += U[q].hi - U[q].lo + 1;
+    }
+    if (g.pow2P) g.logP = ilog2i(P);
+    if (16 * (size_t)g.Ppad * esz > RSP_LDS_BYTES || (g.pow2P && 16 * P > 8192))   // 16 columns: the stage-2 path's tile
+        return fail(RSP_ERR_UNSUPPORTED, "prtNum %d too large", P);
+    return RSP_OK;
+}
+
+// ---- K2 jobs and dispatch order -------------------------------------------------------------
+int derive_k2_jobs(PlanHost& h) {
+    Geometry& g = h.g;
+    const int rows_total = g.B * g.P;
+    int wg = 0;
+    for (size_t si = 0; si < h.segs.size(); ++si) {
+        const SegDesc& s = h.segs[si];
+        const int nwg = (rows_total + s.rows_per_wg - 1) / s.rows_per_wg;
+        const int nbl = (s.type == 1) ? s.nblocks : 1;
+        for (int blk = 0; blk < nbl; ++blk) {
+            h.jobs.push_back(K2Job{(int)si, blk, wg, nwg});
+            wg += nwg;
+        }
+    }
+    g.nseg = (int)h.segs.size();
+    g.njobs = (int)h.jobs.size();
+    if (g.nseg > RSP_MAX_SEG || g.njobs > RSP_MAX_JOBS)
+        return fail(RSP_ERR_UNSUPPORTED, "%d overlap-save jobs exceed %d", g.njobs, RSP_MAX_JOBS);
+    for (int q = 0; q < g.nseg; ++q) g.segs[q] = h.segs[q];
+    for (int q = 0; q < g.njobs; ++q) g.jobs[q] = h.jobs[q];
+    g.nwg_k2 = wg;
+    return RSP_OK;
+}
+
+// K2 dispatch order.  (1) Workgroups of a job covering adjacent rows form groups of gs
+// (below), at key (i + 1/2) / ngroups_j, so that the narrow FIR, medium and long jobs are
+// interleaved in proportion through the launch.  (2) Workgroups go to the 8 XCDs
+// round-robin by dispatch position, so the groups are laid out 8 at a time: positions
+// 8 (gs c + m) + x hold member m of group 8c + x -- every row of a group on one XCD, whose
+// L2 then serves the rest of every 128-B z line the first one fetched.  A z line holds
+// 128 / (NT esz) adjacent rows, a workgroup rows_per_wg of them, so gs = the most
+// workgroups one line spans over the jobs (x2: NT = 4, one-row long blocks -> 2; x4:
+// NT = 1 -> 8).  Workgroups left over go last.
+int derive_k2_order(PlanHost& h) {
+    const Geometry& g = h.g;
+    const int esz = (int)cplx_bytes(g);
+    int gs = 1;
+    for (const K2Job& jb : h.jobs) {
+        const int rw = std::max(h.segs[jb.seg].rows_per_wg, 1);
+        gs = std::max(gs, std::min(8, 128 / std::max(rw * g.NZ * esz, 1)));
+    }
+    // (3) The overlap-save blocks of one row read overlapping sample windows (Lh - 1 samples
+    // shared by neighbouring blocks: x4's long segment, 4 blocks): the groups of all blocks of
+    // the same rows form one unit, placed on one XCD back to back, so that the shared lines
+    // are L2 hits instead of second HBM fetches.  Units go to the XCD with the shortest queue
+    // (round-robin when they are all the same size, x2) and the queues are interleaved:
+    // dispatch position 8 s + x is the s-th workgroup of XCD x's queue.
+    struct Unit { double key; std::vector<int> wgs; };
+    std::vector<Unit> units;
+    std::vector<int> single;
+    for (int si = 0; si < (int)h.segs.size(); ++si) {
+        std::vector<const K2Job*> blks;
+        for (const K2Job& jb : h.jobs)
+            if (jb.seg == si) blks.push_back(&jb);
+        if (blks.empty()) continue;
+        const int wc = blks[0]->wg_count, ng = wc / gs;   // every block of a segment covers all rows
+        for (int i = 0; i < ng; ++i) {
+            Unit u{(i + 0.5) / ng, {}};
+            for (const K2Job* jb : blks)
+                for (int m = 0; m < gs; ++m) u.wgs.push_back(jb->wg_begin + gs * i + m);
+            units.push_back(std::move(u));
+        }
+        for (const K2Job* jb : blks)
+            for (int w = ng * gs; w < wc; ++w) single.push_back(jb->wg_begin + w);
+    }
+    std::stable_sort(units.begin(), units.end(), [](const Unit& x, const Unit& y) { return x.key < y.key; });
+    std::vector<int> q[8];
+    for (const Unit& u : units) {
+        int x = 0;
+        for (int c = 1; c < 8; ++c)
+            if (q[c].size() < q[x].size()) x = c;
+        q[x].insert(q[x].end(), u.wgs.begin(), u.wgs.end());
+    }
+    std::vector<int>& order = h.k2order;
+    size_t qmax = 0;
+    for (auto& v : q) qmax = std::max(qmax, v.size());
+    for (size_t sl = 0; sl < qmax; ++sl)
+        for (int x = 0; x < 8; ++x)
+            if (sl < q[x].size()) order.push_back(q[x][sl]);
+    for (int w : single) order.push_back(w);
+    if ((int)order.size() != g.nwg_k2)
+        return fail(RSP_ERR_INVALID, "K2 dispatch order covers %d of %d workgroups", (int)order.size(), g.nwg_k2);
+    return RSP_OK;
+}
+
+// ---- K3 tiling ------------------------------------------------------------------------------
+#define RSP_K3_TILE_KB 48   // KB of S per K3 tile (48: 2 Doppler bands at P = 128, 3 workgroups per CU)
+#define RSP_K3_RT_C128 32   // K3 tile width in range cells, complex double
+int derive_k3_tiling(Geometry& g) {
+    const size_t rsz = cplx_bytes(g) / 2;
+    g.cfar_hR = (std::max(g.refR + g.guardR, 2) + 3) & ~3;   // halo, multiple of 4 (16-B tile loads)
+    // tiles of RT range cells (64 complex single / 32 complex double: the fast path) x a band of
+    // Doppler rows, <= RSP_K3_TILE_KB of S per tile (48 KB: 3 workgroups per CU; at P = 128 two
+    // bands measured 78 vs 85 us per 8 x2 frames for one band at 2 workgroups per CU): at P = 128
+    // one band holds every row; longer P (x4's 256) splits the rows into bands, each with the
+    // rV + gV window rows on either side
+    g.cfar_RT = rsz == 4 ? 64 : RSP_K3_RT_C128;
+    // LDS row stride, 16-B aligned; complex double + 2 cells (bank spread, k3_cfar).
+    // k3_cfar's compile-time path (the reference's 5/5/10/10) holds only the band's own cells
+    // (its prefilter reads whichever range slice lies in the tile; the rare survivors and S9
+    // read the windows from the magnitude maps)
+    const bool k3_nohalo = k3_fast_params(g);
+    const int hx = k3_nohalo ? 0 : 2;
+    g.cfar_W = ((g.cfar_RT + hx * g.cfar_hR + 3) & ~3) + (rsz == 8 ? 2 : 0);
+    const int hV = g.refV + g.guardV, ncut = std::max(g.P - 2 * hV, 1);
+    const int hrows = k3_nohalo ? 0 : 2 * hV;
+    const int rows_max = (int)((RSP_K3_TILE_KB * 1024) / ((size_t)g.cfar_W * rsz));
+    if (rows_max - hrows < 1) return fail(RSP_ERR_UNSUPPORTED, "CFAR window %d x %d exceeds the LDS tile", hV, g.cfar_hR);
+    g.cfar_nband = (ncut + rows_max - hrows - 1) / (rows_max - hrows);
+    g.cfar_VB = (ncut + g.cfar_nband - 1) / g.cfar_nband;
+    g.cfar_rows = std::min(g.P, g.cfar_VB + hrows);
+    return RSP_OK;
+}
+
+// ---- tables ---------------------------------------------------------------------------------
+// (taps, H and twM were built with their segments)
+void build_tables(const rsp_precomputed* pre, PlanHost& h) {
+    Geometry& g = h.g;
+    const int C = g.C, B = g.B, P = g.P, G = g.G;
+    // conj(W): y = x * W' (fsf:95), W column-major B x C
+    auto wconj = [&](int b, int c) {
+        const size_t i = (size_t)b + (size_t)B * c;
+        return cd(pre->DBF_coeffs_data_C[2 * i], -pre->DBF_coeffs_data_C[2 * i + 1]);
+    };
+    // per-lane A operands of the DBF MFMA (k1_dbf_mtd): lane l holds A[row l&15][channel 4j + l>>4];
+    // row m: beam mb*8 + (m&7), m<8 -> Re(y), m>=8 -> Im(y); y = sum_c conj(W[b][c]) x_c (fsf:95)
+    const K1Cfg kc = k1_cfg(C, B);
+    const int mblk = kc.MB, nj = kc.NJ;
+    h.atab.assign((size_t)mblk * nj * 2 * 64, 0.0);
+    for (int mb = 0; mb < mblk; ++mb)
+        for (int j = 0; j < nj; ++j)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int m = lane & 15, c = 4 * j + (lane >> 4), b = mb * 8 + (m & 7);
+                double wr = 0, wi = 0;
+                if (b < B && c < C) {
+                    wr = wconj(b, c).real();
+                    wi = wconj(b, c).imag();
+                }
+                const bool im = m >= 8;
+                h.atab[((mb * nj + j) * 2 + 0) * 64 + lane] = im ? wi : wr;    // coefficient of Re(x_c)
+                h.atab[((mb * nj + j) * 2 + 1) * 64 + lane] = im ? wr : -wi;   // coefficient of Im(x_c)
+            }
+    h.twP.resize(P);
+    if (g.pow2P) build_pass_twiddles(g.logP, h.twPp);
+    g.twPp_elems = (int)h.twPp.size();
+    if (g.pow2P && P >= 64 && P <= 256)   // k1_fft_dif (k1_dif: P = 64 .. 256): compact pass-A twiddles, column-major [i][n2]
+        for (int i = 0; i < 4; ++i)
+            for (int n2 = 0; n2 < P / 16; ++n2) h.twD.push_back(root_of_unity((long long)n2 << i, P));
+    for (int i = 0; i < P; ++i) h.twP[i] = root_of_unity(i, P);
+    // k1_dft_rq's pass-2 table: [fset][n - 1][r] = (cos, sin)(2 pi k1 n / Q), k1 = RQ_RK fset + r
+    // (zero past (Q - 1) / 2)
+    if (g.rqQ) {
+        const int Q = g.rqQ, Qh = (Q - 1) / 2, nfs = g.twq_elems / (Qh * RQ_RK);
+        for (int fs = 0; fs < nfs; ++fs)
+            for (int n = 1; n <= Qh; ++n)
+                for (int r = 0; r < RQ_RK; ++r) {
+                    const int k1 = fs * RQ_RK + r;
+                    const cd w = k1 <= Qh ? root_of_unity((long long)k1 * n, Q) : cd(0.0, 0.0);
+                    h.twQ.push_back(cd(w.real(), -w.imag()));   // exp(-i theta) -> (cos, sin) theta
+                }
+    }
+    h.win.assign(pre->MTD_win, pre->MTD_win + P);
+    h.range_axis.assign(pre->range_axis, pre->range_axis + G);
+    h.velocity_axis.assign(pre->velocity_axis, pre->velocity_axis + P);
+    h.beam_angles.assign(pre->beam_angles_deg, pre->beam_angles_deg + B);
+    h.klut.assign(std::max(B - 1, 1), 0.0);
+    for (int i = 0; i + 1 < B; ++i) h.klut[i] = pre->k_slopes_LUT[i];
+}
+
+// ---- route helpers --------------------------------------------------------------------------
+
+// sub-tiles per wave of the persistent K1 (one load round per tile): TPW, or 2 TPW
+int k1p_tpw(const Geometry& g) {
+    const int pt = g.prec == RSP_PREC_F64 ? 16 : 32;   // pulses per MFMA sub-tile
+    const int tpw = k1_cfg(g.C, g.B).TPW;
+    const int need = (g.NT * (g.P / pt) + (K1_THREADS / 64) - 1) / (K1_THREADS / 64);
+    return need <= tpw ? tpw : (need <= 2 * tpw ? 2 * tpw : 0);
+}
+
+// sub-tiles per wave of the factored-DFT K1 (one load round per tile): ceil(sub-tiles / 8) <= 4
+int k1q_tpw(const Geometry& g) {
+    const int pt = g.prec == RSP_PREC_F64 ? 16 : 32;
+    const int need = (g.NT * ((g.P + pt - 1) / pt) + (K1_THREADS / 64) - 1) / (K1_THREADS / 64);
+    return need <= 4 ? need : 0;
+}
+
+bool k1q_fits(const Geometry& g) {
+    return !g.pow2P && g.rqQ > 0 && k1q_tpw(g) > 0 && k1q_lds(g) <= RSP_LDS_BYTES && g.ncu > 0 && !g.k1_tiled;
+}
+
+}  // namespace
+
+size_t k1_tiled_lds(const Geometry& g, bool rq) {
+    return ((size_t)g.B * g.NT * g.Ppad + (rq ? rq_table_elems(g.twq_elems, g.P) : g.P)) * cplx_bytes(g);
+}
+
+// tile buffers x 2 | FFT twiddles (<= P) | two MFMA row blocks' Atab when B > 8 (k1p_dbf_mtd ALDS)
+size_t k1p_lds(const Geometry& g) {
+    return ((size_t)2 * g.B * g.NT * g.Ppad + g.P) * cplx_bytes(g) +
+           (g.B > 8 ? (size_t)2 * k1_cfg(g.C, g.B).NJ * 2 * 64 * (cplx_bytes(g) / 2) : 0);
+}
+
+// tile | twQ | W_P^i | Atab (MB x NJ x 2 x 64 <= 1024 reals: CP <= 16)
+size_t k1q_lds(const Geometry& g) {
+    return ((size_t)g.B * g.NT * g.Ppad + rq_table_elems(g.twq_elems, g.P)) * cplx_bytes(g) + (size_t)1024 * (cplx_bytes(g) / 2);
+}
+
+size_t mtd_cols_lds(const Geometry& g) { return ((size_t)16 * g.Ppad + g.P) * cplx_bytes(g); }
+
+bool k1_persistent_fits(const Geometry& g) {
+    const int pts = g.prec == RSP_PREC_F64 ? 8 : 16;   // FFT points per thread (k1p_pts)
+    return g.pow2P && g.logP >= 6 && g.logP <= 8 && k1p_tpw(g) > 0 && k1p_lds(g) <= RSP_LDS_BYTES &&
+           g.B * g.NT * g.P <= pts * K1_THREADS && g.ncu > 0 && !g.k1_tiled;
+}
+
+K1Route k1_route(const Geometry& g, int mode) {
+    const K1Cfg kc = k1_cfg(g.C, g.B);
+    K1Route r;
+    r.lgp2 = g.pow2P ? g.logP : 0;   // k_mtd_cols<T, LGP>: the Stockham passes for P = 16 .. 512, else the direct DFT
+    r.kernel = K1K_TILED;
+    r.tpw = 0;
+    r.transform = g.pow2P ? (k1_dif(g.logP, kc.CP) ? K1X_DIF : K1X_STOCKHAM) : (g.rqQ > 0 ? K1X_FACTORED : K1X_DIRECT);
+    if (mode == 3 && k1_persistent_fits(g)) {
+        // 2 TPW sub-tiles per wave only where an instantiation exists (K1Cfg::twice_ok); otherwise
+        // the tiled kernel
+        const bool twice = k1p_tpw(g) == 2 * kc.TPW;
+        if (!twice || kc.twice_ok) {
+            r.kernel = K1K_PERSISTENT;
+            r.tpw = twice ? 2 * kc.TPW : kc.TPW;
+            return r;
+        }
+    }
+    // the persistent factored-DFT K1 for C <= 16 when one load round of at most 16 16-B cube loads
+    // per lane covers a tile (register budget: no scratch); otherwise the tiled kernel
+    if (kc.CP <= 16 && mode == 3 && k1q_fits(g) && k1q_tpw(g) * kc.NJ <= 16) {
+        r.kernel = K1K_PERSISTENT_FACTORED;
+        r.tpw = k1q_tpw(g);
+    }
+    return r;
+}
+
+int rsp_plan_check_args(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params* cluster,
+                        const rsp_precomputed* pre, const rsp_plan_options* opt) {
+    if (!cfg || !cfar || !cluster || !pre || !opt) return fail(RSP_ERR_INVALID, "null argument");
+    if (opt->precision != RSP_C64 && opt->precision != RSP_C128)
+        return fail(RSP_ERR_INVALID, "precision must be RSP_C128 or RSP_C64, got %d", opt->precision);
+    if (opt->flags & ~(RSP_PLAN_K1_TILED | RSP_PLAN_MONOPULSE_COMPLEX))
+        return fail(RSP_ERR_INVALID, "unknown plan flags 0x%x", opt->flags);
+    const int C = cfg->channel_num, B = cfg->beam_num, P = cfg->prtNum, N = cfg->point_PRT;
+    const int g1 = pre->N_gate_narrow, g2 = pre->N_gate_medium, g3 = pre->N_gate_long, G = pre->N_total_gate;
+    if (C < 1 || C > 32 || B < 1 || B > 16 || P < 2 || N < 2)
+        return fail(RSP_ERR_INVALID, "bad sizes C=%d B=%d P=%d N=%d (1<=C<=32, 1<=B<=16)", C, B, P, N);
+    if (P % 2) return fail(RSP_ERR_UNSUPPORTED, "odd prtNum %d (complex64 pulse pairs are loaded as 16 B)", P);
+    if (g1 < 0 || g2 < 0 || g3 < 0 || G != g1 + g2 + g3 || G < 1) return fail(RSP_ERR_INVALID, "gate counts inconsistent");
+    if (!pre->DBF_coeffs_data_C || !pre->MF_narrow || !pre->MF_medium_fft || !pre->MF_long_fft || !pre->MTD_win ||
+        !pre->range_axis || !pre->velocity_axis || !pre->beam_angles_deg || (B > 1 && !pre->k_slopes_LUT))
+        return fail(RSP_ERR_INVALID, "precomputed_data field missing");
+    if (opt->frames_per_launch < 1 || opt->frames_per_launch > RSP_MAX_F)
+        return fail(RSP_ERR_INVALID, "frames_per_launch must be 1..%d", RSP_MAX_F);
+    const size_t esz = opt->precision == RSP_C128 ? 16 : 8;
+    if ((size_t)C * N * P * esz >= ((size_t)1 << 31))
+        return fail(RSP_ERR_UNSUPPORTED, "echo cube of %zu bytes: the kernels address one frame with 32-bit offsets (< 2 GB)",
+                    (size_t)C * N * P * esz);
+    return RSP_OK;
+}
+
+int rsp_plan_derive(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params*,
+                    const rsp_precomputed* pre, const rsp_plan_options* opt, int ncu, PlanHost* out) {
+    PlanHost& h = *out;
+    h = PlanHost();
+    Geometry& g = h.g;
+    const int C = cfg->channel_num, B = cfg->beam_num, P = cfg->prtNum, N = cfg->point_PRT, G = pre->N_total_gate;
+    g.prec = opt->precision == RSP_C128 ? RSP_PREC_F64 : RSP_PREC_F32;
+    g.k1_tiled = (opt->flags & RSP_PLAN_K1_TILED) ? 1 : 0;
+    g.mono_c = (opt->flags & RSP_PLAN_MONOPULSE_COMPLEX) ? 1 : 0;
+    g.C = C; g.B = B; g.P = P; g.N = N; g.G = G;
+    g.cpitch = N * P;
+    g.Gp = (G + 3) & ~3;
+    g.refR = cfar->refCells_R; g.guardR = cfar->guardCells_R; g.refV = cfar->refCells_V; g.guardV = cfar->guardCells_V;
+    g.T = cfar->T_CFAR;
+    g.max_dets = 1;   // per launch: the lane's list capacity (launch_batch)
+    g.ncu = ncu;
+    {   // the most detections a frame can have: every cell under test of every beam pair (fsf:192-213)
+        const int64_t nv = std::max(P - 2 * (g.refV + g.guardV), 0), nr = std::max(G - 2 * (g.refR + g.guardR), 0);
+        h.det_bound = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)std::max(B - 1, 0) * nv * nr, 1 << 30));
+    }
+    if (g.refR < 1 || g.refV < 1 || g.guardR < 0 || g.guardV < 0) return fail(RSP_ERR_INVALID, "bad CFAR window");
+    std::vector<Interval> U;
+    int rc;
+    if ((rc = derive_segments(cfg, pre, h, U)) || (rc = derive_k1_tile(g, U)) || (rc = derive_k2_jobs(h)) ||
+        (rc = derive_k3_tiling(g)))
+        return rc;
+    build_tables(pre, h);
+    if ((rc = derive_k2_order(h))) return rc;
+    h.z_elems = (size_t)B * g.nzc * g.NZ * P;
+    h.rdm_elems = (size_t)B * P * G;
+    h.mag_elems = (size_t)B * P * g.Gp;
+    return RSP_OK;
+}
+
+void rsp_fill_sizes(const Geometry& g, int det_bound, rsp_sizes* s) {
+    s->cube_elems = (int64_t)g.cpitch * g.C;
+    s->rdm_elems = (int64_t)g.P * g.G * g.B;
+    s->cfar_map_elems = (int64_t)g.P * g.G * std::max(g.B - 1, 0);
+    s->P = g.P; s->N = g.N; s->C = g.C; s->B = g.B; s->G = g.G;
+    s->used_samples = g.nU;
+    s->max_detections = det_bound;
+    s->n_stages = 3;
+    s->precision = g.prec == RSP_PREC_F64 ? RSP_C128 : RSP_C64;
+    s->elem_bytes = (int32_t)cplx_bytes(g);
+}
+
+void rsp_fill_k1_route(const Geometry& g, rsp_k1_route* out) {
+    static_assert(K1K_TILED == RSP_K1_KERNEL_TILED && K1K_PERSISTENT == RSP_K1_KERNEL_PERSISTENT &&
+                      K1K_PERSISTENT_FACTORED == RSP_K1_KERNEL_PERSISTENT_FACTORED &&
+                      K1X_STOCKHAM == RSP_K1_TRANSFORM_STOCKHAM && K1X_DIF == RSP_K1_TRANSFORM_DIF &&
+                      K1X_FACTORED == RSP_K1_TRANSFORM_FACTORED && K1X_DIRECT == RSP_K1_TRANSFORM_DIRECT,
+                  "K1Route's values are rsp.h's");
+    const K1Route r = k1_route(g, 3);   // the frame chain's launch (launch_k1 mode 3)
+    out->kernel = r.kernel;
+    out->transform = r.transform;
+    out->R = g.rqR;
+    out->Q = g.rqQ;
+    out->NT = g.NT;
+    out->Ppad = g.Ppad;
+    out->tiles_per_wave = r.tpw;
+    out->stage2_lgp = r.lgp2;
+}
+
+extern "C" int32_t rsp_plan_describe(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params* cluster,
+                                     const rsp_precomputed* pre, const rsp_plan_options* opt, int32_t ncu, rsp_sizes* sizes,
+                                     rsp_k1_route* route) {
+    int rc = rsp_plan_check_args(cfg, cfar, cluster, pre, opt);
+    if (rc) return rc;
+    PlanHost h;
+    if ((rc = rsp_plan_derive(cfg, cfar, cluster, pre, opt, ncu, &h))) return rc;
+    if (sizes) rsp_fill_sizes(h.g, h.det_bound, sizes);
+    if (route) rsp_fill_k1_route(h.g, route);
+    return RSP_OK;
+}

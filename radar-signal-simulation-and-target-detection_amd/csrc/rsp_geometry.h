@@ -1,0 +1,207 @@
+// rsp_geometry.h -- the device-free half of a plan: the descriptors the kernels take as arguments,
+// every sizing and routing decision (sample windows, overlap-save blocks, the K1 tile and route,
+// the K2 job list and dispatch order, the K3 tiling) and the host tables a plan uploads.  Plain
+// C++17: no HIP header, so that rsp_geometry.cpp builds and runs (and is sanitized) without a GPU.
+#pragma once
+#include "rsp.h"
+
+#include <complex>
+#include <stddef.h>
+#include <stdint.h>
+#include <vector>
+
+// Helpers the kernels call too; empty under a plain C++ compiler.
+#ifdef __HIPCC__
+#define RSP_HD __host__ __device__
+#else
+#define RSP_HD
+#endif
+
+#define RSP_MAX_F 8          // frames batched per launch
+#define RSP_K2_POINTS 4096   // complex points per pulse-compression workgroup (Geometry::k2_pts)
+#define RSP_K2_MIXPTS 2560   // Geometry::k2_pts of a complex-double plan with a 2560-point block
+#define K1_THREADS 512       // threads per K1 workgroup (8 waves)
+
+// Arithmetic of a plan: every device buffer, table and operation of the chain is in one of
+// these.  PREC_F64 is MATLAB's complex double (the reference's arithmetic, fsf:47,92,101,131);
+// PREC_F32 is complex single (an explicitly narrower option).
+#define RSP_PREC_F32 0
+#define RSP_PREC_F64 1
+
+// LDS of a gfx950 compute unit: the most one workgroup can request.
+constexpr size_t RSP_LDS_BYTES = 160 * 1024;
+
+// Pulse-compression segment (fsf:105-126).  Output gates [ga, gb) of the stitched
+// row come from this segment.  x~(n) = x(n) for lo_eff <= n <= hi, else 0, where
+// [lo, hi] is the window of samples that reach a kept gate (plan-time analysis).
+struct SegDesc {
+    int type;        // 0 = direct FIR (narrow, fsf:111-112), 1 = FFT overlap-save (fsf:115-120)
+    int ga, gb;      // stitched gate range
+    int seg_lo;      // 0-based first sample of the segment (seg_start - 1)
+    int lo, hi;      // needed sample window (0-based, inclusive), lo >= seg_lo
+    int off;         // compacted sample index of `lo`
+    // direct FIR: y[g] = sum_j h[j] x~(seg_lo + k - j), k = (g + delay) mod Ls
+    int ntaps, delay, Ls, taps_off;
+    // FFT overlap-save: y[g] = sum_{j<Lh} h[j] x~(seg_lo + g - j), block size M = 2^logM,
+    // V = M-Lh+1 valid outputs per block
+    int Lh, M, logM, V, nblocks, H_off, tw_off;
+    int rows_per_wg;
+};
+
+// One group of pulse-compression workgroups: segment `seg`, overlap-save block `blk`.
+struct K2Job {
+    int seg, blk, wg_begin, wg_count;
+};
+
+#define RSP_MAX_SEG 3
+#define RSP_MAX_JOBS 16
+#define RSP_MAX_IVL 4
+
+struct Geometry {
+    int prec;        // RSP_PREC_F32 / RSP_PREC_F64
+    int C, B, P, N, G;
+    int cpitch;      // device cube channel pitch in complex samples (= N*P)
+    int Gp;          // row stride of the magnitude maps (G rounded up to 4)
+    int NT, nU, ntiles, Ppad;
+    int NZ, nzc;     // z layout: NZ compacted samples per (row, chunk) slab, nzc chunks per row
+    int twPp_elems;  // per-pass twiddles of the P-point FFT
+    int pow2P, logP;
+    // non-power-of-two P = rqR * rqQ (rqR = 2 or 4, rqQ odd >= 3): K1's factored slow-time DFT
+    // (k1_dft_rq); rqQ = 0: the direct O(P^2) DFT.  twq_elems = complex entries of its
+    // frequency-set twiddle table (DevConsts::twQ)
+    int rqR, rqQ, twq_elems;
+    int nseg, njobs, nwg_k2;
+    // complex points of LDS rows per pulse-compression workgroup: RSP_K2_POINTS, or 2560 in a
+    // complex-double plan with a 2560-point block (4 workgroups per CU: 40 KB of LDS each, no pads);
+    // power-of-two blocks then take 2048 / M rows
+    int k2_pts;
+    int cfar_RT, cfar_hR, cfar_W;
+    int cfar_VB, cfar_nband, cfar_rows;   // K3 Doppler bands: cells under test per band, bands, tile rows
+    int refR, guardR, refV, guardV;
+    double T;        // T_CFAR
+    int max_dets;    // detection-list capacity per frame of the launch (grows on demand, rsp_plan.cpp)
+    int ncu;         // compute units of the device (persistent K1 grid)
+    int k1_tiled;    // force the one-tile-per-workgroup K1 (RSP_PLAN_K1_TILED, parity tests)
+    int mono_c;      // S9 angle from the complex ratio of the RD map (RSP_PLAN_MONOPULSE_COMPLEX)
+    // used fast-time samples as <= RSP_MAX_IVL intervals: compacted n' in [ivl_start[q],
+    // ivl_start[q+1]) is sample ivl_lo[q] + n' - ivl_start[q] (kernel-argument lookup, no
+    // dependent global load before the cube loads)
+    int nivl, ivl_lo[RSP_MAX_IVL], ivl_start[RSP_MAX_IVL];
+    // pulse-compression segment and job tables travel as kernel arguments too
+    SegDesc segs[RSP_MAX_SEG];
+    K2Job jobs[RSP_MAX_JOBS];
+};
+// Geometry is a kernel argument: the host and the device compiler must lay it out alike.
+static_assert(sizeof(SegDesc) == 76 && sizeof(K2Job) == 16 && sizeof(Geometry) == 680, "kernel-argument layout");
+
+// K3's compile-time path: the reference's cfar_params (v8:45-46) and a 32/64-cell tile
+RSP_HD inline bool k3_fast_params(const Geometry& g) {
+    return g.refR == 5 && g.refV == 5 && g.guardR == 10 && g.guardV == 10 && (g.cfar_RT == 32 || g.cfar_RT == 64);
+}
+
+// K3 tiles: range cells from the first cell under test rounded down to 4, cfar_RT per tile
+// (k3_cfar, launch_k3, rsp_profile_stages).
+RSP_HD inline int k3_ntiles(const Geometry& g) {
+    const int rc0 = g.refR + g.guardR;
+    return (g.G - rc0 - (rc0 & ~3) + g.cfar_RT - 1) / g.cfar_RT;
+}
+
+// Magnitude-map bytes K3 reads from HBM per frame (the K3 stage's algorithmic bytes): on the
+// fast path the halo-less tiles hold only the Doppler rows under test, P - 2 (refV + guardV), over
+// the tiled range columns (first cell under test rounded down to 4, k3_ntiles * cfar_RT cells,
+// clipped to G); each beam's map is read by two pairs, the second read an L2 hit (XCD-aware
+// order).  The general path reads whole maps.  bench.py / tests/test_bench_args.py restate it.
+RSP_HD inline long long k3_map_bytes(const Geometry& g, int real_bytes) {
+    if (k3_fast_params(g)) {
+        const int hV = g.refV + g.guardV, c0 = (g.refR + g.guardR) & ~3;
+        const int rows = g.P - 2 * hV > 0 ? g.P - 2 * hV : 0;
+        const int c1 = c0 + k3_ntiles(g) * g.cfar_RT < g.G ? c0 + k3_ntiles(g) * g.cfar_RT : g.G;
+        return (long long)g.B * rows * (c1 > c0 ? c1 - c0 : 0) * real_bytes;
+    }
+    return (long long)g.B * g.P * g.G * real_bytes;
+}
+
+// Frequencies per wave-uniform set of the factored slow-time DFT's Q-point stage (k1_dft_rq)
+#define RQ_RK 6
+// Complex LDS entries of k1_dft_rq's tables, twQ | W_P^i.  Pass 2 prefetches the table rows of
+// the step after its last one: up to 2 RQ_RK entries past a frequency set's rows, which for the
+// last set lie in W_P^i.  P < 2 RQ_RK (P = 6: Q = 3) would end them past W_P^i, so the request
+// is never smaller than the prefetch reaches (P >= 12: exactly twq_elems + P).
+inline int rq_table_elems(int twq_elems, int P) { return twq_elems + (P > 2 * RQ_RK ? P : 2 * RQ_RK); }
+
+// LDS pad shift of a pulse-compression workgroup's rows (one pad per 32 points; k2_sh in
+// rsp_kernels.hip says why) and the complex LDS slots of pts points with their pads.
+constexpr int RSP_K2_SH = 5;
+RSP_HD constexpr int k2_lds_data(int pts, int sh) { return pts + (pts >> sh); }
+
+// K1's launch configuration for C channels and B beams: the template arguments CP (channels padded
+// to the MFMA's groups of 4) and BMAX of the K1 kernels, NJ channel groups, MB MFMA row blocks of
+// 8 beams and TPW sub-tiles per wave of a load round (16 16-B registers per lane).  The Atab
+// layout, the route, the LDS sizes and the launchers' template dispatch all read this.
+struct K1Cfg {
+    int CP, BMAX, NJ, MB, TPW;
+    // the persistent K1 has 2 TPW instantiations only where their loads stay within 16 16-B
+    // registers per lane and 4 sub-tiles (x4: 2 x 8 channels); elsewhere they would spill
+    bool twice_ok;
+};
+constexpr K1Cfg k1_cfg(int C, int B) {
+    const int cp = C <= 8 ? 8 : (C <= 16 ? 16 : 32), bmax = B <= 4 ? 4 : (B <= 8 ? 8 : 16);
+    const int nj = cp / 4, mb = bmax <= 8 ? 1 : 2, tpw = (16 / nj) / mb > 0 ? (16 / nj) / mb : 1;
+    return K1Cfg{cp, bmax, nj, mb, tpw, 2 * tpw * nj <= 16 && 2 * tpw <= 4};
+}
+
+// Which K1 slow-time FFTs run k1_fft_dif (the persistent and the tiled K1 agree, so their outputs
+// are bit-identical): P = 64, 128 always; P = 256 for plans of more than 8 channels (with 8, the
+// persistent K1's 8 sub-tiles of loads per wave and the DIF's registers spill: the Stockham passes)
+RSP_HD constexpr bool k1_dif(int lgp, int cp) { return lgp >= 6 && (lgp <= 7 || (lgp == 8 && cp >= 16)); }
+
+// The slow-time transform of a plan: which K1 kernel launch_k1 starts in `mode`, the transform it
+// runs, the sub-tiles per wave of the persistent kernels (0: tiled) and the k_mtd_cols
+// instantiation of the stage-2 path.  The one decision: launch_k1, launch_mtd_cols,
+// rsp_query_k1_route and rsp_plan_describe all read it.  kernel / transform use the values of
+// rsp.h's RSP_K1_KERNEL_* / RSP_K1_TRANSFORM_*.
+enum { K1K_TILED = 0, K1K_PERSISTENT = 1, K1K_PERSISTENT_FACTORED = 2 };
+enum { K1X_STOCKHAM = 0, K1X_DIF = 1, K1X_FACTORED = 2, K1X_DIRECT = 3 };
+struct K1Route {
+    int kernel, transform, tpw, lgp2;
+};
+// `mode` bits as launch_k1's: 1 = apply DBF, 2 = apply MTD (3: the frame chain; 0: the stage-2
+// transpose, always the tiled kernel).
+K1Route k1_route(const Geometry& g, int mode);
+bool k1_persistent_fits(const Geometry& g);
+
+// Dynamic LDS bytes each launcher requests
+size_t k1_tiled_lds(const Geometry& g, bool rq);    // k1_dbf_mtd: tile | twiddles, or (rq) k1_dft_rq's tables
+size_t k1p_lds(const Geometry& g);                  // k1p_dbf_mtd
+size_t k1q_lds(const Geometry& g);                  // k1q_dbf_mtd
+size_t mtd_cols_lds(const Geometry& g);             // k_mtd_cols: 16 columns | twiddles
+
+// Everything rsp_plan_create_ex derives from its arguments before it touches the device: the
+// Geometry, the segment and job lists, the buffer sizes and the host tables in upload order
+// (complex tables as complex double; the plan narrows them to its precision on upload).
+struct PlanHost {
+    typedef std::complex<double> cd;
+    Geometry g{};
+    std::vector<SegDesc> segs;
+    std::vector<K2Job> jobs;
+    int det_bound = 1;   // cells under test per frame: the most detections a frame can have
+    size_t z_elems = 0, rdm_elems = 0, mag_elems = 0;
+    std::vector<double> atab;        // DBF MFMA A operands per lane: [MB][CP/4][Re,Im][64]
+    std::vector<cd> twP, twPp, twD, twQ;
+    std::vector<double> win, taps;
+    std::vector<cd> H, twM;
+    std::vector<double> range_axis, velocity_axis, beam_angles, klut;
+    std::vector<int> k2order;        // pulse-compression workgroup dispatch order
+};
+
+// The checks of rsp_plan_create_ex that need no device and come before its device checks.
+int rsp_plan_check_args(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params* cluster,
+                        const rsp_precomputed* pre, const rsp_plan_options* opt);
+// The derivation for a device of ncu compute units (arguments already checked).  Returns RSP_OK or
+// the status of the first refusal, its message set through rsp_set_error.
+int rsp_plan_derive(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params* cluster,
+                    const rsp_precomputed* pre, const rsp_plan_options* opt, int ncu, PlanHost* out);
+
+// The one filling routine of rsp_query_sizes / rsp_query_k1_route / rsp_plan_describe.
+void rsp_fill_sizes(const Geometry& g, int det_bound, rsp_sizes* s);
+void rsp_fill_k1_route(const Geometry& g, rsp_k1_route* out);

@@ -626,7 +626,6 @@ __device__ __forceinline__ size_t zaddr(const Geometry& g, int b, int v, int np)
 // ======================================================================================
 // K1: DBF + MTD window + slow-time FFT + fftshift -> compacted rows
 // ======================================================================================
-#define K1_THREADS 512
 #define K1_SH 4   // LDS pad shift of the slow-time FFT rows (row stride P + P/16)
 
 // DBF (fsf:93-97) on the matrix cores as a real GEMM: D[16 rows x 16 pulses] += A[16 x 4
@@ -728,10 +727,7 @@ struct StoreZ {
 // twd = the compact pass-A table in LDS, [i][n2] = W_P^(n2 2^i) (load_tw).  Same arithmetic per
 // output as the radix-16 x radix-R1 Stockham plan, with the twiddles on the other side.
 // PTS = points per thread (nrows P <= PTS NTHR, k1_persistent_fits).
-// Which K1 slow-time FFTs run k1_fft_dif (the persistent and the tiled K1 agree, so their outputs
-// are bit-identical): P = 64, 128 always; P = 256 for plans of more than 8 channels (with 8, the
-// persistent K1's 8 sub-tiles of loads per wave and the DIF's registers spill: the Stockham passes)
-__host__ __device__ constexpr bool k1_dif(int lgp, int cp) { return lgp >= 6 && (lgp <= 7 || (lgp == 8 && cp >= 16)); }
+// Which K1 slow-time FFTs run k1_fft_dif: k1_dif (rsp_geometry.h)
 #define K1_DIF k1_dif(LGP, CP)
 
 template <int LGP, int PTS, int NTHR, int SH, class V, class St>
@@ -1496,15 +1492,15 @@ __device__ __forceinline__ ZWin zrow_window(const Geometry& g, const V* z, int r
 // ds_read_b128 of a pass conflict-free (a pad per 16 would shift lanes 20-27 of a lane group
 // onto lane 12's bank), and the stride-16 stores of the two radix-16 Ns = 1 passes 2-way
 // (tools/ab/lds_conflicts64.py)
-template <class T> constexpr int k2_sh() { return 5; }
+template <class T> constexpr int k2_sh() { return RSP_K2_SH; }
 // The 2560-point-sized workgroups (k2_pc<double, 4>): rows without pads and twiddles read from
 // L1/L2, so that a workgroup's LDS is the 2560 complex doubles of its row alone (40 KB) and 4 fit a
 // CU; SH = 30 makes every pad expression zero.  Measured against 3 per CU with pads and staged
 // twiddles: k2_pc -3 % at x2 (profiles/r06zf_k2_w4_ab.txt)
 constexpr int K2_NOPAD_SH = 30;
 template <class T, bool NOPAD> constexpr int k2_sh_np() { return NOPAD ? K2_NOPAD_SH : k2_sh<T>(); }
-// LDS complex slots of a workgroup's rows: pts points (Geometry::k2_pts) + their pads
-__host__ __device__ constexpr int k2_lds_data(int pts, int sh) { return pts + (pts >> sh); }
+// LDS complex slots of a workgroup's rows, pts points (Geometry::k2_pts) + their pads: k2_lds_data
+// (rsp_geometry.h)
 
 // The block's twiddle tables are staged in LDS next to the rows: a pass's twiddles then arrive
 // with its LDS data reads instead of after an L2 round trip (-6% for k2_pc in complex double).
@@ -2698,75 +2694,7 @@ static hipError_t allow_lds(K kernel, size_t bytes) {
                                (int)bytes);
 }
 
-static size_t cplx_bytes(const Geometry& g) { return g.prec == RSP_PREC_F64 ? 16 : 8; }
-static int k1_tpw(const Geometry& g) {
-    const int cp = g.C <= 8 ? 8 : (g.C <= 16 ? 16 : 32), bmax = g.B <= 4 ? 4 : (g.B <= 8 ? 8 : 16);
-    const int nj = cp / 4, mb = bmax <= 8 ? 1 : 2;
-    return (16 / nj) / mb > 0 ? (16 / nj) / mb : 1;
-}
-// tile buffers x 2 | FFT twiddles (<= P) | two MFMA row blocks' Atab when B > 8 (k1p_dbf_mtd ALDS)
-static size_t k1p_lds(const Geometry& g) {
-    const int cp = g.C <= 8 ? 8 : (g.C <= 16 ? 16 : 32);
-    return ((size_t)2 * g.B * g.NT * g.Ppad + g.P) * cplx_bytes(g) +
-           (g.B > 8 ? (size_t)2 * (cp / 4) * 2 * 64 * (cplx_bytes(g) / 2) : 0);
-}
-
-// sub-tiles per wave of the persistent K1 (one load round per tile): TPW, or 2 TPW
-static int k1p_tpw(const Geometry& g) {
-    const int pt = g.prec == RSP_PREC_F64 ? 16 : 32;   // pulses per MFMA sub-tile
-    const int need = (g.NT * (g.P / pt) + (K1_THREADS / 64) - 1) / (K1_THREADS / 64);
-    return need <= k1_tpw(g) ? k1_tpw(g) : (need <= 2 * k1_tpw(g) ? 2 * k1_tpw(g) : 0);
-}
-
-// sub-tiles per wave of the factored-DFT K1 (one load round per tile): ceil(sub-tiles / 8) <= 4
-static int k1q_tpw(const Geometry& g) {
-    const int pt = g.prec == RSP_PREC_F64 ? 16 : 32;
-    const int need = (g.NT * ((g.P + pt - 1) / pt) + (K1_THREADS / 64) - 1) / (K1_THREADS / 64);
-    return need <= 4 ? need : 0;
-}
-static size_t k1q_lds(const Geometry& g) {   // tile | twQ | W_P^i | Atab (MB x NJ x 2 x 64 <= 1024 reals: CP <= 16)
-    return ((size_t)g.B * g.NT * g.Ppad + rq_table_elems(g.twq_elems, g.P)) * cplx_bytes(g) + (size_t)1024 * (cplx_bytes(g) / 2);
-}
-static bool k1q_fits(const Geometry& g) {
-    return !g.pow2P && g.rqQ > 0 && k1q_tpw(g) > 0 && k1q_lds(g) <= 160 * 1024 && g.ncu > 0 && !g.k1_tiled;
-}
-
-bool k1_persistent_fits(const Geometry& g) {
-    const int pts = g.prec == RSP_PREC_F64 ? 8 : 16;   // FFT points per thread (k1p_pts)
-    return g.pow2P && g.logP >= 6 && g.logP <= 8 && k1p_tpw(g) > 0 && k1p_lds(g) <= 160 * 1024 &&
-           g.B * g.NT * g.P <= pts * K1_THREADS && g.ncu > 0 && !g.k1_tiled;
-}
-
-// The route launch_k1 takes in `mode` (3 = DBF + MTD, the frame chain; 0 = transpose only, the
-// stage-2 path, always the tiled kernel) -- see K1Route.  CP / BMAX / TPW as launch_k1_t's template
-// arguments derive them.
-K1Route k1_route(const Geometry& g, int mode) {
-    const int cp = g.C <= 8 ? 8 : (g.C <= 16 ? 16 : 32), nj = cp / 4, tpw = k1_tpw(g);
-    K1Route r;
-    r.lgp2 = g.pow2P ? g.logP : 0;   // k_mtd_cols<T, LGP>: the Stockham passes for P = 16 .. 512, else the direct DFT
-    r.kernel = K1K_TILED;
-    r.tpw = 0;
-    r.transform = g.pow2P ? (k1_dif(g.logP, cp) ? K1X_DIF : K1X_STOCKHAM) : (g.rqQ > 0 ? K1X_FACTORED : K1X_DIRECT);
-    if (mode == 3 && k1_persistent_fits(g)) {
-        // 2 TPW sub-tiles per wave only where their loads stay within 16 16-B registers per lane
-        // and 4 sub-tiles (x4: 2 x 8 channels); otherwise (no instantiation: it would spill) the
-        // tiled kernel
-        const bool twice = k1p_tpw(g) == 2 * tpw, twice_ok = 2 * tpw * nj <= 16 && 2 * tpw <= 4;
-        if (!twice || twice_ok) {
-            r.kernel = K1K_PERSISTENT;
-            r.tpw = twice ? 2 * tpw : tpw;
-            return r;
-        }
-    }
-    // the persistent factored-DFT K1 for C <= 16 when one load round of at most 16 16-B cube loads
-    // per lane covers a tile (register budget: no scratch); otherwise the tiled kernel
-    if (cp <= 16 && mode == 3 && k1q_fits(g) && k1q_tpw(g) * nj <= 16) {
-        r.kernel = K1K_PERSISTENT_FACTORED;
-        r.tpw = k1q_tpw(g);
-    }
-    return r;
-}
-
+// Every request below (LDS bytes, the K1 route, the K1 template arguments) is rsp_geometry.h's.
 template <class T, int BMAX, int CP>
 static hipError_t launch_k1_t(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, int mode,
                               hipStream_t s) {
@@ -2775,7 +2703,9 @@ static hipError_t launch_k1_t(const Geometry& g, const DevConsts& k, const Frame
         // one FFT size per instantiation keeps the prefetch registers + FFT under 256 VGPRs
         const size_t ldsp = k1p_lds(g);
         const int grid = std::min(g.ncu, nf * g.ntiles);
-        constexpr int NJ = CP / 4, MB = BMAX <= 8 ? 1 : 2, TPW = (16 / NJ) / MB > 0 ? (16 / NJ) / MB : 1;
+        constexpr K1Cfg KC = k1_cfg(CP, BMAX);
+        static_assert(KC.CP == CP && KC.BMAX == BMAX, "CP / BMAX are k1_cfg's own values");
+        constexpr int TPW = KC.TPW;
         const bool twice = rt.tpw == 2 * TPW;
 #define K1P_LAUNCH(LGP, TW)                                                                                      \
     do {                                                                                                         \
@@ -2784,8 +2714,8 @@ static hipError_t launch_k1_t(const Geometry& g, const DevConsts& k, const Frame
         hipLaunchKernelGGL((k1p_dbf_mtd<T, BMAX, CP, LGP, TW>), dim3(grid), dim3(K1_THREADS), ldsp, s, g, k, fp, nf); \
         return hipGetLastError();                                                                                \
     } while (0)
-        // the 2 TPW instantiations exist only where k1_route may choose them (its twice_ok)
-        constexpr bool TWICE_OK = 2 * TPW * NJ <= 16 && 2 * TPW <= 4;
+        // the 2 TPW instantiations exist only where k1_route may choose them
+        constexpr bool TWICE_OK = KC.twice_ok;
         if (twice && !TWICE_OK) return hipErrorInvalidValue;
         switch (g.logP) {
             case 6: if constexpr (TWICE_OK) { if (twice) K1P_LAUNCH(6, 2 * TPW); } K1P_LAUNCH(6, TPW);
@@ -2796,7 +2726,7 @@ static hipError_t launch_k1_t(const Geometry& g, const DevConsts& k, const Frame
 #undef K1P_LAUNCH
     }
     if constexpr (CP <= 16) {
-        constexpr int NJ = CP / 4;
+        constexpr int NJ = k1_cfg(CP, BMAX).NJ;
         if (rt.kernel == K1K_PERSISTENT_FACTORED) {
             const size_t ldsq = k1q_lds(g);
             const int grid = std::min(g.ncu, nf * g.ntiles);
@@ -2818,7 +2748,7 @@ static hipError_t launch_k1_t(const Geometry& g, const DevConsts& k, const Frame
     }
     if (rt.kernel != K1K_TILED) return hipErrorInvalidValue;
     const bool rq = (mode & 2) && rt.transform == K1X_FACTORED;
-    const size_t lds = ((size_t)g.B * g.NT * g.Ppad + (rq ? rq_table_elems(g.twq_elems, g.P) : g.P)) * sizeof(cx<T>);
+    const size_t lds = k1_tiled_lds(g, rq);
     hipError_t e;
     if (rq) {
         if ((e = allow_lds(k1_dbf_mtd<T, BMAX, CP, true>, lds)) != hipSuccess) return e;
@@ -2833,17 +2763,21 @@ static hipError_t launch_k1_t(const Geometry& g, const DevConsts& k, const Frame
 template <class T, int BMAX>
 static hipError_t launch_k1_b(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, int mode,
                               hipStream_t s) {
-    if (g.C <= 8) return launch_k1_t<T, BMAX, 8>(g, k, fp, nf, mode, s);
-    if (g.C <= 16) return launch_k1_t<T, BMAX, 16>(g, k, fp, nf, mode, s);
-    return launch_k1_t<T, BMAX, 32>(g, k, fp, nf, mode, s);
+    switch (k1_cfg(g.C, g.B).CP) {
+        case 8: return launch_k1_t<T, BMAX, 8>(g, k, fp, nf, mode, s);
+        case 16: return launch_k1_t<T, BMAX, 16>(g, k, fp, nf, mode, s);
+        default: return launch_k1_t<T, BMAX, 32>(g, k, fp, nf, mode, s);
+    }
 }
 
 template <class T>
 static hipError_t launch_k1_p(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, int mode,
                               hipStream_t s) {
-    if (g.B <= 4) return launch_k1_b<T, 4>(g, k, fp, nf, mode, s);
-    if (g.B <= 8) return launch_k1_b<T, 8>(g, k, fp, nf, mode, s);
-    return launch_k1_b<T, 16>(g, k, fp, nf, mode, s);
+    switch (k1_cfg(g.C, g.B).BMAX) {
+        case 4: return launch_k1_b<T, 4>(g, k, fp, nf, mode, s);
+        case 8: return launch_k1_b<T, 8>(g, k, fp, nf, mode, s);
+        default: return launch_k1_b<T, 16>(g, k, fp, nf, mode, s);
+    }
 }
 
 hipError_t launch_k1(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, int mode, hipStream_t s) {
@@ -2920,7 +2854,7 @@ hipError_t launch_k3(const Geometry& g, const DevConsts& k, const FramePtrs& fp,
 
 template <class T, int LGP>
 static hipError_t launch_mtd_t(const Geometry& g, const DevConsts& k, const void* pc, void* rdm, hipStream_t s) {
-    const size_t lds = ((size_t)16 * g.Ppad + g.P) * sizeof(cx<T>);
+    const size_t lds = mtd_cols_lds(g);
     hipError_t e = allow_lds(k_mtd_cols<T, LGP>, lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_mtd_cols<T, LGP>), dim3((g.G + 15) / 16, g.B), dim3(RSP_THREADS), lds, s, g, k,

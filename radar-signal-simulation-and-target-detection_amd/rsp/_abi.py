@@ -152,6 +152,9 @@ PROTOTYPES = {
     'rsp_plan_destroy': (ct.c_int32, [_P]),
     'rsp_query_sizes': (ct.c_int32, [_P, ct.POINTER(Sizes)]),
     'rsp_query_k1_route': (ct.c_int32, [_P, ct.POINTER(K1Route)]),
+    'rsp_plan_describe': (ct.c_int32, [ct.POINTER(SigConfig), ct.POINTER(CfarParams), ct.POINTER(ClusterParams),
+                                       ct.POINTER(Precomputed), ct.POINTER(PlanOptions), ct.c_int32, ct.POINTER(Sizes),
+                                       ct.POINTER(K1Route)]),
     'rsp_process_cube': (ct.c_int32, [_P, _P, ct.c_int32, ct.c_int32, ct.c_int32, ct.POINTER(FrameOut)]),
     'rsp_process_targets': (ct.c_int32, [_P, ct.POINTER(TargetIn), ct.c_int32, ct.c_int32, ct.c_uint64,
                                          ct.c_double, ct.POINTER(FrameOut)]),

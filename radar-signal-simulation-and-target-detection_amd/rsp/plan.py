@@ -25,6 +25,78 @@ def _tgt_dict(t):
     return {'Range': t.Range, 'Velocity': t.Velocity, 'Angle': t.Angle, 'Power': t.Power}
 
 
+def _marshal(config, cfar_params, cluster_params, pre, keep):
+    """The C structs of rsp_plan_create_ex / rsp_plan_describe; the arrays they borrow go to ``keep``."""
+    sc = config['Sig_Config']
+
+    def arr(x, cplx=False):
+        a = np.ascontiguousarray(np.asarray(x, np.complex128 if cplx else np.float64))
+        if cplx:
+            a = a.view(np.float64)
+        keep.append(a)
+        return _dptr(a)
+
+    cfg = _abi.SigConfig(c=sc['c'], fs=sc['fs'], fc=sc['fc'], prt=sc['prt'], wavelength=sc['wavelength'],
+                         element_spacing=config['Array']['element_spacing'], prtNum=sc['prtNum'],
+                         point_PRT=sc['point_PRT'], channel_num=sc['channel_num'], beam_num=sc['beam_num'])
+    cfar = _abi.CfarParams(refCells_V=cfar_params['refCells_V'], guardCells_V=cfar_params['guardCells_V'],
+                           refCells_R=cfar_params['refCells_R'], guardCells_R=cfar_params['guardCells_R'],
+                           T_CFAR=cfar_params['T_CFAR'])
+    cluster = _abi.ClusterParams(max_range_sep=cluster_params['max_range_sep'],
+                                 max_vel_sep=cluster_params['max_vel_sep'],
+                                 max_angle_sep=cluster_params['max_angle_sep'])
+    W = np.asarray(pre['DBF_coeffs_data_C'], np.complex128)
+    Wcm = np.asfortranarray(W).ravel(order='F')      # B x C column-major (MATLAB)
+    klut = np.asarray(pre['k_slopes_LUT'], float)
+    pre_c = _abi.Precomputed(
+        tx_pulse=arr(pre['tx_pulse'], True) if 'tx_pulse' in pre else None,
+        P_signal_unscaled=pre.get('P_signal_unscaled', 0.0),
+        DBF_coeffs_data_C=arr(Wcm, True), MF_narrow=arr(pre['MF_narrow']), n_MF_narrow=len(pre['MF_narrow']),
+        fir_delay=int(pre['fir_delay']), MF_medium_fft=arr(pre['MF_medium_fft'], True),
+        N_fft_med=int(pre['N_fft_med']), MF_long_fft=arr(pre['MF_long_fft'], True),
+        N_fft_long=int(pre['N_fft_long']), N_gate_narrow=int(pre['N_gate_narrow']),
+        N_gate_medium=int(pre['N_gate_medium']), N_gate_long=int(pre['N_gate_long']),
+        N_total_gate=int(pre['N_total_gate']), seg_start_narrow=int(pre['seg_start_narrow']),
+        seg_start_medium=int(pre['seg_start_medium']), seg_start_long=int(pre['seg_start_long']),
+        MTD_win=arr(pre['MTD_win']), range_axis=arr(pre['range_axis']), velocity_axis=arr(pre['velocity_axis']),
+        deltaR=float(pre['deltaR']), deltaV=float(pre['deltaV']), beam_angles_deg=arr(pre['beam_angles_deg']),
+        k_slopes_LUT=arr(klut if klut.size else np.zeros(1)))
+    return cfg, cfar, cluster, pre_c
+
+
+def _options(device, frames_per_launch, precision, k1_tiled, monopulse):
+    if precision not in ('c128', 'c64'):
+        raise ValueError("precision must be 'c128' or 'c64'")
+    opt = _abi.PlanOptions()
+    check(lib().rsp_plan_options_default(ct.byref(opt)))
+    opt.device, opt.frames_per_launch = int(device), int(frames_per_launch)
+    opt.precision = _abi.RSP_C128 if precision == 'c128' else _abi.RSP_C64
+    if monopulse not in ('amplitude', 'complex'):
+        raise ValueError("monopulse must be 'amplitude' (fsf:282-290) or 'complex' "
+                         "(main_plot_snr_vs_angle_error.m:455-462), got %r" % (monopulse,))
+    opt.flags = (_abi.RSP_PLAN_K1_TILED if k1_tiled else 0) | \
+        (_abi.RSP_PLAN_MONOPULSE_COMPLEX if monopulse == 'complex' else 0)
+    return opt
+
+
+def _route_dict(r):
+    return dict(kernel=_abi.K1_KERNELS[r.kernel], transform=_abi.K1_TRANSFORMS[r.transform], R=r.R, Q=r.Q,
+                NT=r.NT, Ppad=r.Ppad, tiles_per_wave=r.tiles_per_wave, stage2_lgp=r.stage2_lgp)
+
+
+def describe(config, cfar_params, cluster_params, precomputed_data, precision='c128', k1_tiled=False, ncu=256):
+    """What a plan of these arguments would be on a device of ``ncu`` compute units, without a
+    device (rsp_plan_describe): ``(sizes, route)`` as ``Plan.sizes`` and ``Plan.k1_route()``.
+    Refusals raise RspError with the code and message rsp_plan_create_ex would give."""
+    keep = []
+    cfg, cfar, cluster, pre = _marshal(config, cfar_params, cluster_params, precomputed_data, keep)
+    opt = _options(0, 1, precision, k1_tiled, 'amplitude')
+    s, r = _abi.Sizes(), _abi.K1Route()
+    check(lib().rsp_plan_describe(ct.byref(cfg), ct.byref(cfar), ct.byref(cluster), ct.byref(pre), ct.byref(opt),
+                                  int(ncu), ct.byref(s), ct.byref(r)))
+    return s, _route_dict(r)
+
+
 class Plan:
     """One device plan = the reference's per-frame kernel bound to fixed config/precompute.
 
@@ -40,54 +112,11 @@ class Plan:
 
     def __init__(self, config, cfar_params, cluster_params, precomputed_data, device=0, frames_per_launch=1,
                  precision='c128', k1_tiled=False, monopulse='amplitude'):
-        sc = config['Sig_Config']
-        pre = precomputed_data
         self.config = config
         self._keep = []
-
-        def arr(x, cplx=False):
-            a = np.ascontiguousarray(np.asarray(x, np.complex128 if cplx else np.float64))
-            if cplx:
-                a = a.view(np.float64)
-            self._keep.append(a)
-            return _dptr(a)
-
-        self.cfg = _abi.SigConfig(c=sc['c'], fs=sc['fs'], fc=sc['fc'], prt=sc['prt'], wavelength=sc['wavelength'],
-                                  element_spacing=config['Array']['element_spacing'], prtNum=sc['prtNum'],
-                                  point_PRT=sc['point_PRT'], channel_num=sc['channel_num'], beam_num=sc['beam_num'])
-        self.cfar = _abi.CfarParams(refCells_V=cfar_params['refCells_V'], guardCells_V=cfar_params['guardCells_V'],
-                                    refCells_R=cfar_params['refCells_R'], guardCells_R=cfar_params['guardCells_R'],
-                                    T_CFAR=cfar_params['T_CFAR'])
-        self.cluster = _abi.ClusterParams(max_range_sep=cluster_params['max_range_sep'],
-                                          max_vel_sep=cluster_params['max_vel_sep'],
-                                          max_angle_sep=cluster_params['max_angle_sep'])
-        W = np.asarray(pre['DBF_coeffs_data_C'], np.complex128)
-        Wcm = np.asfortranarray(W).ravel(order='F')      # B x C column-major (MATLAB)
-        klut = np.asarray(pre['k_slopes_LUT'], float)
-        self.pre = _abi.Precomputed(
-            tx_pulse=arr(pre['tx_pulse'], True) if 'tx_pulse' in pre else None,
-            P_signal_unscaled=pre.get('P_signal_unscaled', 0.0),
-            DBF_coeffs_data_C=arr(Wcm, True), MF_narrow=arr(pre['MF_narrow']), n_MF_narrow=len(pre['MF_narrow']),
-            fir_delay=int(pre['fir_delay']), MF_medium_fft=arr(pre['MF_medium_fft'], True),
-            N_fft_med=int(pre['N_fft_med']), MF_long_fft=arr(pre['MF_long_fft'], True),
-            N_fft_long=int(pre['N_fft_long']), N_gate_narrow=int(pre['N_gate_narrow']),
-            N_gate_medium=int(pre['N_gate_medium']), N_gate_long=int(pre['N_gate_long']),
-            N_total_gate=int(pre['N_total_gate']), seg_start_narrow=int(pre['seg_start_narrow']),
-            seg_start_medium=int(pre['seg_start_medium']), seg_start_long=int(pre['seg_start_long']),
-            MTD_win=arr(pre['MTD_win']), range_axis=arr(pre['range_axis']), velocity_axis=arr(pre['velocity_axis']),
-            deltaR=float(pre['deltaR']), deltaV=float(pre['deltaV']), beam_angles_deg=arr(pre['beam_angles_deg']),
-            k_slopes_LUT=arr(klut if klut.size else np.zeros(1)))
-        if precision not in ('c128', 'c64'):
-            raise ValueError("precision must be 'c128' or 'c64'")
-        opt = _abi.PlanOptions()
-        check(lib().rsp_plan_options_default(ct.byref(opt)))
-        opt.device, opt.frames_per_launch = int(device), int(frames_per_launch)
-        opt.precision = _abi.RSP_C128 if precision == 'c128' else _abi.RSP_C64
-        if monopulse not in ('amplitude', 'complex'):
-            raise ValueError("monopulse must be 'amplitude' (fsf:282-290) or 'complex' "
-                             "(main_plot_snr_vs_angle_error.m:455-462), got %r" % (monopulse,))
-        opt.flags = (_abi.RSP_PLAN_K1_TILED if k1_tiled else 0) | \
-            (_abi.RSP_PLAN_MONOPULSE_COMPLEX if monopulse == 'complex' else 0)
+        self.cfg, self.cfar, self.cluster, self.pre = _marshal(config, cfar_params, cluster_params, precomputed_data,
+                                                               self._keep)
+        opt = _options(device, frames_per_launch, precision, k1_tiled, monopulse)
         h = ct.c_void_p()
         check(lib().rsp_plan_create_ex(ct.byref(self.cfg), ct.byref(self.cfar), ct.byref(self.cluster),
                                        ct.byref(self.pre), ct.byref(opt), ct.byref(h)))
@@ -120,8 +149,7 @@ class Plan:
         column transform: log2 P, or 0 for the direct DFT)."""
         r = _abi.K1Route()
         check(lib().rsp_query_k1_route(self.h, ct.byref(r)))
-        return dict(kernel=_abi.K1_KERNELS[r.kernel], transform=_abi.K1_TRANSFORMS[r.transform], R=r.R, Q=r.Q,
-                    NT=r.NT, Ppad=r.Ppad, tiles_per_wave=r.tiles_per_wave, stage2_lgp=r.stage2_lgp)
+        return _route_dict(r)
 
     # ---- synchronous frame paths ---------------------------------------------------------
     def _frame_out(self, want_rdm, want_cfar):

@@ -2,13 +2,18 @@
 
 csrc/rsp_mat.cpp (the MAT Level-5 reader/writer that parses untrusted frame files) and
 csrc/rsp_host.cpp (error sink, S10/S11 clustering of fun_process_single_frame.m:302-407,
-inter-frame association of main_simulate_echoes_with_array_v8_3.m:253-352) are compiled with
-g++ -fsanitize=address,undefined together with tests/native/host_fuzz.cpp and driven over:
+inter-frame association of main_simulate_echoes_with_array_v8_3.m:253-352) and
+csrc/rsp_geometry.cpp (plan geometry, K1 routing and host tables: rsp_plan_describe) are compiled
+with g++ -fsanitize=address,undefined together with tests/native/host_fuzz.cpp and driven over:
   * the reference's MATLAB-written files and scipy-written frames;
   * crafted malformed files: a small-form element claiming 8 inline bytes (the overflow the
     round-1 review found), truncations at every 7th byte, dims larger than the data, a corrupt
     zlib stream, and seeded random byte flips;
-  * random detection / track lists of up to 3000 entries with undersized output buffers.
+  * random detection / track lists of up to 3000 entries with undersized output buffers;
+  * 2500 random plan argument sets per seed (C <= 32, B <= 16, even P <= 1100, N <= 8192, power-of-two
+    and other N_fft, matched-filter spectra of random short filters), one in four deliberately out
+    of range: segment starts at 0 and past N, gate sums off by one, no FIR taps, gates beyond
+    N_fft, an all-zero filter.
 Only sanitizer reports (non-zero exit) fail; the functions' status codes are not checked here
 (tests/test_matio.py does that).
 """
@@ -37,6 +42,7 @@ def fuzz_bin(tmp_path_factory):
     cmd = ['g++', '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined',
            '-fno-omit-frame-pointer', '-I', os.path.join(ROOT, 'include'),
            os.path.join(CSRC, 'rsp_mat.cpp'), os.path.join(CSRC, 'rsp_host.cpp'),
+           os.path.join(CSRC, 'rsp_geometry.cpp'),
            os.path.join(HERE, 'native', 'host_fuzz.cpp'), '-o', exe, '-lz', '-lpthread']
     subprocess.run(cmd, check=True)
     return exe
@@ -115,6 +121,11 @@ def test_mat_reader_under_asan(fuzz_bin, tmp_path):
 @pytest.mark.parametrize('seed', [1, 2])
 def test_clustering_under_asan(fuzz_bin, seed):
     _run(fuzz_bin, 'cluster', str(seed))
+
+
+@pytest.mark.parametrize('seed', [1, 2])
+def test_plan_geometry_under_asan(fuzz_bin, seed):
+    _run(fuzz_bin, 'geometry', str(seed))
 
 
 def test_malformed_small_element_is_an_error(tmp_path):

@@ -20,12 +20,14 @@ tiled factored kernel (P = 166 at 4 beams; more than 16 channels), the direct DF
 The bit-identity of the persistent and the tiled K1 and the queue path of the persistent cases
 are test_gpu_parity.py's tests, parametrised over these cases.
 """
+import ctypes as ct
+
 import numpy as np
 import pytest
 
 from oracle import chain, precompute as oracle_precompute
 from rsp import _abi, config as C
-from rsp.plan import Plan
+from rsp.plan import Plan, describe
 from rsp.precompute import precompute as product_precompute
 
 import _parity
@@ -45,6 +47,14 @@ def _input_cube(name, s):
         _cube_cache.clear()
         _cube_cache[name] = noisy_cube(s, targets_for(name), dtype=np.complex128)
     return _cube_cache[name]
+
+
+def _device_cus():
+    """Compute units of device 0, asked of the HIP runtime librsp.so is linked to (the call
+    rsp_plan_create_ex makes; 63 = hipDeviceAttributeMultiprocessorCount of hip_runtime_api.h)."""
+    n = ct.c_int(0)
+    assert _abi.lib().hipDeviceGetAttribute(ct.byref(n), 63, 0) == 0 and n.value > 0
+    return n.value
 
 
 def _stage2(plan, iq, prec, pre_o, pc_o=None, mtd_o=None):
@@ -72,13 +82,14 @@ def case(request):
     plan = Plan(s['cfg'], s['cfar'], s['clus'], s['pre_p'], precision=prec)
     try:
         route = plan.k1_route()
+        sizes = {f: getattr(plan.sizes, f) for f, _ in _abi.Sizes._fields_}
         gpu = plan.process_cube(cube, frame_idx=1, want_rdm=True, want_cfar=True)
         gpu_mag = plan.process_cube(cube, frame_idx=1, want_rdm=False, want_cfar=True)
         s2 = _stage2(plan, st['iq'], prec, s['pre_o'], st['pc'], st['rdm'])
     finally:
         plan.close()
     st = {k: st[k] for k in ('rdm', 'S_all', 'dets', 'par')}
-    yield dict(name=name, prec=prec, s=s, fin=fin, st=st, gpu=gpu, gpu_mag=gpu_mag, route=route, s2=s2,
+    yield dict(name=name, prec=prec, s=s, fin=fin, st=st, gpu=gpu, gpu_mag=gpu_mag, route=route, sizes=sizes, s2=s2,
                dets=ROUTE_CASES[name]['dets'], P=ROUTE_CASES[name]['P'])
 
 
@@ -91,6 +102,11 @@ def test_route(case):
     assert got['Ppad'] >= case['P'] and got['NT'] in (1, 2, 4, 8)
     if got['kernel'] != 'tiled':
         assert 1 <= got['tiles_per_wave'] <= 4
+    # the device-free description for this device's CU count is the created plan's
+    s = case['s']
+    dsz, droute = describe(s['cfg'], s['cfar'], s['clus'], s['pre_p'], precision=case['prec'], ncu=_device_cus())
+    assert droute == got
+    assert {f: getattr(dsz, f) for f, _ in _abi.Sizes._fields_} == case['sizes']
 
 
 def test_rdm_parity(case):
