@@ -210,6 +210,23 @@ typedef struct rsp_k1_route {
 } rsp_k1_route;
 int32_t rsp_query_k1_route(const rsp_plan* plan, rsp_k1_route* out);
 
+/* How the plan tiles the CFAR/S9 kernel k3_cfar for its window, prtNum, gates and precision
+ * (read-only; the fields the launcher and the kernel read).  Tests assert it, so that a case
+ * runs the kernel path and the Doppler band count it is there to cover. */
+typedef struct rsp_k3_tiling {
+    int32_t fast;             /* 1: the compile-time 5/5/10/10 kernel, tiles without halo; 0: the
+                                 generic kernel, tiles with the window halo                    */
+    int32_t RT;               /* range cells under test per tile                               */
+    int32_t hR;               /* range halo of the generic tile, cells on either side          */
+    int32_t W;                /* LDS row stride of a tile, cells                               */
+    int32_t n_tiles;          /* range tiles per Doppler band and beam pair (<= 0: the window
+                                 leaves no range cell under test, K3 writes the maps only)     */
+    int32_t n_bands;          /* Doppler bands                                                 */
+    int32_t VB;               /* Doppler cells under test per band                             */
+    int32_t rows;             /* Doppler rows of a tile in LDS                                 */
+} rsp_k3_tiling;
+int32_t rsp_query_k3_tiling(const rsp_plan* plan, rsp_k3_tiling* out);
+
 /* What rsp_plan_create_ex would build for these arguments on a device of `ncu` compute units,
  * without a device: the same checks (opt->device aside), refusals and messages, and the values
  * rsp_query_sizes and rsp_query_k1_route report for the created plan.  `sizes` / `route` may be
@@ -217,6 +234,10 @@ int32_t rsp_query_k1_route(const rsp_plan* plan, rsp_k1_route* out);
 int32_t rsp_plan_describe(const rsp_sig_config* cfg, const rsp_cfar_params* cfar,
                           const rsp_cluster_params* cluster, const rsp_precomputed* pre,
                           const rsp_plan_options* opt, int32_t ncu, rsp_sizes* sizes, rsp_k1_route* route);
+/* The same for rsp_query_k3_tiling's values. */
+int32_t rsp_plan_describe_k3(const rsp_sig_config* cfg, const rsp_cfar_params* cfar,
+                             const rsp_cluster_params* cluster, const rsp_precomputed* pre,
+                             const rsp_plan_options* opt, int32_t ncu, rsp_k3_tiling* tiling);
 
 /* Cube-in path: S5..S11 of fun_process_single_frame on one host cube
  * (layout RSP_LAYOUT_PNC, dtype RSP_C64 or RSP_C128; converted to the plan's precision

@@ -712,6 +712,17 @@ void rsp_fill_k1_route(const Geometry& g, rsp_k1_route* out) {
     out->stage2_lgp = r.lgp2;
 }
 
+void rsp_fill_k3_tiling(const Geometry& g, rsp_k3_tiling* out) {
+    out->fast = k3_fast_params(g) ? 1 : 0;   // launch_k3_p's choice of instantiation
+    out->RT = g.cfar_RT;
+    out->hR = g.cfar_hR;
+    out->W = g.cfar_W;
+    out->n_tiles = k3_ntiles(g);
+    out->n_bands = g.cfar_nband;
+    out->VB = g.cfar_VB;
+    out->rows = g.cfar_rows;
+}
+
 extern "C" int32_t rsp_plan_describe(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params* cluster,
                                      const rsp_precomputed* pre, const rsp_plan_options* opt, int32_t ncu, rsp_sizes* sizes,
                                      rsp_k1_route* route) {
@@ -721,5 +732,16 @@ extern "C" int32_t rsp_plan_describe(const rsp_sig_config* cfg, const rsp_cfar_p
     if ((rc = rsp_plan_derive(cfg, cfar, cluster, pre, opt, ncu, &h))) return rc;
     if (sizes) rsp_fill_sizes(h.g, h.det_bound, sizes);
     if (route) rsp_fill_k1_route(h.g, route);
+    return RSP_OK;
+}
+
+extern "C" int32_t rsp_plan_describe_k3(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params* cluster,
+                                        const rsp_precomputed* pre, const rsp_plan_options* opt, int32_t ncu,
+                                        rsp_k3_tiling* tiling) {
+    int rc = rsp_plan_check_args(cfg, cfar, cluster, pre, opt);
+    if (rc) return rc;
+    PlanHost h;
+    if ((rc = rsp_plan_derive(cfg, cfar, cluster, pre, opt, ncu, &h))) return rc;
+    if (tiling) rsp_fill_k3_tiling(h.g, tiling);
     return RSP_OK;
 }

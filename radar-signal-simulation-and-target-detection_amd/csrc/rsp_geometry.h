@@ -202,6 +202,8 @@ int rsp_plan_check_args(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, 
 int rsp_plan_derive(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params* cluster,
                     const rsp_precomputed* pre, const rsp_plan_options* opt, int ncu, PlanHost* out);
 
-// The one filling routine of rsp_query_sizes / rsp_query_k1_route / rsp_plan_describe.
+// The one filling routine of rsp_query_sizes / rsp_query_k1_route / rsp_query_k3_tiling and
+// rsp_plan_describe / rsp_plan_describe_k3.
 void rsp_fill_sizes(const Geometry& g, int det_bound, rsp_sizes* s);
 void rsp_fill_k1_route(const Geometry& g, rsp_k1_route* out);
+void rsp_fill_k3_tiling(const Geometry& g, rsp_k3_tiling* out);

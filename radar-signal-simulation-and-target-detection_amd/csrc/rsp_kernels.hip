@@ -2464,9 +2464,13 @@ __global__ __launch_bounds__(RSP_THREADS, RSP_K3_WGS) void k3_cfar(Geometry g, D
     __syncthreads();
     const int base = qn[1];
     // S(v, r) as the CFAR test read it: the tile, or the maps where a halo-less tile lacks it
+    // The tile's Doppler halo is the window's rV + gV rows; S9 reads rows v - 2 .. v + 2, so with
+    // rV + gV = 1 a hit on a band's first or last row reaches one row past the tile (the rows of
+    // the neighbouring band, outside this tile's LDS): those come from the maps, the same two
+    // values and the same add.  The range halo is never narrower than 2 (derive_k3_tiling).
     auto st = [&](int vv, int rr) -> T {
         if constexpr (NOH) return sg(vv, rr);
-        else return Sv[vv * W + (rr - c0)];
+        else return vv >= vt0 && vv < vt1 ? Sv[vv * W + (rr - c0)] : sg(vv, rr);
     };
     for (int i = threadIdx.x; i < n; i += RSP_THREADS) {
         const int idx = base + i;
@@ -2516,6 +2520,19 @@ __global__ __launch_bounds__(RSP_THREADS, RSP_K3_WGS) void k3_cfar(Geometry g, D
             if (idx < g.max_dets) s9_estimate<T>(s9c, st, P, G, Gp, v, r, pair, MA, MB, RA, RB, &fp.dets[f][idx]);
         }
     }
+}
+
+// rdm_for_cfar_all alone, for a range window that leaves no cell under test (G <= 2 (rR + gR):
+// k3_cfar has no tile then): S = |A| + |B| of every cell, the add k3_cfar's tile load makes.
+// Grid: (cells / RSP_THREADS, pairs, frames).
+template <class T>
+__global__ __launch_bounds__(RSP_THREADS) void k3_smap(Geometry g, FramePtrs fp) {
+    const int pair = blockIdx.y, f = blockIdx.z, e = blockIdx.x * RSP_THREADS + threadIdx.x;
+    if (!fp.smap[f] || e >= g.P * g.G) return;
+    const int v = e / g.G, r = e - v * g.G;
+    const T* MA = static_cast<const T*>(fp.mag[f]) + (size_t)pair * g.P * g.Gp;
+    const T* MB = MA + (size_t)g.P * g.Gp;
+    static_cast<T*>(fp.smap[f])[(size_t)pair * g.P * g.G + e] = MA[(size_t)v * g.Gp + r] + MB[(size_t)v * g.Gp + r];
 }
 
 // ======================================================================================
@@ -2848,7 +2865,16 @@ static hipError_t launch_k3_p(const Geometry& g, const DevConsts& k, const Frame
 }
 
 hipError_t launch_k3(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, hipStream_t s) {
-    if (g.B < 2 || g.G - 2 * (g.refR + g.guardR) <= 0) return hipSuccess;
+    if (g.B < 2) return hipSuccess;
+    if (g.G - 2 * (g.refR + g.guardR) <= 0) {   // no range cell under test: no detections, the maps on request
+        bool want = false;
+        for (int f = 0; f < nf; ++f) want = want || fp.smap[f];
+        if (!want) return hipSuccess;
+        const dim3 grid((g.P * g.G + RSP_THREADS - 1) / RSP_THREADS, g.B - 1, nf);
+        if (g.prec == RSP_PREC_F64) hipLaunchKernelGGL(k3_smap<double>, grid, dim3(RSP_THREADS), 0, s, g, fp);
+        else hipLaunchKernelGGL(k3_smap<float>, grid, dim3(RSP_THREADS), 0, s, g, fp);
+        return hipGetLastError();
+    }
     return g.prec == RSP_PREC_F64 ? launch_k3_p<double>(g, k, fp, nf, s) : launch_k3_p<float>(g, k, fp, nf, s);
 }
 

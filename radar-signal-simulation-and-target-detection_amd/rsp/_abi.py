@@ -81,6 +81,11 @@ class K1Route(ct.Structure):
                 ('stage2_lgp', ct.c_int32)]
 
 
+class K3Tiling(ct.Structure):
+    _fields_ = [('fast', ct.c_int32), ('RT', ct.c_int32), ('hR', ct.c_int32), ('W', ct.c_int32),
+                ('n_tiles', ct.c_int32), ('n_bands', ct.c_int32), ('VB', ct.c_int32), ('rows', ct.c_int32)]
+
+
 RSP_PLAN_K1_TILED = 1
 RSP_PLAN_MONOPULSE_COMPLEX = 2
 
@@ -155,6 +160,10 @@ PROTOTYPES = {
     'rsp_plan_describe': (ct.c_int32, [ct.POINTER(SigConfig), ct.POINTER(CfarParams), ct.POINTER(ClusterParams),
                                        ct.POINTER(Precomputed), ct.POINTER(PlanOptions), ct.c_int32, ct.POINTER(Sizes),
                                        ct.POINTER(K1Route)]),
+    'rsp_query_k3_tiling': (ct.c_int32, [_P, ct.POINTER(K3Tiling)]),
+    'rsp_plan_describe_k3': (ct.c_int32, [ct.POINTER(SigConfig), ct.POINTER(CfarParams), ct.POINTER(ClusterParams),
+                                          ct.POINTER(Precomputed), ct.POINTER(PlanOptions), ct.c_int32,
+                                          ct.POINTER(K3Tiling)]),
     'rsp_process_cube': (ct.c_int32, [_P, _P, ct.c_int32, ct.c_int32, ct.c_int32, ct.POINTER(FrameOut)]),
     'rsp_process_targets': (ct.c_int32, [_P, ct.POINTER(TargetIn), ct.c_int32, ct.c_int32, ct.c_uint64,
                                          ct.c_double, ct.POINTER(FrameOut)]),

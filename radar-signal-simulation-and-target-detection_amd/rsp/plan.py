@@ -97,6 +97,23 @@ def describe(config, cfar_params, cluster_params, precomputed_data, precision='c
     return s, _route_dict(r)
 
 
+def _tiling_dict(t):
+    return dict(fast=bool(t.fast), RT=t.RT, hR=t.hR, W=t.W, n_tiles=t.n_tiles, n_bands=t.n_bands, VB=t.VB,
+                rows=t.rows)
+
+
+def describe_k3(config, cfar_params, cluster_params, precomputed_data, precision='c128', k1_tiled=False, ncu=256):
+    """``Plan.k3_tiling()`` of the plan these arguments would give, without a device
+    (rsp_plan_describe_k3); refusals as ``describe``."""
+    keep = []
+    cfg, cfar, cluster, pre = _marshal(config, cfar_params, cluster_params, precomputed_data, keep)
+    opt = _options(0, 1, precision, k1_tiled, 'amplitude')
+    t = _abi.K3Tiling()
+    check(lib().rsp_plan_describe_k3(ct.byref(cfg), ct.byref(cfar), ct.byref(cluster), ct.byref(pre), ct.byref(opt),
+                                     int(ncu), ct.byref(t)))
+    return _tiling_dict(t)
+
+
 class Plan:
     """One device plan = the reference's per-frame kernel bound to fixed config/precompute.
 
@@ -150,6 +167,15 @@ class Plan:
         r = _abi.K1Route()
         check(lib().rsp_query_k1_route(self.h, ct.byref(r)))
         return _route_dict(r)
+
+    def k3_tiling(self):
+        """How this plan tiles the CFAR/S9 kernel (rsp_query_k3_tiling): ``fast`` (the compile-time
+        5/5/10/10 kernel with halo-less tiles, else the generic one), ``RT`` range cells under test
+        per tile, ``hR`` range halo, ``W`` LDS row stride, ``n_tiles`` range tiles, ``n_bands``
+        Doppler bands of ``VB`` cells under test, ``rows`` Doppler rows per tile."""
+        t = _abi.K3Tiling()
+        check(lib().rsp_query_k3_tiling(self.h, ct.byref(t)))
+        return _tiling_dict(t)
 
     # ---- synchronous frame paths ---------------------------------------------------------
     def _frame_out(self, want_rdm, want_cfar):

@@ -111,8 +111,98 @@ def _route_targets(cfg, ang, slow=False):
     return tg
 
 
+# ---- K3 (CFAR + S9) window shapes, Doppler bands and tile edges --------------------------------
+# One case per path of k3_cfar that the named configurations and the route cases do not reach, each
+# on the `plumbing` waveform with 16 channels and a noise-only cube (k3_noise_cube): at these
+# thresholds the hits are spread over the whole map, so every band's first and last row under test
+# and the outermost range cells carry some.  win = (refR, guardR, refV, guardV); tiling = what
+# Plan.k3_tiling() / rsp.plan.describe_k3 must report per precision (the tests assert it, so a
+# change of derive_k3_tiling cannot silently move a case off the path it is there for).
+# test_k3_window_cases.py holds the oracle's preconditions and prints the measured figures.
+#   min         1/0 windows: S9's 4-point Doppler windows at v = 1 and v = P - 2, the max(.., 2) range halo
+#   min-r4      the same at T = 0.9: also hits on the outermost range cells under test, r = 1 and
+#               r = G - 2 (S9's 4-point range windows; at T = 1.2 these two gates never hit)
+#   div37       refR != refV: noise2's two quotients, divisors 3 and 7
+#   div37-b2    the same with one beam pair
+#   rc17        refR + guardR = 17, no multiple of 4: the first tile starts left of the first cell
+#               under test and tile column 0 left of the map
+#   rc17-dense  more than K3_QCAP = 1024 hits per tile: the generic kernel's overflow pass
+#   bands-hv1   two Doppler bands with a 1-row Doppler halo: S9's rows v +- 2 leave the tile
+#   fast-2band  the halo-less 5/10/5/10 kernel with two Doppler bands and thousands of hits
+#   empty-r, empty-v   no range cell / no Doppler cell under test
+def _k3(P, B, win, T, both, c128, c64):
+    return dict(P=P, B=B, C=16, win=win, T=T, tiling={'c128': dict(both, **c128), 'c64': dict(both, **c64)})
+
+
+_G32 = dict(RT=32, n_tiles=16)
+_G64 = dict(RT=64, n_tiles=8)
+K3_CASES = {
+    'min': _k3(16, 3, (1, 0, 1, 0), 1.2, dict(fast=False, hR=4, n_bands=1, VB=14, rows=16),
+               dict(_G32, W=42), dict(_G64, W=72)),
+    'min-r4': _k3(16, 3, (1, 0, 1, 0), 0.9, dict(fast=False, hR=4, n_bands=1, VB=14, rows=16),
+                  dict(_G32, W=42), dict(_G64, W=72)),
+    'div37': _k3(32, 3, (3, 1, 7, 0), 1.5, dict(fast=False, hR=4, n_bands=1, VB=18, rows=32),
+                 dict(_G32, W=42), dict(_G64, W=72)),
+    'div37-b2': _k3(32, 2, (3, 1, 7, 0), 1.5, dict(fast=False, hR=4, n_bands=1, VB=18, rows=32),
+                    dict(_G32, W=42), dict(_G64, W=72)),
+    'rc17': _k3(64, 3, (6, 11, 3, 2), 2.0, dict(fast=False, hR=20, n_bands=1, VB=54, rows=64),
+                dict(RT=32, n_tiles=15, W=74), dict(_G64, W=104)),
+    'rc17-dense': _k3(64, 3, (6, 11, 3, 2), 0.5, dict(fast=False, hR=20, n_bands=1, VB=54, rows=64),
+                      dict(RT=32, n_tiles=15, W=74), dict(_G64, W=104)),
+    'bands-hv1': _k3(128, 3, (8, 20, 1, 0), 1.5, dict(fast=False, hR=28, n_bands=2, VB=63, rows=65),
+                     dict(RT=32, n_tiles=15, W=90), dict(_G64, W=120)),
+    'fast-2band': _k3(256, 3, (5, 10, 5, 10), 2.0, dict(fast=True, hR=16, n_bands=2, VB=113, rows=113),
+                      dict(_G32, W=34), dict(_G64, W=64)),
+    # G = 512 = 2 (100 + 156): no range tile
+    'empty-r': _k3(16, 3, (100, 156, 1, 0), 2.0, dict(fast=False, hR=256, n_tiles=0),
+                   dict(RT=32, W=546, n_bands=2, VB=7, rows=9), dict(RT=64, W=576, n_bands=1, VB=14, rows=16)),
+    # P = 16 = 2 * 8: the band has no row under test (VB = 1 is derive_k3_tiling's floor)
+    'empty-v': _k3(16, 3, (1, 0, 8, 0), 1.0, dict(fast=False, hR=4, n_bands=1, VB=1, rows=16),
+                   dict(_G32, W=42), dict(_G64, W=72)),
+}
+
+
+def k3_scenario(name):
+    kc = K3_CASES[name]
+    cfg = plumbing_config(kc['P'], kc['B'], kc['C'])
+    W, ang, k = plumbing_weights(cfg)
+    rR, gR, rV, gV = kc['win']
+    cfar = dict(refCells_R=rR, guardCells_R=gR, refCells_V=rV, guardCells_V=gV, T_CFAR=kc['T'], method='GOCA')
+    return cfg, cfar, C.default_cluster_params(), W, ang, k
+
+
+def k3_noise_cube(s, prec):
+    """The noise-only cube of a K3 case: complex128, or rounded to complex64 for the c64 plans."""
+    raw = chain.philox_noise(s['cfg'], 1, SEED)
+    return raw if prec == 'c128' else raw.astype(np.complex64)
+
+
+def k3_oracle(s, cube):
+    """(rdm, detections, S_all) of the oracle's S5..S8 (process_cube's S9 loop over every hit of
+    the dense case takes minutes)."""
+    pre = s['pre_o']
+    rdm = chain.mtd(chain.pulse_compress(chain.dbf(cube.astype(np.complex128), pre['DBF_coeffs_data_C']), pre), pre)
+    dets, S_all = chain.goca_cfar(rdm, s['cfar'])
+    return rdm, dets, S_all
+
+
+def k3_band_edges(P, win, tiling):
+    """First and last Doppler row under test (0-based) of every band of a tiling, as k3_cfar's v0, v1."""
+    hV = win[2] + win[3]
+    out = []
+    for b in range(tiling['n_bands']):
+        v0, v1 = hV + b * tiling['VB'], min(hV + (b + 1) * tiling['VB'], P - hV)
+        out.append((v0, v1 - 1))
+    return out
+
+
 def scenario(name):
-    cfg, cfar, clus, W, ang, k = _route_scenario(name) if name in ROUTE_CASES else C.named_config(name)
+    if name in ROUTE_CASES:
+        cfg, cfar, clus, W, ang, k = _route_scenario(name)
+    elif name in K3_CASES:
+        cfg, cfar, clus, W, ang, k = k3_scenario(name)
+    else:
+        cfg, cfar, clus, W, ang, k = C.named_config(name)
     pre_o = oracle_precompute.precompute(cfg, W, ang, k, C.V8_FIR)
     pre_p = product_precompute(cfg, W, ang, k, C.V8_FIR)
     return dict(name=name, cfg=cfg, cfar=cfar, clus=clus, pre_o=pre_o, pre_p=pre_p)

@@ -46,7 +46,8 @@ STRUCTS = {'rsp_sig_config': _abi.SigConfig, 'rsp_cfar_params': _abi.CfarParams,
            'rsp_frame_out': _abi.FrameOut, 'rsp_sizes': _abi.Sizes, 'rsp_music_config': _abi.MusicConfig,
            'rsp_music_scene': _abi.MusicScene, 'rsp_music_out': _abi.MusicOut, 'rsp_track_point': _abi.TrackPoint,
            'rsp_inter_frame_params': _abi.InterFrameParams, 'rsp_track': _abi.Track,
-           'rsp_plan_options': _abi.PlanOptions, 'rsp_k1_route': _abi.K1Route}
+           'rsp_plan_options': _abi.PlanOptions, 'rsp_k1_route': _abi.K1Route,
+           'rsp_k3_tiling': _abi.K3Tiling}
 
 
 def test_struct_layouts_match_header():
@@ -86,6 +87,8 @@ def test_null_arguments_are_rejected():
     assert b'null' in lib.rsp_last_error()
     assert lib.rsp_query_sizes(None, None) == _abi.RSP_ERR_INVALID
     assert lib.rsp_query_k1_route(None, None) == _abi.RSP_ERR_INVALID
+    assert lib.rsp_query_k3_tiling(None, None) == _abi.RSP_ERR_INVALID
+    assert lib.rsp_plan_describe_k3(None, None, None, None, None, 256, None) == _abi.RSP_ERR_INVALID
     assert lib.rsp_drain(None) == _abi.RSP_ERR_INVALID
     assert lib.rsp_process_cube(None, None, 1, 0, 0, None) == _abi.RSP_ERR_INVALID
     assert lib.rsp_stage_name(99) == b'?'
