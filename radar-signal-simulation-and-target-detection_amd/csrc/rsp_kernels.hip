@@ -79,8 +79,6 @@ __device__ __forceinline__ double cmag(d2 x) {
 
 // Raw buffer resources (SRSRC): 32-bit byte offsets and hardware range checking.  An offset at
 // or past num_records reads 0 / drops the store, so masked lanes need no branch or select.
-// The read/write barrier inside an in-place LDS pass (every read of the pass before any write)
-#define RSP_WAR_SYNC() __syncthreads()
 #define RSP_OOB 0x80000000u   // > any buffer this library makes (plans are validated < 2 GB/frame)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* p, unsigned bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
@@ -486,7 +484,7 @@ template <int R, bool INV, int NB, int SH, int NTHR, int LGL, int LGNS, bool CMP
 __device__ __forceinline__ void sh_pass(V* buf, int rs, int nrows, const TW& tw, const St& st) {
     V v[NB][R];
     sh_load<R, INV, NB, SH, NTHR, LGL, LGNS, CMP, XL>(buf, rs, nrows, tw, v);
-    if constexpr (StoresLds<St>::value) RSP_WAR_SYNC();
+    if constexpr (StoresLds<St>::value) __syncthreads();   // every read of the pass before any write
     sh_store<R, INV, NB, SH, NTHR, LGL, LGNS>(v, rs, nrows, st);
     if constexpr (TAIL) __syncthreads();
 }
@@ -593,7 +591,7 @@ template <int R, bool INV, int NB, int SH, int NTHR, int L, int NS, bool CMP, in
 __device__ __forceinline__ void shg_pass(V* buf, int rs, int nrows, const TW& tw, const St& st) {
     V v[NB][R];
     shg_load<R, INV, NB, SH, NTHR, L, NS, CMP, XL>(buf, rs, nrows, tw, v);
-    RSP_WAR_SYNC();
+    __syncthreads();   // every read of the pass before any write
     shg_store<R, INV, NB, SH, NTHR, L, NS>(v, rs, nrows, st);
     __syncthreads();
 }
@@ -661,6 +659,35 @@ template <> struct Dbf<double> {
     static __device__ __forceinline__ int row(int grp, int i) { return grp + 4 * i; }
 };
 
+// A table from global memory into LDS, all NTHR threads of the workgroup.
+template <int NTHR, class V>
+__device__ __forceinline__ void stage_lds(V* lds, const V* glob, int n) {
+    for (int i = threadIdx.x; i < n; i += NTHR) lds[i] = glob[i];
+}
+
+// Flat tile index TT of a persistent launch -> (frame, tile).
+struct FrameTile { int f, tile; };
+__device__ __forceinline__ FrameTile frame_tile(const Geometry& g, int TT) {
+    const int f = __builtin_amdgcn_readfirstlane(TT / g.ntiles);
+    return FrameTile{f, TT - f * g.ntiles};
+}
+
+// Bin v (after fftshift: frequency v - P/2 mod P) of the direct O(P^2) DFT of col[0 .. P), the
+// index into twP = W_P^i walked mod P.
+template <class V>
+__device__ __forceinline__ V dft_bin(const V* col, const V* twP, int P, int v) {
+    int kk = v - (P >> 1);
+    if (kk < 0) kk += P;
+    V acc = V{};
+    int idx = 0;
+    for (int p = 0; p < P; ++p) {
+        acc += vmul(col[p], twP[idx]);
+        idx += kk;
+        if (idx >= P) idx -= P;
+    }
+    return acc;
+}
+
 // D of one sub-tile (sample nl, pulses p .. p + PPL*... of this lane) x window -> padded LDS
 // columns [b * NT + nl][Ppad] (Re / Im parts as two scalar stores).
 // plim: pulses >= plim (the last sub-tile's lanes past P when P is not a multiple of 16) are not
@@ -706,14 +733,18 @@ __device__ __forceinline__ void dbf_store(T* Yf, const typename Dbf<T>::Acc (&ac
 // row = b NT + nl, frequency o -> Doppler cell v = (o + P/2) mod P.  16 lanes of a butterfly
 // group write consecutive v of one column (64 B apart) and the next 16 lanes the neighbouring
 // column, so the lines fill within the workgroup.
+// Byte offset in z of column col = b NT + nl of store s's tile at Doppler cell v (StoreZ, StoreZq).
+template <class V, class St>
+__device__ __forceinline__ unsigned z_off(const St& s, int col, int v) {
+    const int b = col >> s.lgNT, nl = col & ((1 << s.lgNT) - 1);
+    const int np = (s.tile << s.lgNT) + nl;   // compacted sample
+    return (unsigned)((((b * s.nzc + (np >> s.lgNZ)) * s.P + v) << s.lgNZ) + (np & ((1 << s.lgNZ) - 1))) * (unsigned)sizeof(V);
+}
 template <class V>
 struct StoreZ {
     __amdgpu_buffer_rsrc_t z; int lgNT, nzc, tile, P, half, lgNZ;
     __device__ __forceinline__ void put(int, int row, int o, int, V x) const {
-        const int b = row >> lgNT, nl = row & ((1 << lgNT) - 1);
-        const int v = (o + half) & (P - 1);
-        const int np = (tile << lgNT) + nl;   // compacted sample
-        buf_st<RSP_Z_AUX>(z, (unsigned)(((((b * nzc + (np >> lgNZ)) * P + v) << lgNZ) + (np & ((1 << lgNZ) - 1)))) * (unsigned)sizeof(V), x);
+        buf_st<RSP_Z_AUX>(z, z_off<V>(*this, row, (o + half) & (P - 1)), x);   // power-of-two P: the wrap is a mask
     }
 };
 
@@ -933,15 +964,12 @@ template <class V>
 struct StoreZq {
     __amdgpu_buffer_rsrc_t z; int lgNT, nzc, tile, P, half, lgNZ;
     __device__ __forceinline__ void put(int col, int o, V x) const {
-        const int b = col >> lgNT, nl = col & ((1 << lgNT) - 1);
         int v = o + half;
         v = v >= P ? v - P : v;
-        const int np = (tile << lgNT) + nl;
         // default cache policy, not non-temporal: one store instruction writes 4 consecutive bins
         // (64 B) of each column and the next one of the wave the other half of the 128-B line,
         // which then merge in L2 (non-temporal partial lines went to HBM unmerged: 1.8x the bytes)
-        buf_st<0>(z, (unsigned)((((b * nzc + (np >> lgNZ)) * P + v) << lgNZ) + (np & ((1 << lgNZ) - 1))) *
-                         (unsigned)sizeof(V), x);
+        buf_st<0>(z, z_off<V>(*this, col, v), x);
     }
 };
 
@@ -1072,10 +1100,8 @@ __global__ __launch_bounds__(K1_THREADS, 2) void k1_dbf_mtd(Geometry g, DevConst
         for (int i = threadIdx.x + TWPRE * K1_THREADS; i < ntw; i += K1_THREADS) twl[i] = twPp[i];
     }
     if (RQ && rq) {
-        const V* __restrict__ twQ = static_cast<const V*>(k.twQ);
-        const V* __restrict__ twP = static_cast<const V*>(k.twP);
-        for (int i = threadIdx.x; i < g.twq_elems; i += K1_THREADS) twl[i] = twQ[i];
-        for (int i = threadIdx.x; i < P; i += K1_THREADS) twl[g.twq_elems + i] = twP[i];
+        stage_lds<K1_THREADS>(twl, static_cast<const V*>(k.twQ), g.twq_elems);
+        stage_lds<K1_THREADS>(twl + g.twq_elems, static_cast<const V*>(k.twP), P);
     }
     __syncthreads();
     V* __restrict__ z = static_cast<V*>(fp.z[f]);
@@ -1104,17 +1130,7 @@ __global__ __launch_bounds__(K1_THREADS, 2) void k1_dbf_mtd(Geometry g, DevConst
         for (int e = threadIdx.x; e < B * zslab; e += K1_THREADS) {
             const int b = e / zslab, rem = e - b * zslab;
             const int v = rem >> lgNT, nl = rem & (NT - 1);
-            int kk = v - half;
-            if (kk < 0) kk += P;
-            const V* colv = Y + (b * NT + nl) * Ppad;
-            V acc = V{};
-            int idx = 0;
-            for (int p = 0; p < P; ++p) {
-                acc += vmul(colv[p], twP[idx]);
-                idx += kk;
-                if (idx >= P) idx -= P;
-            }
-            z[zaddr(g, b, v, tile * NT + nl)] = acc;
+            z[zaddr(g, b, v, tile * NT + nl)] = dft_bin(Y + (b * NT + nl) * Ppad, twP, P, v);
         }
     }
 }
@@ -1145,13 +1161,8 @@ __global__ __launch_bounds__(K1_THREADS, 1) void k1p_dbf_mtd(Geometry g, DevCons
     int TT = blockIdx.x;
     if (TT >= total) return;
     static_assert(LGP >= 6 && LGP <= 8, "the persistent K1 runs P = 64 .. 256 (k1_persistent_fits)");
-    if constexpr (K1_DIF) {   // k1_fft_dif's table, 4 x P/16
-        const V* __restrict__ twD = static_cast<const V*>(k.twD);
-        for (int i = threadIdx.x; i < (P >> 2); i += K1_THREADS) twl[i] = twD[i];
-    } else {
-        const V* __restrict__ twPp = static_cast<const V*>(k.twPp);
-        for (int i = threadIdx.x; i < g.twPp_elems; i += K1_THREADS) twl[i] = twPp[i];
-    }
+    if constexpr (K1_DIF) stage_lds<K1_THREADS>(twl, static_cast<const V*>(k.twD), P >> 2);   // k1_fft_dif's table, 4 x P/16
+    else stage_lds<K1_THREADS>(twl, static_cast<const V*>(k.twPp), g.twPp_elems);
     constexpr int NJ = CP / 4, MB = BMAX <= 8 ? 1 : 2, TPW = TPWX;
     constexpr int PT = 16 * D::PPL;
     const int lane = threadIdx.x & 63, grp = lane >> 4, col = lane & 15;
@@ -1165,7 +1176,7 @@ __global__ __launch_bounds__(K1_THREADS, 1) void k1p_dbf_mtd(Geometry g, DevCons
     T* Al = reinterpret_cast<T*>(twl + P);
     T are[MB][NJ], aim[MB][NJ];
     if constexpr (ALDS) {
-        for (int i = threadIdx.x; i < MB * NJ * 2 * 64; i += K1_THREADS) Al[i] = At[i];
+        stage_lds<K1_THREADS>(Al, At, MB * NJ * 2 * 64);
     } else {
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb)
@@ -1204,10 +1215,11 @@ __global__ __launch_bounds__(K1_THREADS, 1) void k1p_dbf_mtd(Geometry g, DevCons
     const unsigned cube_bytes = (unsigned)((size_t)C * NPc * sizeof(V));
     typename D::Ld xv[TPW][NJ];
     bool vld[TPW];   // wave-uniform: sub-tile u of the tile in flight lies inside the used samples
+    // (k1q_dbf_mtd's issue differs on purpose: it re-forms the lane offsets instead of keeping loff[][])
     auto issue_u = [&](int Tn, int u) {   // cube loads of sub-tile u of tile Tn (fsf:93 operands) into xv[u]
-        const int f = __builtin_amdgcn_readfirstlane(Tn / g.ntiles), tile = Tn - f * g.ntiles;
-        const __amdgpu_buffer_rsrc_t xr = buf_rsrc(fp.in[f], cube_bytes);
-        const int np = tile * NT + nlv[u];
+        const FrameTile ft = frame_tile(g, Tn);
+        const __amdgpu_buffer_rsrc_t xr = buf_rsrc(fp.in[ft.f], cube_bytes);
+        const int np = ft.tile * NT + nlv[u];
         vld[u] = nlv[u] >= 0 && np < g.nU;
         if (vld[u]) {   // no else: zeroing xv here would wait (vmcnt) on the pending z stores
             const int soff = used_sample(g, np) * P * (int)sizeof(V);
@@ -1268,7 +1280,8 @@ __global__ __launch_bounds__(K1_THREADS, 1) void k1p_dbf_mtd(Geometry g, DevCons
         const int Tn = TT + gridDim.x;
         K1_STAMP(it, 0);
         if (!EARLY && Tn < total) issue(Tn);   // next tile's loads fly during this tile's FFT + z stores
-        const int f = __builtin_amdgcn_readfirstlane(TT / g.ntiles), tile = TT - f * g.ntiles;
+        const FrameTile ft = frame_tile(g, TT);
+        const int f = ft.f, tile = ft.tile;
         if (tile == 0 && threadIdx.x == 0 && fp.count[f]) *fp.count[f] = 0;   // K3's detection counter
         V* __restrict__ z = static_cast<V*>(fp.z[f]);
         const StoreZ<V> sz{buf_rsrc(z, (unsigned)(B * g.nzc * P * g.NZ * sizeof(V))), lgNT, g.nzc, tile, P, half, ilog2(g.NZ)};
@@ -1317,14 +1330,9 @@ __global__ __launch_bounds__(K1_THREADS, 1) void k1q_dbf_mtd(Geometry g, DevCons
     const int total = nf * g.ntiles;
     int TT = blockIdx.x;
     if (TT >= total) return;
-    {
-        const V* __restrict__ tq = static_cast<const V*>(k.twQ);
-        const V* __restrict__ tp = static_cast<const V*>(k.twP);
-        const T* __restrict__ At = static_cast<const T*>(k.Atab);
-        for (int i = threadIdx.x; i < g.twq_elems; i += K1_THREADS) twq[i] = tq[i];
-        for (int i = threadIdx.x; i < P; i += K1_THREADS) twp[i] = tp[i];
-        for (int i = threadIdx.x; i < MB * NJ * 2 * 64; i += K1_THREADS) Al[i] = At[i];
-    }
+    stage_lds<K1_THREADS>(twq, static_cast<const V*>(k.twQ), g.twq_elems);
+    stage_lds<K1_THREADS>(twp, static_cast<const V*>(k.twP), P);
+    stage_lds<K1_THREADS>(Al, static_cast<const T*>(k.Atab), MB * NJ * 2 * 64);
     __syncthreads();   // the first DBF reads Atab entries other waves wrote
     constexpr int PT = 16 * D::PPL;
     const int lane = threadIdx.x & 63, grp = lane >> 4, col = lane & 15;
@@ -1349,14 +1357,15 @@ __global__ __launch_bounds__(K1_THREADS, 1) void k1q_dbf_mtd(Geometry g, DevCons
     const unsigned cube_bytes = (unsigned)((size_t)C * g.cpitch * sizeof(V));
     typename D::Ld xv[TPW][NJ];
     bool vld[TPW];
+    // (k1p_dbf_mtd's issue_u differs on purpose: it keeps the lane offsets in loff[][] for the kernel's life)
     auto issue = [&](int Tn) {   // cube loads of tile Tn (fsf:93 operands) into xv
-        const int f = __builtin_amdgcn_readfirstlane(Tn / g.ntiles), tile = Tn - f * g.ntiles;
-        const __amdgpu_buffer_rsrc_t xr = buf_rsrc(fp.in[f], cube_bytes);
+        const FrameTile ft = frame_tile(g, Tn);
+        const __amdgpu_buffer_rsrc_t xr = buf_rsrc(fp.in[ft.f], cube_bytes);
         int gq = grp;
         asm volatile("" : "+v"(gq));   // the lane offsets are formed here, not kept live across the DFT
 #pragma unroll
         for (int u = 0; u < TPW; ++u) {
-            const int np = tile * NT + nlv[u];
+            const int np = ft.tile * NT + nlv[u];
             vld[u] = nlv[u] >= 0 && np < g.nU;
             if (vld[u]) {
                 const int soff = used_sample(g, np) * P * (int)sizeof(V);
@@ -1397,7 +1406,8 @@ __global__ __launch_bounds__(K1_THREADS, 1) void k1q_dbf_mtd(Geometry g, DevCons
         }
         if (Tn < total) issue(Tn);   // the next tile's loads fly during this tile's DFT
         K1_STAMP(it, 1);
-        const int f = __builtin_amdgcn_readfirstlane(TT / g.ntiles), tile = TT - f * g.ntiles;
+        const FrameTile ft = frame_tile(g, TT);
+        const int f = ft.f, tile = ft.tile;
         if (tile == 0 && threadIdx.x == 0 && fp.count[f]) *fp.count[f] = 0;   // K3's detection counter
         __syncthreads();   // the tile (and, the first time, the tables) in LDS
         K1_STAMP(it, 2);
@@ -1486,6 +1496,19 @@ __device__ __forceinline__ ZWin zrow_window(const Geometry& g, const V* z, int r
     const V* base = z + ((size_t)b * g.nzc * g.P + v) * g.NZ + w.e_lo;
     w.r = buf_rsrc(base, rho < rows_total ? (unsigned)(e_hi - w.e_lo + 1) * (unsigned)sizeof(V) : 0u);
     return w;
+}
+// The R0 samples n' = np0 + r NB0, r < R0, of one pass-0 butterfly through its row's window zw (a
+// scalar buffer resource, uniform per wave: a load's offset needs no mask).
+template <int NB0, int R0, class V>
+__device__ __forceinline__ void k2_load_wrow(const Geometry& g, const ZWin& zw, int np0, V (&v)[R0]) {
+    if ((NB0 & (g.NZ - 1)) == 0) {   // uniform: element r sits r (NB0 P) past element 0
+        const unsigned e0 = (unsigned)zw.rel(np0) * (unsigned)sizeof(V), st = (unsigned)(NB0 * g.P) * (unsigned)sizeof(V);
+#pragma unroll
+        for (int r = 0; r < R0; ++r) v[r] = buf_ld<V>(zw.r, e0 + r * st);
+    } else {
+#pragma unroll
+        for (int r = 0; r < R0; ++r) v[r] = buf_ld<V>(zw.r, (unsigned)zw.rel(np0 + r * NB0) * (unsigned)sizeof(V));
+    }
 }
 
 // LDS pad of the overlap-save rows: one complex per 32.  For 16-B elements this keeps every
@@ -1616,16 +1639,7 @@ __device__ __forceinline__ void k2_fft_job(const Geometry& g, const DevConsts& k
         const int rl = __builtin_amdgcn_readfirstlane(tid / nb0);
         // waves past the block's rows (fewer rows than 256 / nb0) load nothing
         const ZWin zw = zrow_window(g, z, row0 + rl, rl < rows ? rows_total : 0, off, lo, hi);
-        const int j = tid & (nb0 - 1);
-        const int np0 = a + j - lo + off;
-        if ((nb0 & (g.NZ - 1)) == 0) {   // uniform: element r sits r (nb0 P) past element 0
-            const unsigned e0 = (unsigned)zw.rel(np0) * (unsigned)sizeof(V), st = (unsigned)(nb0 * P) * (unsigned)sizeof(V);
-#pragma unroll
-            for (int r = 0; r < R0; ++r) v0[0][r] = buf_ld<V>(zw.r, e0 + r * st);
-        } else {
-#pragma unroll
-            for (int r = 0; r < R0; ++r) v0[0][r] = buf_ld<V>(zw.r, (unsigned)zw.rel(np0 + r * nb0) * (unsigned)sizeof(V));
-        }
+        k2_load_wrow<nb0>(g, zw, a + (tid & (nb0 - 1)) - lo + off, v0[0]);
     }
     const __amdgpu_buffer_rsrc_t zr = buf_rsrc(z, (unsigned)(g.B * g.nzc * P * g.NZ * sizeof(V)));
 #pragma unroll
@@ -1673,13 +1687,12 @@ __device__ __forceinline__ void k2_fft_job(const Geometry& g, const DevConsts& k
     // 2-per-CU workgroup's LDS and are read from L1/L2 instead
     constexpr bool TW_LDS = LGM <= 11 && !NOPAD;
     V* twL = L + k2_lds_data(g.k2_pts, SH);
-    if constexpr (TW_LDS)
-        for (int e = tid; e < k2_tw_lds(LGM); e += K2_THREADS) twL[e] = twl[e];   // visible after the pass-0 barrier
+    if constexpr (TW_LDS) stage_lds<K2_THREADS>(twL, twl, k2_tw_lds(LGM));   // visible after the pass-0 barrier
     const auto twF = k2_tw_src<TW_LDS, V>(twL, twl);
     const auto twI = k2_tw_sym(LGM) ? twF : twF + NTWF;
     // forward pass 0 (Ns = 1, no twiddles) straight from the loaded samples
     // the Ns = 1 passes' outputs XOR-swizzled (sh_store) when a middle pass reads them (3 passes)
-    constexpr int XZ = (NP == 3 && R0 == 16 && RL == 16 && 1) ? 1 : 0;
+    constexpr int XZ = (NP == 3 && R0 == 16 && RL == 16) ? 1 : 0;
     sh_store<R0, false, NB0, SH, K2_THREADS, LGM, 0, XZ>(v0, rs, rows, StoreLds<V>{L});
     __syncthreads();
     K2_STAMP(1);
@@ -1691,7 +1704,7 @@ __device__ __forceinline__ void k2_fft_job(const Geometry& g, const DevConsts& k
         V v[NBL][RL];
         sh_load<RL, false, NBL, SH, K2_THREADS, LGM, LGM - RBL, CMP>(L, rs, rows,
                                                                       twF + tw_pass_off(LGM, NP - 1, false, CMP, PAL), v);
-        RSP_WAR_SYNC();
+        __syncthreads();   // every read of the pass before any write
 #pragma unroll
         for (int t = 0; t < NBL; ++t) {
             Dft<RL, false, V>::run(v[t]);
@@ -1766,7 +1779,7 @@ __device__ __forceinline__ void k2_fft_job_mix(const Geometry& g, const DevConst
     constexpr int NS1 = R0, NS2 = R0 * R1;                               // Ns of passes 1 and 2
     constexpr int TW2 = NS1 * tw_row(R1, CMP);                           // offset of pass 2's table
     constexpr int NTWF = TW2 + NS2 * tw_row(R0, CMP);
-    const int P = g.P, G = g.G;
+    const int G = g.G;
     const int lo = sd.lo, hi = sd.hi, off = sd.off;
     const int tid = threadIdx.x;
     const int Lh1 = sd.Lh - 1;
@@ -1786,15 +1799,7 @@ __device__ __forceinline__ void k2_fft_job_mix(const Geometry& g, const DevConst
     const int j = tid - rl * nb0;
     if (tid < nb0 * rows) {
         const ZWin zw = zrow_window(g, z, row0 + rl, rows_total, off, lo, hi);
-        const int np0 = a + j - lo + off;
-        if ((nb0 & (g.NZ - 1)) == 0) {   // uniform
-            const unsigned e0 = (unsigned)zw.rel(np0) * (unsigned)sizeof(V), st = (unsigned)(nb0 * P) * (unsigned)sizeof(V);
-#pragma unroll
-            for (int r = 0; r < R0; ++r) v0[0][r] = buf_ld<V>(zw.r, e0 + r * st);
-        } else {
-#pragma unroll
-            for (int r = 0; r < R0; ++r) v0[0][r] = buf_ld<V>(zw.r, (unsigned)zw.rel(np0 + r * nb0) * (unsigned)sizeof(V));
-        }
+        k2_load_wrow<nb0>(g, zw, a + j - lo + off, v0[0]);
         if constexpr (!EPI) {
             const __amdgpu_buffer_rsrc_t hr = buf_rsrc(H + sd.H_off, (unsigned)(M * sizeof(V)));
 #pragma unroll
@@ -1803,8 +1808,7 @@ __device__ __forceinline__ void k2_fft_job_mix(const Geometry& g, const DevConst
         }
     }
     V* twL = L + k2_lds_data(g.k2_pts, SH);
-    if constexpr (!NOPAD)
-        for (int e = threadIdx.x; e < NTWF; e += K2_THREADS) twL[e] = twl[e];
+    if constexpr (!NOPAD) stage_lds<K2_THREADS>(twL, twl, NTWF);
     const auto twF = k2_tw_src<!NOPAD, V>(twL, twl);
     const auto twI = twF;   // palindrome: the reversed plan's table is the forward one
     constexpr int XZ = R0 == 16 ? 1 : 0;   // Ns = 1 outputs XOR-swizzled (see sh_store)
@@ -1816,7 +1820,7 @@ __device__ __forceinline__ void k2_fft_job_mix(const Geometry& g, const DevConst
     {
         V v[NB0][R0];
         shg_load<R0, false, NB0, SH, K2_THREADS, M, NS2, CMP>(L, rs, rows, twF + TW2, v, tid);
-        RSP_WAR_SYNC();
+        __syncthreads();   // every read of the pass before any write
         const __amdgpu_buffer_rsrc_t hr = buf_rsrc(H + sd.H_off, (unsigned)(M * sizeof(V)));
 #pragma unroll
         for (int t = 0; t < NB0; ++t) {
@@ -1885,26 +1889,23 @@ __global__ __launch_bounds__(K2_THREADS, WGS) void k2_pc(Geometry g, DevConsts k
     if (sd.type == 1 && sd.logM == 0) {   // mixed-radix block
         k2_fft_job_mix<T, 2560, 16, 10, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L);
     } else if (sd.type == 1) {
-        if constexpr (WGS >= 3) {   // workgroups sized for the 2560-point block: 2048 points of 2^k rows
-            static_assert(2048 <= 2560, "2^k rows in the 2560-point workgroup");
-            switch (sd.logM) {
-                case 6: k2_fft_job<T, 6, 2048, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
-                case 7: k2_fft_job<T, 7, 2048, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
-                case 8: k2_fft_job<T, 8, 2048, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
-                case 9: k2_fft_job<T, 9, 2048, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
-                case 10: k2_fft_job<T, 10, 2048, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
-                default: k2_fft_job<T, 11, 2048, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
-            }
-        } else {
-            switch (sd.logM) {
-                case 6: k2_fft_job<T, 6, RSP_K2_POINTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
-                case 7: k2_fft_job<T, 7, RSP_K2_POINTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
-                case 8: k2_fft_job<T, 8, RSP_K2_POINTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
-                case 9: k2_fft_job<T, 9, RSP_K2_POINTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
-                case 10: k2_fft_job<T, 10, RSP_K2_POINTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
-                case 11: k2_fft_job<T, 11, RSP_K2_POINTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
-                default: k2_fft_job<T, 12, RSP_K2_POINTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
-            }
+        // workgroups sized for the 2560-point block (WGS >= 3) run 2048 points of 2^k rows, up to
+        // one 2048-point row; the others RSP_K2_POINTS, up to one 4096-point row
+        constexpr int PTS = WGS >= 3 ? 2048 : RSP_K2_POINTS;
+        constexpr int LGTOP = WGS >= 3 ? 11 : 12;   // the largest block: the default
+        switch (sd.logM) {
+            case 6: k2_fft_job<T, 6, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
+            case 7: k2_fft_job<T, 7, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
+            case 8: k2_fft_job<T, 8, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
+            case 9: k2_fft_job<T, 9, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
+            case 10: k2_fft_job<T, 10, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
+            case 11:
+                if constexpr (LGTOP > 11) {
+                    k2_fft_job<T, 11, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L);
+                    break;
+                }
+                [[fallthrough]];
+            default: k2_fft_job<T, LGTOP, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
         }
     } else {
         // direct FIR (narrow segment): filter() + circshift(-fir_delay) (fsf:111-112).  Each
@@ -2132,14 +2133,12 @@ __global__ __launch_bounds__(RSP_THREADS, RSP_K3_WGS) void k3_cfar(Geometry g, D
     typedef typename U16<T>::U U;
     constexpr int EPU = U16<T>::E;
     constexpr bool FAST = RR > 0 && RV > 0 && GR > 0 && GV > 0 && (RTC == 32 || RTC == 64);
-    constexpr int HRC = ((RR + GR > 2 ? RR + GR : 2) + 3) & ~3;   // = g.cfar_hR (rsp_plan.cpp)
-    // = g.cfar_W; complex double rows get 2 extra cells (stride 132 dwords = 4 mod 64 banks), see
-    // the row-group order of the CFAR loop
-    // NOH (the fast path): the tile holds the band's own cells only, no halo; the
-    // prefilter takes whichever range slice lies inside the tile, survivors and S9 read the rest
-    // from the maps
-    constexpr bool NOH = FAST;
-    constexpr int WC = ((RTC + (NOH ? 0 : 2) * HRC + 3) & ~3) + (sizeof(T) == 8 ? 2 : 0);
+    // FAST (the compile-time 5/5/10/10 kernel): the tile holds the band's own cells only, no halo;
+    // the prefilter takes whichever range slice lies inside the tile, survivors and S9 read the
+    // rest from the maps.  The generic kernel's tile holds the halo (g.cfar_W, g.cfar_hR).
+    // FAST rows: RTC cells; complex double rows get 2 extra cells (stride 132 dwords = 4 mod 64
+    // banks), see the row-group order of the CFAR loop
+    constexpr int WC = ((RTC + 3) & ~3) + (sizeof(T) == 8 ? 2 : 0);
     // XCD-aware order (bijective swizzle, cdna_hip_programming.md T1): the workgroups that
     // share an XCD take consecutive (tile, pair) ids with pairs fastest, so beam b's tile --
     // read by pairs b-1 and b -- and the range halos of neighbouring tiles are L2 hits
@@ -2152,17 +2151,18 @@ __global__ __launch_bounds__(RSP_THREADS, RSP_K3_WGS) void k3_cfar(Geometry g, D
     const int pair = wg % npair, col = wg / npair;
     const int tile = col % ntile, col2 = col / ntile;
     const int band = col2 % g.cfar_nband, f = col2 / g.cfar_nband;
-    const int P = g.P, G = g.G, W = FAST ? WC : g.cfar_W, hR = FAST ? HRC : g.cfar_hR, RT = FAST ? RTC : g.cfar_RT;
+    const int P = g.P, G = g.G, W = FAST ? WC : g.cfar_W, hR = FAST ? 0 : g.cfar_hR, RT = FAST ? RTC : g.cfar_RT;
     const int rR = RR ? RR : g.refR, gR = GR ? GR : g.guardR, rV = RV ? RV : g.refV, gV = GV ? GV : g.guardV;
     const int rc0 = rR + gR;                           // first cell under test (0-based)
     const int tstart = (rc0 & ~3) + tile * RT;         // multiple of 4
-    const int c0 = tstart - (NOH ? 0 : hR);            // tile column 0 (multiple of 4; may be < 0)
+    const int c0 = tstart - hR;                        // tile column 0 (multiple of 4; may be < 0)
     const int cut_lo = max(tstart, rc0), cut_hi = min(tstart + RT, G - rc0);
     // Doppler band: cells under test in rows [v0, v1), the tile holds rows [vt0, vt1) (the
-    // band plus the rV + gV window rows on each side; bands of one tile column tile the map)
+    // band alone when FAST, else plus the rV + gV window rows on each side; bands of one tile
+    // column tile the map)
     const int hV = rV + gV;
     const int v0 = hV + band * g.cfar_VB, v1 = min(hV + (band + 1) * g.cfar_VB, P - hV);
-    const int vt0 = NOH ? v0 : max(v0 - hV, 0), vt1 = NOH ? max(v1, v0) : min(v1 + hV, P), nv = vt1 - vt0;
+    const int vt0 = FAST ? v0 : max(v0 - hV, 0), vt1 = FAST ? max(v1, v0) : min(v1 + hV, P), nv = vt1 - vt0;
     int* queue = reinterpret_cast<int*>(S + g.cfar_rows * W);
     int* qn = queue + K3_QCAP;
     const T* Sv = S - vt0 * W;                         // row v of the map at Sv + v W
@@ -2258,7 +2258,7 @@ __global__ __launch_bounds__(RSP_THREADS, RSP_K3_WGS) void k3_cfar(Geometry g, D
         const int nwc = whi - wlo;
         for (int e = threadIdx.x; e < (vhi - vlo) * nwc; e += RSP_THREADS) {
             const int v = vlo + e / nwc, r = wlo + (e - (v - vlo) * nwc);
-            sm[(size_t)v * G + r] = NOH ? sg(v, r) : Sv[v * W + (r - c0)];
+            sm[(size_t)v * G + r] = FAST ? sg(v, r) : Sv[v * W + (r - c0)];
         }
     }
     if (v1 <= v0 || cut_hi <= cut_lo) return;
@@ -2300,8 +2300,8 @@ __global__ __launch_bounds__(RSP_THREADS, RSP_K3_WGS) void k3_cfar(Geometry g, D
         // a thread takes 4 adjacent range cells of one Doppler row: every window value comes
         // from 16-B LDS reads; sums run left to right over each slice like mean()
         constexpr int DL = -(GR + RR), DR = GR + 1;              // window starts rel. to the cell
-        constexpr int BL = floor4(DL), BR = floor4(DR);
-        constexpr int NL = (DL + 3 + RR - BL + 3) / 4, NR = (DR + 3 + RR - BR + 3) / 4;
+        constexpr int BL = floor4(DL);
+        constexpr int NL = (DL + 3 + RR - BL + 3) / 4;
         constexpr int lgT = RTC == 64 ? 4 : 3;                    // log2 threads per row (RT / 4)
         // 16-lane row groups of a wave take rows {0, 2, 1, 3} + 4w: the ds_read_b128 lane groups
         // ({0-3,12-15,20-27}, ... MI355X_MICROARCH.md §LDS) then pair rows 2 apart, 2W = 192
@@ -2317,29 +2317,29 @@ __global__ __launch_bounds__(RSP_THREADS, RSP_K3_WGS) void k3_cfar(Geometry g, D
         // once.  (Rows 2a + {0, 16, 1, 17} with unrotated columns put the two slices in one lane
         // group: 2-way on a quarter of the slots, 30 % of K3's LDS cycles.)
         const int q = lgT == 3 ? ((threadIdx.x & 7) ^ (((rg ^ (rg >> 1)) & 1) << 2)) : threadIdx.x & ((1 << lgT) - 1);
-        const int c = (NOH ? 0 : hR) + 4 * q;                     // first tile column of the group
+        const int c = 4 * q;                                      // first tile column of the group
         const int r = c0 + c;
         const int rgp = lgT == 4 ? (rg & ~3) | ((rg & 1) << 1) | ((rg >> 1) & 1)
                                  : (rg & 1) + ((rg & 2) << 2) + 2 * ((rg >> 2) & 3) + 16 * (rg >> 4);
         // Exact prefilter.  A hit needs CUT > T mean(max of the four slices) >= T mean(left range
         // slice): quot() is the correctly rounded (double) or a monotone (float) quotient and the
         // product with T > 0 rounds monotonically, so a cell with CUT <= T quot(lr) cannot be a
-        // hit.  That test needs the left range slice alone (4 of the 27 ld4 per 4 cells: the CFAR
-        // phase was bound by LDS bandwidth); the rare survivors (T = 8 on amplitude sums: cells
-        // near targets) run the full test below with the same sums in the same order, so the
-        // detection list is the one the full test gives.  A NaN sum never rejects (the
-        // comparison is false).
-        if (NOH || Tc > 0.0) {
+        // hit.  That test needs one range slice alone (4 ld4 per 4 cells, where the full window
+        // took 27: the CFAR phase was bound by LDS bandwidth); the rare survivors (T = 8 on
+        // amplitude sums: cells near targets) run the full test on the maps with the sums in
+        // sum() order, so the detection list is the one the full test gives.  A NaN sum never
+        // rejects (the comparison is false).
+        {
             const T Tt = (T)Tc;
             const bool pf = Tc > 0.0;   // the bound needs T > 0; otherwise every cell takes the full test
-            // NOH: lanes whose 4 cells start in the first 16 tile columns test the right range
-            // slice (cells c + 11 .. c + 15 + 3 <= 30 < RT), the others the left one (c - 15 >= 1):
-            // either is a lower bound of the max.  The right slice's loads start at c + OR so
-            // that both slices sit at the same register offsets when the alignment allows (ld4 of
-            // double: 2 cells; of float: 4 cells, so float selects between offsets 1 and 3)
-            static_assert(!NOH || (RR == 5 && GR == 10 && NL == 3 && BL == -16), "NOH constants for the 5/10 window");
+            // The tile has no halo: lanes whose 4 cells start in the first 16 tile columns test the
+            // right range slice (cells c + 11 .. c + 15 + 3 <= 30 < RT), the others the left one
+            // (c - 15 >= 1): either is a lower bound of the max.  The right slice's loads start at
+            // c + OR so that both slices sit at the same register offsets when the alignment allows
+            // (ld4 of double: 2 cells; of float: 4 cells, so float selects between offsets 1 and 3)
+            static_assert(RR == 5 && GR == 10 && NL == 3 && BL == -16, "slice constants for the 5/10 window");
             constexpr int OR = sizeof(T) == 8 ? 10 : 8, XR = DR - OR;   // XR: register offset of the right slice
-            const bool useR = NOH && q < 4;
+            const bool useR = q < 4;
             const int base = useR ? OR : BL;
 #pragma unroll 1
             for (int v = v0 + rgp; v < v1; v += RSP_THREADS >> lgT) {
@@ -2355,80 +2355,26 @@ __global__ __launch_bounds__(RSP_THREADS, RSP_K3_WGS) void k3_cfar(Geometry g, D
                 ld4(row, cv);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    T lr = 0;   // NOH: the left or the right slice sum (a lower bound either way)
+                    T lr = 0;   // the left or the right slice sum (a lower bound either way)
 #pragma unroll
                     for (int qq = 0; qq < RR; ++qq) {
                         const T xa = xl[i + DL - BL + qq];
-                        if constexpr (NOH && XR != DL - BL) lr += useR ? xl[i + XR + qq] : xa;
+                        if constexpr (XR != DL - BL) lr += useR ? xl[i + XR + qq] : xa;
                         else lr += xa;
                     }
                     const int ri = r + i;
                     if (ri >= cut_lo && ri < cut_hi && (!pf || !(cv[i] <= Tt * quot(lr, fR, iR)))) {
-                        T tr = 0, lv = 0, tv = 0;
-                        if constexpr (NOH) {   // every slice from the maps, in sum() order
-                            lr = 0;
-                            for (int qq = 0; qq < RR; ++qq) lr += sg(v, ri + DL + qq);
-                            for (int qq = 0; qq < RR; ++qq) tr += sg(v, ri + DR + qq);
-                            for (int qq = 0; qq < RV; ++qq) {
-                                lv += sg(v + qq - GV - RV, ri);
-                                tv += sg(v + qq + GV + 1, ri);
-                            }
-                        } else {
-                            const T* cp = row + i;
-#pragma unroll
-                            for (int qq = 0; qq < RR; ++qq) tr += cp[DR + qq];
-#pragma unroll
-                            for (int qq = 0; qq < RV; ++qq) {
-                                lv += cp[(qq - GV - RV) * WC];
-                                tv += cp[(qq + GV + 1) * WC];
-                            }
+                        T tr = 0, lv = 0, tv = 0;   // every slice from the maps, in sum() order
+                        lr = 0;
+                        for (int qq = 0; qq < RR; ++qq) lr += sg(v, ri + DL + qq);
+                        for (int qq = 0; qq < RR; ++qq) tr += sg(v, ri + DR + qq);
+                        for (int qq = 0; qq < RV; ++qq) {
+                            lv += sg(v + qq - GV - RV, ri);
+                            tv += sg(v + qq + GV + 1, ri);
                         }
                         K3_HIT(v, c + i, cv[i], lr, tr, lv, tv);
                     }
                 }
-            }
-        } else
-#pragma unroll 1
-        for (int v = v0 + rgp; v < v1; v += RSP_THREADS >> lgT) {
-            const T* row = Sv + v * WC + c;
-            T xl[4 * NL], xr[4 * NR], cv[4];
-            T lv[4] = {0, 0, 0, 0}, tv[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int j = 0; j < NL; ++j) {
-                T t[4];
-                ld4(row + BL + 4 * j, t);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) xl[4 * j + i] = t[i];
-            }
-#pragma unroll
-            for (int j = 0; j < NR; ++j) {
-                T t[4];
-                ld4(row + BR + 4 * j, t);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) xr[4 * j + i] = t[i];
-            }
-            ld4(row, cv);
-#pragma unroll
-            for (int qq = 0; qq < RV; ++qq) {
-                T a[4], b[4];
-                ld4(row + (qq - GV - RV) * WC, a);
-                ld4(row + (qq + GV + 1) * WC, b);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    lv[i] += a[i];
-                    tv[i] += b[i];
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                T lr = 0, tr = 0;
-#pragma unroll
-                for (int qq = 0; qq < RR; ++qq) {
-                    lr += xl[i + DL - BL + qq];
-                    tr += xr[i + DR - BR + qq];
-                }
-                const int ri = r + i;
-                if (ri >= cut_lo && ri < cut_hi) K3_HIT(v, c + i, cv[i], lr, tr, lv[i], tv[i]);
             }
         }
     } else {
@@ -2463,13 +2409,14 @@ __global__ __launch_bounds__(RSP_THREADS, RSP_K3_WGS) void k3_cfar(Geometry g, D
     if (threadIdx.x == 0) qn[1] = atomicAdd(fp.count[f], n);   // one global reservation per workgroup
     __syncthreads();
     const int base = qn[1];
-    // S(v, r) as the CFAR test read it: the tile, or the maps where a halo-less tile lacks it
-    // The tile's Doppler halo is the window's rV + gV rows; S9 reads rows v - 2 .. v + 2, so with
-    // rV + gV = 1 a hit on a band's first or last row reaches one row past the tile (the rows of
-    // the neighbouring band, outside this tile's LDS): those come from the maps, the same two
-    // values and the same add.  The range halo is never narrower than 2 (derive_k3_tiling).
+    // S(v, r) as the CFAR test read it: FAST, the maps (survivors and S9 never read the tile);
+    // else the tile.  The generic tile's Doppler halo is the window's rV + gV rows; S9 reads rows
+    // v - 2 .. v + 2, so with rV + gV = 1 a hit on a band's first or last row reaches one row past
+    // the tile (the rows of the neighbouring band, outside this tile's LDS): those come from the
+    // maps, the same two values and the same add.  The range halo is never narrower than 2
+    // (derive_k3_tiling).
     auto st = [&](int vv, int rr) -> T {
-        if constexpr (NOH) return sg(vv, rr);
+        if constexpr (FAST) return sg(vv, rr);
         else return vv >= vt0 && vv < vt1 ? Sv[vv * W + (rr - c0)] : sg(vv, rr);
     };
     for (int i = threadIdx.x; i < n; i += RSP_THREADS) {
@@ -2546,8 +2493,7 @@ __global__ __launch_bounds__(RSP_THREADS, 2) void k_mtd_cols(Geometry g, DevCons
     constexpr int GT = 16;
     V* twl = Y + GT * g.Ppad;
     const T* __restrict__ win = static_cast<const T*>(k.win);
-    if constexpr (LGP > 0)
-        for (int i = threadIdx.x; i < tw_total(LGP); i += RSP_THREADS) twl[i] = static_cast<const V*>(k.twPp)[i];
+    if constexpr (LGP > 0) stage_lds<RSP_THREADS>(twl, static_cast<const V*>(k.twPp), tw_total(LGP));
     const int b = blockIdx.y, gt0 = blockIdx.x * GT;
     const int P = g.P, G = g.G, Ppad = g.Ppad;
     for (int e = threadIdx.x; e < P * GT; e += RSP_THREADS) {
@@ -2574,15 +2520,7 @@ __global__ __launch_bounds__(RSP_THREADS, 2) void k_mtd_cols(Geometry g, DevCons
         for (int e = threadIdx.x; e < P * GT; e += RSP_THREADS) {
             const int v = e / GT, gl = e - v * GT;
             const int gg = gt0 + gl;
-            int kk = v - half;
-            if (kk < 0) kk += P;
-            V acc = V{};
-            int idx = 0;
-            for (int p = 0; p < P; ++p) {
-                acc += vmul(Y[gl * Ppad + p], twP[idx]);
-                idx += kk;
-                if (idx >= P) idx -= P;
-            }
+            const V acc = dft_bin(Y + gl * Ppad, twP, P, v);
             if (gg < G) rdm[((size_t)b * P + v) * G + gg] = acc;
         }
     }
@@ -2710,6 +2648,14 @@ static hipError_t allow_lds(K kernel, size_t bytes) {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)bytes);
 }
+// One kernel launch: the LDS opt-in, the launch, the launch's error.
+template <class K, class... A>
+static hipError_t launch(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args) {
+    const hipError_t e = allow_lds(kernel, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+    return hipGetLastError();
+}
 
 // Every request below (LDS bytes, the K1 route, the K1 template arguments) is rsp_geometry.h's.
 template <class T, int BMAX, int CP>
@@ -2724,57 +2670,43 @@ static hipError_t launch_k1_t(const Geometry& g, const DevConsts& k, const Frame
         static_assert(KC.CP == CP && KC.BMAX == BMAX, "CP / BMAX are k1_cfg's own values");
         constexpr int TPW = KC.TPW;
         const bool twice = rt.tpw == 2 * TPW;
-#define K1P_LAUNCH(LGP, TW)                                                                                      \
-    do {                                                                                                         \
-        hipError_t e = allow_lds(k1p_dbf_mtd<T, BMAX, CP, LGP, TW>, ldsp);                                       \
-        if (e != hipSuccess) return e;                                                                           \
-        hipLaunchKernelGGL((k1p_dbf_mtd<T, BMAX, CP, LGP, TW>), dim3(grid), dim3(K1_THREADS), ldsp, s, g, k, fp, nf); \
-        return hipGetLastError();                                                                                \
-    } while (0)
+        const auto go = [&](auto kernel) { return launch(kernel, dim3(grid), dim3(K1_THREADS), ldsp, s, g, k, fp, nf); };
         // the 2 TPW instantiations exist only where k1_route may choose them
         constexpr bool TWICE_OK = KC.twice_ok;
         if (twice && !TWICE_OK) return hipErrorInvalidValue;
         switch (g.logP) {
-            case 6: if constexpr (TWICE_OK) { if (twice) K1P_LAUNCH(6, 2 * TPW); } K1P_LAUNCH(6, TPW);
-            case 7: if constexpr (TWICE_OK) { if (twice) K1P_LAUNCH(7, 2 * TPW); } K1P_LAUNCH(7, TPW);
-            case 8: if constexpr (TWICE_OK) { if (twice) K1P_LAUNCH(8, 2 * TPW); } K1P_LAUNCH(8, TPW);
+            case 6:
+                if constexpr (TWICE_OK) { if (twice) return go(k1p_dbf_mtd<T, BMAX, CP, 6, 2 * TPW>); }
+                return go(k1p_dbf_mtd<T, BMAX, CP, 6, TPW>);
+            case 7:
+                if constexpr (TWICE_OK) { if (twice) return go(k1p_dbf_mtd<T, BMAX, CP, 7, 2 * TPW>); }
+                return go(k1p_dbf_mtd<T, BMAX, CP, 7, TPW>);
+            case 8:
+                if constexpr (TWICE_OK) { if (twice) return go(k1p_dbf_mtd<T, BMAX, CP, 8, 2 * TPW>); }
+                return go(k1p_dbf_mtd<T, BMAX, CP, 8, TPW>);
             default: return hipErrorInvalidValue;
         }
-#undef K1P_LAUNCH
     }
     if constexpr (CP <= 16) {
         constexpr int NJ = k1_cfg(CP, BMAX).NJ;
         if (rt.kernel == K1K_PERSISTENT_FACTORED) {
             const size_t ldsq = k1q_lds(g);
             const int grid = std::min(g.ncu, nf * g.ntiles);
-            hipError_t e;
-#define K1Q_LAUNCH(TW)                                                                                            \
-    do {                                                                                                          \
-        if ((e = allow_lds(k1q_dbf_mtd<T, BMAX, CP, TW>, ldsq)) != hipSuccess) return e;                           \
-        hipLaunchKernelGGL((k1q_dbf_mtd<T, BMAX, CP, TW>), dim3(grid), dim3(K1_THREADS), ldsq, s, g, k, fp, nf); \
-    } while (0)
+            const auto go = [&](auto kernel) { return launch(kernel, dim3(grid), dim3(K1_THREADS), ldsq, s, g, k, fp, nf); };
             switch (rt.tpw) {
-                case 1: K1Q_LAUNCH(1); break;
-                case 2: K1Q_LAUNCH(2); break;
-                case 3: K1Q_LAUNCH(3); break;
-                default: if constexpr (NJ <= 4) K1Q_LAUNCH(4); break;
+                case 1: return go(k1q_dbf_mtd<T, BMAX, CP, 1>);
+                case 2: return go(k1q_dbf_mtd<T, BMAX, CP, 2>);
+                case 3: return go(k1q_dbf_mtd<T, BMAX, CP, 3>);
+                default:
+                    if constexpr (NJ <= 4) return go(k1q_dbf_mtd<T, BMAX, CP, 4>);
+                    return hipGetLastError();   // no such instantiation: nothing launched
             }
-#undef K1Q_LAUNCH
-            return hipGetLastError();
         }
     }
     if (rt.kernel != K1K_TILED) return hipErrorInvalidValue;
     const bool rq = (mode & 2) && rt.transform == K1X_FACTORED;
-    const size_t lds = k1_tiled_lds(g, rq);
-    hipError_t e;
-    if (rq) {
-        if ((e = allow_lds(k1_dbf_mtd<T, BMAX, CP, true>, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL((k1_dbf_mtd<T, BMAX, CP, true>), dim3(g.ntiles, nf), dim3(K1_THREADS), lds, s, g, k, fp, mode);
-    } else {
-        if ((e = allow_lds(k1_dbf_mtd<T, BMAX, CP, false>, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL((k1_dbf_mtd<T, BMAX, CP, false>), dim3(g.ntiles, nf), dim3(K1_THREADS), lds, s, g, k, fp, mode);
-    }
-    return hipGetLastError();
+    return launch(rq ? k1_dbf_mtd<T, BMAX, CP, true> : k1_dbf_mtd<T, BMAX, CP, false>, dim3(g.ntiles, nf), dim3(K1_THREADS),
+                  k1_tiled_lds(g, rq), s, g, k, fp, mode);
 }
 
 template <class T, int BMAX>
@@ -2809,15 +2741,12 @@ static hipError_t launch_k2_p(const Geometry& g, const DevConsts& k, const Frame
     const bool w4 = g.k2_pts != RSP_K2_POINTS;
     const size_t lds = w4 ? (size_t)g.k2_pts * sizeof(cx<T>)
                           : (size_t)(k2_lds_data(g.k2_pts, k2_sh<T>()) + k2_tw_lds_max()) * sizeof(cx<T>);
-    hipError_t e = w4 ? allow_lds(k2_pc<T, 4>, lds) : allow_lds(k2_pc<T, 2>, lds);
-    if (e != hipSuccess) return e;
-    if (g.nwg_k2 > 0) {
-        if (w4)
-            hipLaunchKernelGGL((k2_pc<T, 4>), dim3(g.nwg_k2, nf), dim3(K2_THREADS), lds, s, g, k, fp, rows);
-        else
-            hipLaunchKernelGGL((k2_pc<T, 2>), dim3(g.nwg_k2, nf), dim3(K2_THREADS), lds, s, g, k, fp, rows);
+    const auto kernel = w4 ? k2_pc<T, 4> : k2_pc<T, 2>;
+    if (g.nwg_k2 == 0) {   // nothing to launch; the LDS attribute is set all the same
+        const hipError_t e = allow_lds(kernel, lds);
+        return e != hipSuccess ? e : hipGetLastError();
     }
-    return hipGetLastError();
+    return launch(kernel, dim3(g.nwg_k2, nf), dim3(K2_THREADS), lds, s, g, k, fp, rows);
 }
 
 // Streaming copy (rsp_hbm_copy_probe): CU16 x 16 B per lane, all loads in flight before the
@@ -2849,19 +2778,11 @@ template <class T>
 static hipError_t launch_k3_p(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, hipStream_t s) {
     const size_t lds = (size_t)g.cfar_rows * g.cfar_W * sizeof(T) + (K3_QCAP + 4) * sizeof(int);
     const dim3 grid(k3_ntiles(g) * g.cfar_nband * (g.B - 1) * nf);   // 1-D; k3_cfar remaps it XCD-aware
-    hipError_t e;
     const bool ref = k3_fast_params(g);   // the reference's cfar_params (v8:45-46); the plan sized the tile for it
-    if (ref && g.cfar_RT == 64) {
-        if ((e = allow_lds(k3_cfar<T, 5, 5, 10, 10, 64>, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL((k3_cfar<T, 5, 5, 10, 10, 64>), grid, dim3(RSP_THREADS), lds, s, g, k, fp);
-    } else if (ref && g.cfar_RT == 32) {
-        if ((e = allow_lds(k3_cfar<T, 5, 5, 10, 10, 32>, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL((k3_cfar<T, 5, 5, 10, 10, 32>), grid, dim3(RSP_THREADS), lds, s, g, k, fp);
-    } else {
-        if ((e = allow_lds(k3_cfar<T, 0, 0, 0, 0, 0>, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL((k3_cfar<T, 0, 0, 0, 0, 0>), grid, dim3(RSP_THREADS), lds, s, g, k, fp);
-    }
-    return hipGetLastError();
+    const auto kernel = ref && g.cfar_RT == 64   ? k3_cfar<T, 5, 5, 10, 10, 64>
+                        : ref && g.cfar_RT == 32 ? k3_cfar<T, 5, 5, 10, 10, 32>
+                                                 : k3_cfar<T, 0, 0, 0, 0, 0>;
+    return launch(kernel, grid, dim3(RSP_THREADS), lds, s, g, k, fp);
 }
 
 hipError_t launch_k3(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, hipStream_t s) {
@@ -2880,12 +2801,8 @@ hipError_t launch_k3(const Geometry& g, const DevConsts& k, const FramePtrs& fp,
 
 template <class T, int LGP>
 static hipError_t launch_mtd_t(const Geometry& g, const DevConsts& k, const void* pc, void* rdm, hipStream_t s) {
-    const size_t lds = mtd_cols_lds(g);
-    hipError_t e = allow_lds(k_mtd_cols<T, LGP>, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_mtd_cols<T, LGP>), dim3((g.G + 15) / 16, g.B), dim3(RSP_THREADS), lds, s, g, k,
-                       static_cast<const cx<T>*>(pc), static_cast<cx<T>*>(rdm));
-    return hipGetLastError();
+    return launch(k_mtd_cols<T, LGP>, dim3((g.G + 15) / 16, g.B), dim3(RSP_THREADS), mtd_cols_lds(g), s, g, k,
+                  static_cast<const cx<T>*>(pc), static_cast<cx<T>*>(rdm));
 }
 
 template <class T>

@@ -1,6 +1,7 @@
 """Per-kernel code hashes of librsp.so's gfx950 code objects (bench provenance).
 
 usage: kernel_hashes.py LIBRSP.so OUT.json
+       kernel_hashes.py LIB_OR_OBJECT --instantiations
 
 The HIP fat binary in the .so holds one clang offload bundle per device translation unit; its
 gfx950 entry is an AMDGPU ELF.  For every kernel symbol (STT_FUNC with a `.kd` descriptor) the
@@ -8,6 +9,10 @@ bytes of its code are hashed; kernels are keyed by their short name (the identif
 template arguments, as tools/pmc_traffic.py keys its counters), all instantiations of a name
 hashed together in mangled-name order.  bench.py compares these with the hashes a PMC traffic
 file recorded when it was measured: a kernel whose code changed since has no measured traffic.
+
+--instantiations prints one `hash mangled-name` line per kernel function instead, sorted by name,
+for a library or a single object file (build/rsp_kernels.hip.o): two builds whose lists are equal
+run the same machine code in every template instantiation.
 """
 import hashlib
 import json
@@ -70,15 +75,28 @@ def short_name(mangled):
             return name
 
 
-def main():
-    lib, out = sys.argv[1:3]
-    blob = open(lib, 'rb').read()
+def kernels(path):
+    """{mangled name: code bytes} of every kernel in the gfx950 code objects of a library or object."""
+    blob = open(path, 'rb').read()
     funcs = {}
     for _, elf in code_objects(blob):
         funcs.update(kernel_code(elf))
     kd = set()
     for _, elf in code_objects(blob):   # kernels = functions that have a kernel descriptor
         kd |= {n[:-3] for n in re.findall(rb'([_A-Za-z0-9]+\.kd)\0', elf) for n in [n.decode()]}
+    return funcs, kd
+
+
+def main():
+    if '--instantiations' in sys.argv[1:]:
+        path, = [a for a in sys.argv[1:] if a != '--instantiations']
+        funcs, kd = kernels(path)
+        for nm in sorted(funcs):
+            if nm in kd:
+                print(hashlib.sha256(funcs[nm]).hexdigest()[:16], nm)
+        return
+    lib, out = sys.argv[1:3]
+    funcs, kd = kernels(lib)
     groups = {}
     for nm in sorted(funcs):
         if nm in kd:
