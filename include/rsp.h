@@ -551,6 +551,58 @@ int32_t rsp_music_device_alloc(rsp_music_plan* plan, int64_t bytes, void** d_ptr
 int32_t rsp_music_device_free(rsp_music_plan* plan, void* d_ptr);
 int32_t rsp_music_device_download(rsp_music_plan* plan, void* h_dst, const void* d_src, int64_t bytes);
 
+/* ---- 2-D MUSIC for a uniform rectangular array (MUSIC_2D.m) ----
+ * MUSIC_2D.m:52-138 per instance X [N x K], N = nx*ny elements, element (ix, iy) is channel
+ * iy + ny*ix (meshgrid(0:Nx-1, 0:Ny-1) flattened by (:), MUSIC_2D.m:17-19):
+ *   R = X*X'/K, eig, sort 'descend', Q_n (:52-57);
+ *   a(phi, theta) = exp(1j*2*pi*(dx/lambda*ix*cos(theta)*cos(phi) + dy/lambda*iy*cos(theta)*sin(phi)))
+ *   (:35,87-89); P = 1./sum(abs(Q_n'*S1).^2) over the n_theta x n_phi grid (:92-93);
+ *   P_dB = 10*log10(P/max(P(:))) (:96-98); imregionalmax (8-connected), the M largest (:119-124).
+ * rsp_music_create_2d returns the same plan type as rsp_music_create, and rsp_music_process,
+ * rsp_music_process_device, rsp_music_fast_count, rsp_music_device_alloc / _free / _download and
+ * rsp_music_destroy take it with N = nx*ny and n_scan = n_theta*n_phi.  In rsp_music_out:
+ *   spectrum_db [n_theta x n_phi x I], column-major with theta fastest (P_MUSIC_dB);
+ *   peak_idx    [M x I] 1-based linear indices r + n_theta*(c - 1) (sub2ind, :123), 0 = none;
+ *   n_peaks     [I] pixels of the imregionalmax mask (length(peak_vals), :123);
+ *   eigenvalues, covariance as for a line-array plan.
+ * A peaks-only call (M <= 4) may keep the block-power signal subspace (rsp_music_fast_count); a
+ * call that reads spectrum_db or eigenvalues runs the full eigensolver.  Complex double only.
+ * Device memory: the spectrum buffer is max_batch * n_theta*n_phi * 8 bytes (132 KB per instance
+ * at MUSIC_2D.m's 91 x 181 grid), next to max_batch * 64 KB of covariance.
+ * rsp_music_synthesize_device, rsp_music_profile and rsp_music_profile_ex refuse a 2-D plan, and
+ * the _2d calls below refuse a line-array plan (RSP_ERR_INVALID).
+ * Tolerances vs the complex128 restatement: tests/test_music2d.py. */
+typedef struct rsp_music2d_config {
+    int32_t nx, ny;            /* URA elements along x and y (MUSIC_2D.m:10-12); N = nx*ny in 2..64 */
+    int32_t num_snapshots;     /* K (MUSIC_2D.m:30)                                             */
+    int32_t num_sources;       /* M, 1..min(8, N-1)                                             */
+    int32_t n_phi, n_theta;    /* each 3..1024, n_phi*n_theta <= 65536 (MUSIC_2D.m:61-62: 181, 91) */
+    double dx_over_lambda, dy_over_lambda;   /* MUSIC_2D.m:13-14: 0.5, 0.5                      */
+    const double* phi_rad;     /* azimuth grid, n_phi entries (borrowed for create)             */
+    const double* theta_rad;   /* elevation grid, n_theta entries                               */
+    int32_t max_batch;         /* instances per call (device buffers sized for it)              */
+    int32_t precision;         /* RSP_C128 (RSP_C64: RSP_ERR_UNSUPPORTED)                        */
+} rsp_music2d_config;
+
+/* rsp_music_scene plus the elevations (MUSIC_2D.m:24-25,46-48: complex_sources = 1,
+ * snr_measured = 1); the Philox streams are those of the line array (noise index c + N*k with
+ * c = iy + ny*ix). */
+typedef struct rsp_music2d_scene {
+    int32_t n_src, complex_sources, snr_measured, reserved;
+    double snr_db;
+    double azim_rad[8];        /* phi   (MUSIC_2D.m:24) */
+    double elev_rad[8];        /* theta (MUSIC_2D.m:25) */
+    double amplitudes[8];
+} rsp_music2d_scene;
+
+int32_t rsp_music_create_2d(const rsp_music2d_config* cfg, int32_t device, rsp_music_plan** out);
+int32_t rsp_music_synthesize_device_2d(rsp_music_plan* plan, const rsp_music2d_scene* scene, int32_t n_inst,
+                                       int32_t inst0, uint64_t seed, void* d_X);
+/* HIP-event timing of the four device stages, averaged over `iters` launches: ms_out[0]
+ * covariance, [1] signal subspace, [2] scan, [3] dB + peaks; `what` as rsp_music_profile_ex. */
+int32_t rsp_music_profile_2d(rsp_music_plan* plan, const void* d_X, int32_t n_inst, int32_t iters, int32_t what,
+                             float* ms_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,10 @@
 //
 // Batching: one workgroup per instance (k_music_eig: one wave per instance); BASELINE config
 // #5 runs >= 1024 instances per launch so that the 256 CUs are full.
+//
+// Planar arrays (MUSIC_2D.m, rsp_music_create_2d; complex double): the same covariance, then
+// k_music_sub64 (signal subspace), k_music_scan2d (the theta x phi scan) and k_music_peaks2d
+// (P_dB, imregionalmax, the M largest) -- see the section before the host code.
 #include "rsp.h"
 #include "rsp_internal.h"
 
@@ -1035,12 +1039,14 @@ __device__ bool me_fast_subspace(const double2 (&a)[16], int n, int t, int lane,
 
 // FAST (peaks-only launches, neig <= 4): try me_fast_subspace first.  A separate instantiation, so
 // that the launches that read every eigenvalue run the full path without the fast path's registers.
-template <int M, bool FAST>
-__global__ __launch_bounds__(ME_THREADS, ME_WPS) void k_music_eig64(int N, int S, int neig, double spec_tol,
-                                                          const double2* __restrict__ R,
-                                                          const double2* __restrict__ S1T, int Spad,
-                                                          double* __restrict__ spec_db, double* __restrict__ eig_out,
-                                                          int* __restrict__ peaks_out, unsigned long long* __restrict__ trace) {
+// SUB (k_music_sub64, the planar-array path): phases 0-3 only.  The workgroup stops once Q_s is
+// complete and writes it ([M][64] per instance) to qs_out, with the fast-path flag where
+// rsp_music_fast_count reads it; no den[S] is carved out of LDS (S = 0) and S1T, spec_db are unused.
+template <int M, bool FAST, bool SUB>
+__device__ __forceinline__ void me_eig_body(int N, int S, int neig, double spec_tol, const double2* R,
+                                            const double2* S1T, int Spad, double* spec_db, double* eig_out,
+                                            int* peaks_out, unsigned long long* trace, double2* qs_out) {
+    // (no __restrict__ here: the two kernels' parameters carry it)
     // trace (diagnostic builds, RSP_MUSIC_TRACE=1): s_memrealtime at the phase boundaries
 #define ME_STAMP(ix) \
     if (trace && threadIdx.x == 0) trace[(size_t)blockIdx.x * 8 + (ix)] = wall_clock64()
@@ -1116,7 +1122,7 @@ __global__ __launch_bounds__(ME_THREADS, ME_WPS) void k_music_eig64(int N, int S
     };
     double pmax = 0.0;
     bool have_den = false;
-    if constexpr (FAST) {
+    if constexpr (FAST && !SUB) {
         // A call that reads the spectrum (spec_tol > 0) keeps the fast subspace only if it also
         // bounds the spectrum: sin(angle) <= 1e-12 to the signal eigenvectors moves the projector
         // by <= 1e-12, so each den(s) by <= e0 = 1e-12 |a(s)|^2 = 1e-12 n (unit-modulus steering),
@@ -1475,6 +1481,12 @@ __global__ __launch_bounds__(ME_THREADS, ME_WPS) void k_music_eig64(int N, int S
     }
     }   // !fast
     ME_STAMP(4);
+    if constexpr (SUB) {   // Q_s (rows >= n are zero on both paths) and the path taken; the scan is k_music_scan2d's
+        double2* __restrict__ qo = qs_out + (size_t)blockIdx.x * M * 64;
+        for (int e = t; e < M * 64; e += ME_THREADS) qo[e] = Qs[e];
+        if (t == 0 && M < MU_MMAX) peaks_out[(size_t)blockIdx.x * (MU_MMAX + 1) + MU_MMAX] = fast ? 1 : 0;
+        return;
+    }
     if (!have_den) pmax = den_pmax();
     ME_STAMP(5);
     // ---- 5. P = 1 ./ den, P_dB = 10 log10(P / max P) (MUSIC_1D.m:37-41)
@@ -1545,6 +1557,239 @@ __global__ __launch_bounds__(ME_THREADS, ME_WPS) void k_music_eig64(int N, int S
 #undef ME_STAMP
 }
 
+template <int M, bool FAST>
+__global__ __launch_bounds__(ME_THREADS, ME_WPS) void k_music_eig64(int N, int S, int neig, double spec_tol,
+                                                          const double2* __restrict__ R,
+                                                          const double2* __restrict__ S1T, int Spad,
+                                                          double* __restrict__ spec_db, double* __restrict__ eig_out,
+                                                          int* __restrict__ peaks_out, unsigned long long* __restrict__ trace) {
+    me_eig_body<M, FAST, false>(N, S, neig, spec_tol, R, S1T, Spad, spec_db, eig_out, peaks_out, trace, nullptr);
+}
+
+// =======================================================================================
+// Planar (uniform rectangular) arrays, MUSIC_2D.m:50-138 in complex double.  The covariance is
+// k_music_cov64's; the rest is three kernels, because the (theta, phi) scan (up to 65536 points)
+// does not fit the eigensolver's LDS and is the larger part of the work:
+//   k_music_sub64    Q_s [M][64] per instance: k_music_eig64's phases 0-3 (MUSIC_2D.m:53-57)
+//   k_music_scan2d   den(theta, phi) = |a - Q_s (Q_s^H a)|^2 = sum |Q_n^H a|^2 (MUSIC_2D.m:87-92)
+//   k_music_peaks2d  P_dB (MUSIC_2D.m:96-98), imregionalmax + the M largest (MUSIC_2D.m:119-124)
+// =======================================================================================
+template <int M, bool FAST>
+__global__ __launch_bounds__(ME_THREADS, ME_WPS) void k_music_sub64(int N, int neig, const double2* __restrict__ R,
+                                                          double2* __restrict__ qs_out, double* __restrict__ eig_out,
+                                                          int* __restrict__ peaks_out, unsigned long long* __restrict__ trace) {
+    me_eig_body<M, FAST, true>(N, 0, neig, 0.0, R, nullptr, 0, nullptr, eig_out, peaks_out, trace, qs_out);
+}
+
+// The scan: one lane per grid point, M2_IB instances per workgroup over the same steering vector.
+// The array is separable (element c = iy + ny ix, MUSIC_2D.m:17-19): a[c] = ex^ix ey^iy with
+// ex = exp(1j 2 pi dx/lambda cos(theta) cos(phi)), ey = exp(1j 2 pi dy/lambda cos(theta) sin(phi))
+// from the plan's table, so a lane builds its steering vector by repeated multiplication (one
+// complex product per element, shared by the M2_IB instances) instead of reading a [64][S] table.
+// Residual form as k_music_eig64's den_pmax: the M projection coefficients first, then the squared
+// norm of a - Q_s cf (the steering vector is rebuilt, identically, for the second pass).  Q_s of
+// the workgroup's instances sits in LDS and is read as a broadcast.  A point's value depends only
+// on its (ex, ey) and the instance: every lane runs the same sequence of operations.
+#define M2_THREADS 256
+#define M2_IB 4
+template <int M>
+__global__ __launch_bounds__(M2_THREADS) void k_music_scan2d(int nx, int ny, int S, int n_inst,
+                                                           const double2* __restrict__ exy,
+                                                           const double2* __restrict__ Qs, double* __restrict__ den) {
+    __shared__ double2 ql[M2_IB][M][MU_NMAX];
+    const int t = threadIdx.x;
+    const int i0 = blockIdx.x * M2_IB;
+    const double2 z2 = make_double2(0.0, 0.0);
+    for (int e = t; e < M2_IB * M * MU_NMAX; e += M2_THREADS) {   // a group past n_inst repeats the last instance
+        const int b = e / (M * MU_NMAX), r = e - b * (M * MU_NMAX);
+        (&ql[0][0][0])[e] = Qs[(size_t)min(i0 + b, n_inst - 1) * (M * MU_NMAX) + r];
+    }
+    __syncthreads();
+    const int g = blockIdx.y * M2_THREADS + t;
+    const int gc = min(g, S - 1);   // lanes past the grid repeat its last point and store nothing
+    const double2 ex = exy[2 * gc], ey = exy[2 * gc + 1];
+    double2 cf[M2_IB][M];
+#pragma unroll
+    for (int b = 0; b < M2_IB; ++b)
+#pragma unroll
+        for (int m = 0; m < M; ++m) cf[b][m] = z2;
+    {
+        double2 px = make_double2(1.0, 0.0);
+        int c = 0;
+        for (int ix = 0; ix < nx; ++ix) {
+            double2 a = px;
+            for (int iy = 0; iy < ny; ++iy, ++c) {
+#pragma unroll
+                for (int b = 0; b < M2_IB; ++b)
+#pragma unroll
+                    for (int m = 0; m < M; ++m) cf[b][m] = zadd(cf[b][m], zmc(ql[b][m][c], a));
+                a = zm(a, ey);
+            }
+            px = zm(px, ex);
+        }
+    }
+    double r2[M2_IB];
+#pragma unroll
+    for (int b = 0; b < M2_IB; ++b) r2[b] = 0.0;
+    {
+        double2 px = make_double2(1.0, 0.0);
+        int c = 0;
+        for (int ix = 0; ix < nx; ++ix) {
+            double2 a = px;
+            for (int iy = 0; iy < ny; ++iy, ++c) {
+#pragma unroll
+                for (int b = 0; b < M2_IB; ++b) {
+                    double2 rr = a;
+#pragma unroll
+                    for (int m = 0; m < M; ++m) rr = zsub(rr, zm(ql[b][m][c], cf[b][m]));
+                    r2[b] += rr.x * rr.x + rr.y * rr.y;
+                }
+                a = zm(a, ey);
+            }
+            px = zm(px, ex);
+        }
+    }
+    if (g < S)
+#pragma unroll
+        for (int b = 0; b < M2_IB; ++b)
+            if (i0 + b < n_inst) den[(size_t)(i0 + b) * S + g] = r2[b];
+}
+
+// P_dB and the peaks of one instance's map (one workgroup; the map, <= 512 KB, stays in L2):
+// spec holds den [n_theta x n_phi], theta fastest (MATLAB's P_MUSIC, MUSIC_2D.m:93), and is
+// rewritten with P_dB = 10 log10((1 / den) / max(1 / den)) (:96-98, the expression of
+// k_music_eig64).  imregionalmax, 8-connected (:119), exactly, on those values: a pixel is in the
+// mask iff no pixel of its plateau (the 8-connected set of equal values around it) has a larger
+// in-bounds neighbour.  Candidates = pixels with no larger neighbour; a candidate touching an
+// equal non-candidate is dropped, pass after pass (two bit masks, read one and write the other)
+// until a pass drops nothing -- one pass (over no pixel at all) when there are no ties; at most
+// S passes.  In those passes and the selection lane t owns the 32-pixel mask words t, t + 256, ...
+// Then n_peaks = the mask's pixel count and the M largest
+// by value, ties to the lower linear index (find order + stable sort, :120-124), as 1-based
+// linear indices r + n_theta (c - 1) (sub2ind, :123).
+#define M2_SMAX 65536
+__global__ __launch_bounds__(M2_THREADS) void k_music_peaks2d(int nt, int np, int M, double* spec,
+                                                            int* __restrict__ peaks_out) {
+    __shared__ unsigned mk[2][M2_SMAX / 32];
+    __shared__ unsigned tie[M2_SMAX / 32];
+    __shared__ double dred[4];
+    __shared__ int ired[4];
+    __shared__ int cnt;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int S = nt * np, nw = (S + 31) >> 5;
+    double* sp = spec + (size_t)blockIdx.x * S;
+    double pm = 0.0;
+    for (int s = t; s < S; s += M2_THREADS) pm = fmax(pm, 1.0 / sp[s]);
+    pm = wmaxd(pm);
+    if (lane == 0) dred[w] = pm;
+    if (t == 0) cnt = 0;
+    __syncthreads();
+    const double pmax = fmax(fmax(dred[0], dred[1]), fmax(dred[2], dred[3]));
+    for (int s = t; s < S; s += M2_THREADS) sp[s] = 10.0 * log10((1.0 / sp[s]) / pmax);
+    __syncthreads();   // the map is complete (and dred free) before any lane reads a neighbour
+    // candidates, one lane per pixel (a wave reads 64 consecutive pixels of a column and their 8
+    // neighbours: coalesced, no branch -- an out-of-bounds neighbour re-reads the pixel itself and
+    // is masked out); the wave's ballot is two mask words.  tie: candidates with an equal
+    // neighbour, the only ones the passes below can drop.
+    for (int base = 0; base < S; base += M2_THREADS) {   // uniform trip count
+        const int p = base + t, pc = min(p, S - 1);
+        const int c = pc / nt, r = pc - c * nt;
+        const double v = sp[pc];
+        bool larger = false, equal = false;
+#pragma unroll
+        for (int dc = -1; dc <= 1; ++dc)
+#pragma unroll
+            for (int dr = -1; dr <= 1; ++dr)
+                if ((dr | dc) != 0) {
+                    const int rr = r + dr, cc = c + dc;
+                    const bool inb = rr >= 0 && rr < nt && cc >= 0 && cc < np;
+                    const double u = sp[inb ? rr + nt * cc : pc];
+                    larger |= inb && u > v;
+                    equal |= inb && u == v;
+                }
+        const bool cand = p < S && !larger;
+        const unsigned long long cb = __builtin_amdgcn_ballot_w64(cand);
+        const unsigned long long tb = __builtin_amdgcn_ballot_w64(cand && equal);
+        if (lane == 0) {   // pixels base + 64 w .. + 63: words <= 2047 (bits past S are zero)
+            const int wd = (base + 64 * w) >> 5;
+            mk[0][wd] = (unsigned)cb;
+            mk[0][wd + 1] = (unsigned)(cb >> 32);
+            tie[wd] = (unsigned)tb;
+            tie[wd + 1] = (unsigned)(tb >> 32);
+        }
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int it = 0; it < S; ++it) {
+        const unsigned* mc = mk[cur];
+        int changed = 0;
+        for (int wd = t; wd < nw; wd += M2_THREADS) {
+            const unsigned bits = mc[wd];
+            unsigned keep = bits;
+            for (unsigned rem = bits & tie[wd]; rem; rem &= rem - 1) {
+                const int b = __builtin_ctz(rem), p = (wd << 5) + b;
+                const int c = p / nt, r = p - c * nt;
+                const double v = sp[p];
+                bool drop = false;   // an equal-valued in-bounds neighbour that is not a candidate
+                for (int dc = -1; dc <= 1; ++dc)
+                    for (int dr = -1; dr <= 1; ++dr) {
+                        const int rr = r + dr, cc = c + dc;
+                        if ((dr | dc) != 0 && rr >= 0 && rr < nt && cc >= 0 && cc < np) {
+                            const int q = rr + nt * cc;
+                            drop = drop || (sp[q] == v && !(mc[q >> 5] >> (q & 31) & 1u));
+                        }
+                    }
+                if (drop) keep &= ~(1u << b);
+            }
+            mk[cur ^ 1][wd] = keep;
+            changed |= keep != bits;
+        }
+        cur ^= 1;
+        if (!__syncthreads_or(changed)) break;
+    }
+    unsigned* mf = mk[cur];
+    int npk = 0;
+    for (int wd = t; wd < nw; wd += M2_THREADS) npk += __popc(mf[wd]);
+    if (npk) atomicAdd(&cnt, npk);
+    __syncthreads();
+    int* po = peaks_out + (size_t)blockIdx.x * (MU_MMAX + 1);
+    if (t == 0) po[0] = cnt;
+    for (int rk = 0; rk < M; ++rk) {
+        double bv = -1.0e300;
+        int bs = 1 << 30;
+        for (int wd = t; wd < nw; wd += M2_THREADS)
+            for (unsigned rem = mf[wd]; rem; rem &= rem - 1) {
+                const int p = (wd << 5) + __builtin_ctz(rem);
+                const double v = sp[p];
+                if (v > bv) { bv = v; bs = p; }   // p ascending within a lane: ties keep the lower index
+            }
+        const double gv = wmaxd(bv);
+        int cand = bv == gv ? bs : (1 << 30);
+        cand = min(cand, dppi<0xB1>(cand));
+        cand = min(cand, dppi<0x4E>(cand));
+        cand = min(cand, dppi<0x141>(cand));
+        cand = min(cand, dppi<0x140>(cand));
+        cand = min(min(__builtin_amdgcn_readlane(cand, 0), __builtin_amdgcn_readlane(cand, 16)),
+                   min(__builtin_amdgcn_readlane(cand, 32), __builtin_amdgcn_readlane(cand, 48)));
+        if (lane == 0) {
+            dred[w] = gv;
+            ired[w] = cand;
+        }
+        __syncthreads();
+        double best = dred[0];
+        for (int ww = 1; ww < 4; ++ww) best = fmax(best, dred[ww]);
+        int gs = 1 << 30;
+        for (int ww = 0; ww < 4; ++ww)
+            if (dred[ww] == best) gs = min(gs, ired[ww]);
+        if (gs < (1 << 30) && ((gs >> 5) % M2_THREADS) == t) mf[gs >> 5] &= ~(1u << (gs & 31));
+        if (t == 0) po[1 + rk] = gs < (1 << 30) ? gs + 1 : 0;
+        __syncthreads();
+    }
+    // (slot MU_MMAX past the M < 8 peaks is k_music_sub64's fast-path flag)
+    if (t == 0)
+        for (int rk = M; rk < MU_MMAX - 1; ++rk) po[1 + rk] = 0;
+}
+
 }  // namespace
 
 // =======================================================================================
@@ -1566,8 +1811,14 @@ struct rsp_music_plan {
     double2* d_src = nullptr;     // synthesis: source steering [MU_MMAX][N]
     double* d_amp = nullptr;      // [MU_MMAX]
     unsigned long long* d_trace = nullptr;   // RSP_MUSIC_TRACE: [max_batch][8] phase stamps (f32 eig)
-    hipEvent_t ev[4] = {};
+    hipEvent_t ev[5] = {};
     int last_inst = 0;            // instances of the last eig launch (rsp_music_fast_count)
+    // planar-array plans (rsp_music_create_2d): N = nx ny, S = n_theta n_phi, no S1T
+    bool planar = false;
+    int nx = 0, ny = 0, n_theta = 0, n_phi = 0;
+    double dxl = 0.0, dyl = 0.0;
+    double2* d_exy = nullptr;     // [S][2]: (ex, ey) of grid point r + n_theta c (k_music_scan2d)
+    double2* d_qs = nullptr;      // [max_batch][M][64] signal subspace (k_music_sub64)
 };
 
 namespace {
@@ -1661,6 +1912,57 @@ int music_run(rsp_music_plan* p, const void* dX, int n_inst, bool timed, float* 
     return RSP_OK;
 }
 
+// The planar-array path (MUSIC_2D.m:52-124): covariance, signal subspace, scan, dB + peaks.  A
+// peaks-only call (M <= 4) may keep the block-power subspace; a call that reads the spectrum or
+// the eigenvalues runs the full eigensolver (the fast path's 1e-12 subspace bound is turned into
+// a P_dB bound from den_min inside k_music_eig64 only, and the 2-D scan does not live there).
+template <int MC>
+hipError_t launch_planar(rsp_music_plan* p, int n_inst, int want, bool timed) {
+    const int neig = want == MU_WANT_EIGS ? p->N : p->M;
+    const size_t lds = me_lds_bytes(MC, 0);
+    hipError_t e;
+    if (want == MU_WANT_PEAKS && MC <= 4)
+        hipLaunchKernelGGL((k_music_sub64<MC, true>), dim3(n_inst), dim3(ME_THREADS), lds, p->stream, p->N, neig,
+                           (const double2*)p->d_R, p->d_qs, (double*)p->d_eig, p->d_peaks, p->d_trace);
+    else
+        hipLaunchKernelGGL((k_music_sub64<MC, false>), dim3(n_inst), dim3(ME_THREADS), lds, p->stream, p->N, neig,
+                           (const double2*)p->d_R, p->d_qs, (double*)p->d_eig, p->d_peaks, p->d_trace);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (timed && (e = hipEventRecord(p->ev[2], p->stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_music_scan2d<MC>, dim3((n_inst + M2_IB - 1) / M2_IB, (p->S + M2_THREADS - 1) / M2_THREADS),
+                       dim3(M2_THREADS), 0, p->stream, p->nx, p->ny, p->S, n_inst, (const double2*)p->d_exy,
+                       (const double2*)p->d_qs, (double*)p->d_spec);
+    return hipGetLastError();
+}
+
+int music_run_planar(rsp_music_plan* p, const void* dX, int n_inst, bool timed, float* ms, int want) {
+    if (n_inst < 1 || n_inst > p->max_batch)
+        return rsp_set_error(RSP_ERR_INVALID, "n_inst %d outside 1..max_batch %d", n_inst, p->max_batch);
+    MUCHK(hipSetDevice(p->device));
+    if (timed) MUCHK(hipEventRecord(p->ev[0], p->stream));
+    hipLaunchKernelGGL(k_music_cov64, dim3(n_inst), dim3(MU_THREADS), 0, p->stream, p->N, p->K, (const double2*)dX,
+                       (double2*)p->d_R);
+    MUCHK(hipGetLastError());
+    if (timed) MUCHK(hipEventRecord(p->ev[1], p->stream));
+    p->last_inst = n_inst;
+    switch (p->M) {
+#define MU_PLANAR(MC) \
+    case MC: MUCHK(launch_planar<MC>(p, n_inst, want, timed)); break;
+        MU_PLANAR(1) MU_PLANAR(2) MU_PLANAR(3) MU_PLANAR(4) MU_PLANAR(5) MU_PLANAR(6) MU_PLANAR(7) MU_PLANAR(8)
+#undef MU_PLANAR
+    }
+    if (timed) MUCHK(hipEventRecord(p->ev[3], p->stream));
+    hipLaunchKernelGGL(k_music_peaks2d, dim3(n_inst), dim3(M2_THREADS), 0, p->stream, p->n_theta, p->n_phi, p->M,
+                       (double*)p->d_spec, p->d_peaks);
+    MUCHK(hipGetLastError());
+    if (timed) {
+        MUCHK(hipEventRecord(p->ev[4], p->stream));
+        MUCHK(hipEventSynchronize(p->ev[4]));
+        for (int q = 0; q < 4; ++q) MUCHK(hipEventElapsedTime(&ms[q], p->ev[q], p->ev[q + 1]));
+    }
+    return RSP_OK;
+}
+
 // device results -> caller (double; a complex-single plan's are widened)
 int music_fetch(rsp_music_plan* p, int n_inst, rsp_music_out* out) {
     if (!out) return RSP_OK;
@@ -1721,9 +2023,146 @@ int music_fetch(rsp_music_plan* p, int n_inst, rsp_music_out* out) {
     return RSP_OK;
 }
 
+// k_music_synth over the source steering table src [n_src][N] (the line array's or the planar one's)
+template <class SC>
+int music_synth(rsp_music_plan* p, const SC* sc, const std::vector<double2>& src, int n_inst, int inst0, uint64_t seed,
+                void* d_X) {
+    const int N = p->N, Ms = sc->n_src;
+    double amp[MU_MMAX];
+    for (int m = 0; m < MU_MMAX; ++m) amp[m] = m < Ms ? sc->amplitudes[m] : 0.0;
+    MUCHK(hipMemcpyAsync(p->d_src, src.data(), src.size() * sizeof(double2), hipMemcpyHostToDevice, p->stream));
+    MUCHK(hipMemcpyAsync(p->d_amp, amp, sizeof amp, hipMemcpyHostToDevice, p->stream));
+    const double nsc_fixed = std::sqrt(1.0 / std::pow(10.0, sc->snr_db / 10.0) / 2.0);
+    if (p->f64)
+        hipLaunchKernelGGL(k_music_synth<double2>, dim3(n_inst), dim3(MU_THREADS), 0, p->stream, N, p->K, Ms, inst0,
+                           seed, p->d_src, p->d_amp, sc->complex_sources, sc->snr_measured ? 1 : 0, sc->snr_db,
+                           nsc_fixed, (double2*)d_X);
+    else
+        hipLaunchKernelGGL(k_music_synth<float2>, dim3(n_inst), dim3(MU_THREADS), 0, p->stream, N, p->K, Ms, inst0,
+                           seed, p->d_src, p->d_amp, sc->complex_sources, sc->snr_measured ? 1 : 0, sc->snr_db,
+                           nsc_fixed, (float2*)d_X);
+    MUCHK(hipGetLastError());
+    MUCHK(hipStreamSynchronize(p->stream));   // the host staging above is stack memory
+    return RSP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int32_t rsp_music_create_2d(const rsp_music2d_config* cfg, int32_t device, rsp_music_plan** out) {
+    if (!cfg || !out || !cfg->phi_rad || !cfg->theta_rad) return rsp_set_error(RSP_ERR_INVALID, "null argument");
+    *out = nullptr;
+    const int nx = cfg->nx, ny = cfg->ny, K = cfg->num_snapshots, M = cfg->num_sources;
+    const int np = cfg->n_phi, nt = cfg->n_theta;
+    if (nx < 1 || ny < 1 || nx > MU_NMAX || ny > MU_NMAX || nx * ny < 2 || nx * ny > MU_NMAX)
+        return rsp_set_error(RSP_ERR_UNSUPPORTED, "nx*ny = %d*%d outside 2..%d", nx, ny, MU_NMAX);
+    const int N = nx * ny;
+    if (M < 1 || M >= N || M > MU_MMAX)
+        return rsp_set_error(RSP_ERR_UNSUPPORTED, "num_sources %d outside 1..min(%d, nx*ny-1)", M, MU_MMAX);
+    if (np < 3 || np > 1024 || nt < 3 || nt > 1024 || np * nt > M2_SMAX)
+        return rsp_set_error(RSP_ERR_UNSUPPORTED, "grid n_phi %d x n_theta %d: each 3..1024, at most %d points", np, nt,
+                             M2_SMAX);
+    if (cfg->precision == RSP_C64)
+        return rsp_set_error(RSP_ERR_UNSUPPORTED, "2-D MUSIC is complex double only (precision RSP_C128)");
+    if (cfg->precision != RSP_C128)
+        return rsp_set_error(RSP_ERR_INVALID, "precision must be RSP_C128, got %d", cfg->precision);
+    if (K < 1) return rsp_set_error(RSP_ERR_INVALID, "num_snapshots %d < 1", K);
+    if (cfg->max_batch < 1) return rsp_set_error(RSP_ERR_INVALID, "max_batch %d < 1", cfg->max_batch);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+        return rsp_set_error(RSP_ERR_DEVICE, "HIP device %d not available (%d devices)", device, ndev);
+    rsp_music_plan* p = new rsp_music_plan();
+    p->device = device;
+    p->planar = true;
+    p->nx = nx; p->ny = ny; p->n_phi = np; p->n_theta = nt;
+    p->N = N; p->K = K; p->M = M; p->S = nt * np; p->Spad = 0;
+    p->max_batch = cfg->max_batch;
+    p->dxl = cfg->dx_over_lambda;
+    p->dyl = cfg->dy_over_lambda;
+    auto bail = [&](int rc) { rsp_music_destroy(p); return rc; };
+    if (hipSetDevice(device) != hipSuccess) return bail(rsp_set_error(RSP_ERR_DEVICE, "hipSetDevice(%d)", device));
+    if (hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess)
+        return bail(rsp_set_error(RSP_ERR_DEVICE, "hipStreamCreate failed"));
+    for (auto& e : p->ev)
+        if (hipEventCreate(&e) != hipSuccess) return bail(rsp_set_error(RSP_ERR_DEVICE, "hipEventCreate failed"));
+    const size_t B = (size_t)p->max_batch;
+    struct { void** ptr; size_t bytes; } allocs[] = {
+        {(void**)&p->d_exy, (size_t)p->S * 2 * sizeof(double2)},
+        {(void**)&p->d_qs, B * M * MU_NMAX * sizeof(double2)},
+        {&p->d_R, B * MU_NMAX * MU_NMAX * sizeof(double2)},
+        {&p->d_spec, B * p->S * sizeof(double)},
+        {&p->d_eig, B * N * sizeof(double)},
+        {(void**)&p->d_peaks, B * (MU_MMAX + 1) * sizeof(int)},
+        {(void**)&p->d_src, (size_t)MU_MMAX * MU_NMAX * sizeof(double2)},
+        {(void**)&p->d_amp, (size_t)MU_MMAX * sizeof(double)},
+    };
+    for (auto& a : allocs)
+        if (hipMalloc(a.ptr, a.bytes) != hipSuccess)
+            return bail(rsp_set_error(RSP_ERR_NOMEM, "hipMalloc(%zu bytes) failed", a.bytes));
+    // per grid point r + n_theta c (theta fastest: Theta_vec, Phi_vec of MUSIC_2D.m:82-84) the two
+    // unit steps of the separable steering vector (MUSIC_2D.m:87-89)
+    std::vector<double2> exy((size_t)p->S * 2);
+    for (int c = 0; c < np; ++c)
+        for (int r = 0; r < nt; ++r) {
+            const double ct = std::cos(cfg->theta_rad[r]);
+            const double ax = 2.0 * M_PI * p->dxl * (ct * std::cos(cfg->phi_rad[c]));
+            const double ay = 2.0 * M_PI * p->dyl * (ct * std::sin(cfg->phi_rad[c]));
+            const size_t g = (size_t)r + (size_t)nt * c;
+            exy[2 * g] = make_double2(std::cos(ax), std::sin(ax));
+            exy[2 * g + 1] = make_double2(std::cos(ay), std::sin(ay));
+        }
+    if (hipMemcpy(p->d_exy, exy.data(), exy.size() * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess)
+        return bail(rsp_set_error(RSP_ERR_DEVICE, "steering upload failed"));
+#ifdef RSP_DEBUG_KNOBS
+    const char* tr = getenv("RSP_MUSIC_TRACE");
+    if (tr && atoi(tr) && hipMalloc(&p->d_trace, B * 8 * sizeof(unsigned long long)) != hipSuccess)
+        return bail(rsp_set_error(RSP_ERR_NOMEM, "trace buffer"));
+#endif
+    *out = p;
+    return RSP_OK;
+}
+
+int32_t rsp_music_synthesize_device_2d(rsp_music_plan* p, const rsp_music2d_scene* sc, int32_t n_inst, int32_t inst0,
+                                       uint64_t seed, void* d_X) {
+    if (!p || !sc || !d_X) return rsp_set_error(RSP_ERR_INVALID, "null argument");
+    if (!p->planar) return rsp_set_error(RSP_ERR_INVALID, "rsp_music_synthesize_device_2d on a line-array plan");
+    if (sc->n_src < 1 || sc->n_src > MU_MMAX)
+        return rsp_set_error(RSP_ERR_UNSUPPORTED, "n_src %d outside 1..%d", sc->n_src, MU_MMAX);
+    if (n_inst < 1) return rsp_set_error(RSP_ERR_INVALID, "n_inst %d < 1", n_inst);
+    MUCHK(hipSetDevice(p->device));
+    const int N = p->N, Ms = sc->n_src;
+    std::vector<double2> src((size_t)Ms * N);
+    for (int m = 0; m < Ms; ++m) {   // S(:, m), element iy + ny ix (MUSIC_2D.m:17-19,41-42)
+        const double ct = std::cos(sc->elev_rad[m]);
+        const double A = ct * std::cos(sc->azim_rad[m]), Bq = ct * std::sin(sc->azim_rad[m]);
+        for (int ix = 0; ix < p->nx; ++ix)
+            for (int iy = 0; iy < p->ny; ++iy) {
+                const double ph = 2.0 * M_PI * (p->dxl * ix * A + p->dyl * iy * Bq);
+                src[(size_t)m * N + iy + p->ny * ix] = make_double2(std::cos(ph), std::sin(ph));
+            }
+    }
+    return music_synth(p, sc, src, n_inst, inst0, seed, d_X);
+}
+
+int32_t rsp_music_profile_2d(rsp_music_plan* p, const void* d_X, int32_t n_inst, int32_t iters, int32_t what,
+                             float* ms_out) {
+    if (!p || !d_X || !ms_out || iters < 1) return rsp_set_error(RSP_ERR_INVALID, "bad argument");
+    if (!p->planar) return rsp_set_error(RSP_ERR_INVALID, "rsp_music_profile_2d on a line-array plan");
+    if (what != RSP_MUSIC_PEAKS && what != RSP_MUSIC_SPECTRUM && what != RSP_MUSIC_EIGENVALUES)
+        return rsp_set_error(RSP_ERR_INVALID, "unknown profile form %d", what);
+    const int want = what == RSP_MUSIC_EIGENVALUES ? MU_WANT_EIGS
+                   : what == RSP_MUSIC_SPECTRUM ? MU_WANT_SPECTRUM : MU_WANT_PEAKS;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int it = 0; it < iters; ++it) {
+        float ms[4];
+        int rc = music_run_planar(p, d_X, n_inst, true, ms, want);
+        if (rc) return rc;
+        for (int q = 0; q < 4; ++q) acc[q] += ms[q];
+    }
+    for (int q = 0; q < 4; ++q) ms_out[q] = (float)(acc[q] / iters);
+    return RSP_OK;
+}
 
 int32_t rsp_music_create(const rsp_music_config* cfg, int32_t device, rsp_music_plan** out) {
     if (!cfg || !out || !cfg->scan_rad) return rsp_set_error(RSP_ERR_INVALID, "null argument");
@@ -1796,7 +2235,8 @@ int32_t rsp_music_destroy(rsp_music_plan* p) {
     if (!p) return RSP_OK;
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);
-    void* bufs[] = {p->d_S1T, p->d_R, p->d_X, p->d_spec, p->d_eig, p->d_peaks, p->d_src, p->d_amp, p->d_trace};
+    void* bufs[] = {p->d_S1T, p->d_R, p->d_X, p->d_spec, p->d_eig, p->d_peaks, p->d_src, p->d_amp, p->d_trace,
+                    p->d_exy, p->d_qs};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (auto& e : p->ev)
@@ -1809,6 +2249,7 @@ int32_t rsp_music_destroy(rsp_music_plan* p) {
 int32_t rsp_music_synthesize_device(rsp_music_plan* p, const rsp_music_scene* sc, int32_t n_inst, int32_t inst0,
                                     uint64_t seed, void* d_X) {
     if (!p || !sc || !d_X) return rsp_set_error(RSP_ERR_INVALID, "null argument");
+    if (p->planar) return rsp_set_error(RSP_ERR_INVALID, "rsp_music_synthesize_device on a planar-array plan");
     if (sc->n_src < 1 || sc->n_src > MU_MMAX)
         return rsp_set_error(RSP_ERR_UNSUPPORTED, "n_src %d outside 1..%d", sc->n_src, MU_MMAX);
     if (n_inst < 1) return rsp_set_error(RSP_ERR_INVALID, "n_inst %d < 1", n_inst);
@@ -1820,29 +2261,15 @@ int32_t rsp_music_synthesize_device(rsp_music_plan* p, const rsp_music_scene* sc
             const double ph = 2.0 * M_PI * p->dl * c * std::sin(sc->angles_rad[m]);
             src[(size_t)m * N + c] = make_double2(std::cos(ph), std::sin(ph));
         }
-    double amp[MU_MMAX];
-    for (int m = 0; m < MU_MMAX; ++m) amp[m] = m < Ms ? sc->amplitudes[m] : 0.0;
-    MUCHK(hipMemcpyAsync(p->d_src, src.data(), src.size() * sizeof(double2), hipMemcpyHostToDevice, p->stream));
-    MUCHK(hipMemcpyAsync(p->d_amp, amp, sizeof amp, hipMemcpyHostToDevice, p->stream));
-    const double nsc_fixed = std::sqrt(1.0 / std::pow(10.0, sc->snr_db / 10.0) / 2.0);
-    if (p->f64)
-        hipLaunchKernelGGL(k_music_synth<double2>, dim3(n_inst), dim3(MU_THREADS), 0, p->stream, N, p->K, Ms, inst0,
-                           seed, p->d_src, p->d_amp, sc->complex_sources, sc->snr_measured ? 1 : 0, sc->snr_db,
-                           nsc_fixed, (double2*)d_X);
-    else
-        hipLaunchKernelGGL(k_music_synth<float2>, dim3(n_inst), dim3(MU_THREADS), 0, p->stream, N, p->K, Ms, inst0,
-                           seed, p->d_src, p->d_amp, sc->complex_sources, sc->snr_measured ? 1 : 0, sc->snr_db,
-                           nsc_fixed, (float2*)d_X);
-    MUCHK(hipGetLastError());
-    MUCHK(hipStreamSynchronize(p->stream));   // the host staging above is stack memory
-    return RSP_OK;
+    return music_synth(p, sc, src, n_inst, inst0, seed, d_X);
 }
 
 int32_t rsp_music_process_device(rsp_music_plan* p, const void* d_X, int32_t n_inst, rsp_music_out* out) {
     if (!p || !d_X) return rsp_set_error(RSP_ERR_INVALID, "null argument");
     const int want = !out ? MU_WANT_PEAKS
                           : out->eigenvalues ? MU_WANT_EIGS : out->spectrum_db ? MU_WANT_SPECTRUM : MU_WANT_PEAKS;
-    int rc = music_run(p, d_X, n_inst, false, nullptr, want);
+    int rc = p->planar ? music_run_planar(p, d_X, n_inst, false, nullptr, want)
+                       : music_run(p, d_X, n_inst, false, nullptr, want);
     if (rc) return rc;
     if (!out) {
         MUCHK(hipStreamSynchronize(p->stream));
@@ -1886,6 +2313,7 @@ int32_t rsp_music_profile(rsp_music_plan* p, const void* d_X, int32_t n_inst, in
 int32_t rsp_music_profile_ex(rsp_music_plan* p, const void* d_X, int32_t n_inst, int32_t iters, int32_t what,
                              float* ms_out) {
     if (!p || !d_X || !ms_out || iters < 1) return rsp_set_error(RSP_ERR_INVALID, "bad argument");
+    if (p->planar) return rsp_set_error(RSP_ERR_INVALID, "planar-array plan: use rsp_music_profile_2d (four stages)");
     if (what != RSP_MUSIC_PEAKS && what != RSP_MUSIC_SPECTRUM && what != RSP_MUSIC_EIGENVALUES)
         return rsp_set_error(RSP_ERR_INVALID, "unknown profile form %d", what);
     const int want = what == RSP_MUSIC_EIGENVALUES ? MU_WANT_EIGS

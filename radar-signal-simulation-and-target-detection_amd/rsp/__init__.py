@@ -24,7 +24,7 @@ from .precompute import precompute
 from .plan import Plan, process_targets_multi
 from ._abi import RspError
 from .matio import load_frame, save_frame
-from .music import MusicPlan, MUSIC_1D
+from .music import MusicPlan, MUSIC_1D, MusicPlan2D, MUSIC_2D
 from .tracks import inter_frame_cluster, default_inter_frame_params
 from . import matio
 

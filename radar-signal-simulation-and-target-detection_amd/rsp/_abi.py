@@ -140,6 +140,19 @@ class MusicScene(ct.Structure):
                 ('amplitudes', ct.c_double * 8)]
 
 
+class Music2DConfig(ct.Structure):
+    _fields_ = [('nx', ct.c_int32), ('ny', ct.c_int32), ('num_snapshots', ct.c_int32), ('num_sources', ct.c_int32),
+                ('n_phi', ct.c_int32), ('n_theta', ct.c_int32), ('dx_over_lambda', ct.c_double),
+                ('dy_over_lambda', ct.c_double), ('phi_rad', _dp), ('theta_rad', _dp), ('max_batch', ct.c_int32),
+                ('precision', ct.c_int32)]
+
+
+class Music2DScene(ct.Structure):
+    _fields_ = [('n_src', ct.c_int32), ('complex_sources', ct.c_int32), ('snr_measured', ct.c_int32),
+                ('reserved', ct.c_int32), ('snr_db', ct.c_double), ('azim_rad', ct.c_double * 8),
+                ('elev_rad', ct.c_double * 8), ('amplitudes', ct.c_double * 8)]
+
+
 class MusicOut(ct.Structure):
     _fields_ = [('spectrum_db', _dp), ('eigenvalues', _dp),
                 ('peak_idx', ct.POINTER(ct.c_int32)), ('n_peaks', ct.POINTER(ct.c_int32)), ('covariance', _dp)]
@@ -228,6 +241,10 @@ PROTOTYPES = {
     'rsp_music_device_alloc': (ct.c_int32, [_P, ct.c_int64, ct.POINTER(_P)]),
     'rsp_music_device_free': (ct.c_int32, [_P, _P]),
     'rsp_music_device_download': (ct.c_int32, [_P, _P, _P, ct.c_int64]),
+    'rsp_music_create_2d': (ct.c_int32, [ct.POINTER(Music2DConfig), ct.c_int32, ct.POINTER(_P)]),
+    'rsp_music_synthesize_device_2d': (ct.c_int32, [_P, ct.POINTER(Music2DScene), ct.c_int32, ct.c_int32, ct.c_uint64,
+                                                    _P]),
+    'rsp_music_profile_2d': (ct.c_int32, [_P, _P, ct.c_int32, ct.c_int32, ct.c_int32, ct.POINTER(ct.c_float)]),
 }
 
 _lib = None

@@ -10,6 +10,9 @@ and returns what the scripts compute: ``P_MUSIC_dB``, the sorted eigenvalues ``E
 peak indices / angles ``phi_e`` (MUSIC_1D.m:48).  ``MUSIC_1D(X, ...)`` is the one-instance
 form of MUSIC_1D.m.  ``precision``: 'c128' (complex double, MATLAB's arithmetic; default) or
 'c64' (complex single).  All compute runs in librsp.so; there is no CPU path.
+
+``MusicPlan2D`` / ``MUSIC_2D`` are the planar-array form (MUSIC_2D.m): an nx x ny uniform
+rectangular array scanned over a theta x phi grid, peaks by imregionalmax; complex double only.
 """
 import ctypes as ct
 
@@ -173,6 +176,97 @@ class MusicPlan:
         ms = (ct.c_float * 2)()
         _abi.check(self._lib.rsp_music_profile_ex(self._h, ct.c_void_p(d_X), n_inst, iters, forms[what], ms))
         return {'cov_ms': ms[0], 'eig_ms': ms[1]}
+
+
+class MusicPlan2D(MusicPlan):
+    """MUSIC_2D.m:50-138 for an nx x ny uniform rectangular array (rsp_music_create_2d): element
+    (ix, iy) is channel iy + ny*ix (MUSIC_2D.m:17-19), the scan runs over the theta x phi grid, the
+    peaks are imregionalmax's.  Complex double only.  Outputs of ``process`` / ``process_device``:
+    ``spectrum_db`` [n, n_theta, n_phi] (P_MUSIC_dB), ``peaks`` (1-based linear indices
+    r + n_theta (c - 1), 0 = none), ``peak_rows`` / ``peak_cols`` (1-based), ``phi_e_deg`` /
+    ``theta_e_deg`` (NaN where there is no peak), ``n_peaks`` (pixels of the imregionalmax mask),
+    ``eig``, ``R``."""
+
+    def __init__(self, nx, ny, num_snapshots, num_sources, phi_rad, theta_rad, dx_over_lambda=0.5,
+                 dy_over_lambda=0.5, max_batch=1, device=0):
+        self._lib = _abi.lib()
+        self.precision = 'c128'
+        self.cdtype = np.complex128
+        self.phi_rad = np.ascontiguousarray(phi_rad, np.float64)
+        self.theta_rad = np.ascontiguousarray(theta_rad, np.float64)
+        self.nx, self.ny = int(nx), int(ny)
+        self.n_phi, self.n_theta = len(self.phi_rad), len(self.theta_rad)
+        self.N, self.K, self.M = self.nx * self.ny, int(num_snapshots), int(num_sources)
+        self.S = self.n_phi * self.n_theta
+        self.max_batch = int(max_batch)
+        cfg = _abi.Music2DConfig(self.nx, self.ny, self.K, self.M, self.n_phi, self.n_theta, float(dx_over_lambda),
+                                 float(dy_over_lambda), self.phi_rad.ctypes.data_as(_abi._dp),
+                                 self.theta_rad.ctypes.data_as(_abi._dp), self.max_batch, _abi.RSP_C128)
+        h = ct.c_void_p()
+        _abi.check(self._lib.rsp_music_create_2d(ct.byref(cfg), int(device), ct.byref(h)))
+        self._h = h
+
+    def _finish(self, o):
+        if 'R' in o:
+            r = o.pop('R')
+            o['R'] = np.ascontiguousarray(np.transpose(r[..., 0] + 1j * r[..., 1], (0, 2, 1)))
+        n = o['spectrum_db'].shape[0]
+        # device order: theta fastest (MATLAB's column-major n_theta x n_phi)
+        o['spectrum_db'] = np.ascontiguousarray(
+            np.transpose(o['spectrum_db'].reshape(n, self.n_phi, self.n_theta), (0, 2, 1)))
+        o.update(self._peak_fields(o['peaks']))
+        return o
+
+    def _peak_fields(self, pk):
+        z = np.maximum(pk - 1, 0)
+        rows, cols = z % self.n_theta, z // self.n_theta
+        return {'peak_rows': np.where(pk > 0, rows + 1, 0), 'peak_cols': np.where(pk > 0, cols + 1, 0),
+                'phi_e_deg': np.where(pk > 0, np.rad2deg(self.phi_rad[cols]), np.nan),
+                'theta_e_deg': np.where(pk > 0, np.rad2deg(self.theta_rad[rows]), np.nan)}
+
+    def synthesize_device(self, d_X, scene, n_inst, inst0=0, seed=20250101):
+        az, el = list(scene['azim_rad']), list(scene['elev_rad'])
+        amp = list(scene.get('amplitudes', [1.0] * len(az)))
+        sc = _abi.Music2DScene(len(az), int(scene.get('complex_sources', 1)), int(scene.get('snr_measured', 1)), 0,
+                               float(scene['snr_db']), (ct.c_double * 8)(*az), (ct.c_double * 8)(*el),
+                               (ct.c_double * 8)(*amp))
+        _abi.check(self._lib.rsp_music_synthesize_device_2d(self._h, ct.byref(sc), n_inst, inst0, ct.c_uint64(seed),
+                                                            ct.c_void_p(d_X)))
+
+    def profile(self, d_X, n_inst, iters=20, what='peaks'):
+        """HIP-event times of the four stages (covariance, signal subspace, scan, dB + peaks) for the
+        form of call ``what``: 'peaks', 'spectrum' or 'eigenvalues'."""
+        forms = {'peaks': _abi.RSP_MUSIC_PEAKS, 'spectrum': _abi.RSP_MUSIC_SPECTRUM,
+                 'eigenvalues': _abi.RSP_MUSIC_EIGENVALUES}
+        ms = (ct.c_float * 4)()
+        _abi.check(self._lib.rsp_music_profile_2d(self._h, ct.c_void_p(d_X), n_inst, iters, forms[what], ms))
+        return {'cov_ms': ms[0], 'subspace_ms': ms[1], 'scan_ms': ms[2], 'peaks_ms': ms[3]}
+
+
+def music_2d_scene():
+    """MUSIC_2D.m:4-30,61-62: 8 x 8 array at dx = dy = lambda/2, complex sources at (phi, theta) =
+    (30, 20) and (-60, 45) deg, 1000 snapshots, awgn 10 dB 'measured', scan phi = linspace(-90, 90,
+    181), theta = linspace(0, 90, 91) deg.  Returns (scene dict for MusicPlan2D.synthesize_device,
+    phi grid [rad], theta grid [rad], dx/lambda, dy/lambda); nx = ny = 8, K = 1000, M = 2."""
+    return ({'azim_rad': np.array([30.0, -60.0]) * np.pi / 180, 'elev_rad': np.array([20.0, 45.0]) * np.pi / 180,
+             'amplitudes': np.ones(2), 'complex_sources': 1, 'snr_db': 10.0, 'snr_measured': 1},
+            np.linspace(-90.0, 90.0, 181) * np.pi / 180, np.linspace(0.0, 90.0, 91) * np.pi / 180, 0.5, 0.5)
+
+
+def MUSIC_2D(X1, M, nx, ny, phi_list=None, theta_list=None, dx_over_lambda=0.5, dy_over_lambda=0.5, device=0):
+    """MUSIC_2D.m:50-138 on one snapshot matrix X1 [nx*ny x K]: returns (phi_e [deg], theta_e [deg],
+    P_MUSIC_dB [n_theta x n_phi], EVA)."""
+    X1 = np.asarray(X1)
+    _, phi_d, theta_d, _, _ = music_2d_scene()
+    phi_list = phi_d if phi_list is None else phi_list          # MUSIC_2D.m:61
+    theta_list = theta_d if theta_list is None else theta_list  # MUSIC_2D.m:62
+    plan = MusicPlan2D(nx, ny, X1.shape[1], M, phi_list, theta_list, dx_over_lambda, dy_over_lambda, max_batch=1,
+                       device=device)
+    try:
+        o = plan.process(X1)
+    finally:
+        plan.close()
+    return o['phi_e_deg'][0], o['theta_e_deg'][0], o['spectrum_db'][0], o['eig'][0]
 
 
 def music_1d_scene():
