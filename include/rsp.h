@@ -73,7 +73,8 @@ typedef struct rsp_sig_config {
     int32_t beam_num;         /* B                                  */
 } rsp_sig_config;
 
-/* cfar_params (v8:45-47). Only 'GOCA' exists in the reference. */
+/* cfar_params (v8:45-47). Only 'GOCA' exists in fun_process_single_frame; the range CFAR of the
+ * stage-2 path, with its greatest-of / smallest-of switch, is rsp_stage3_cfar_params below. */
 typedef struct rsp_cfar_params {
     int32_t refCells_V, guardCells_V, refCells_R, guardCells_R;
     double T_CFAR;
@@ -333,6 +334,89 @@ int32_t rsp_process_stage2(rsp_plan* plan, const void* iq_beams, int32_t dtype,
  * cols = NULL: the reference gating 83:310, 311:1033, 1034:3486 (n_gated = 3404). */
 int32_t rsp_process_stage2_gated(rsp_plan* plan, const void* iq_gated, int32_t dtype, int32_t n_gated,
                                  const int32_t* cols, double* mtd_out, double* pc_out);
+
+/* ---- stage-3 range CFAR of the stage-2 path ----
+ * local_execute_cfar / executeCFAR_2D / Function_CFAR1D_sub of
+ * debug_simulated_data_processing_v2.m:419-511, the detector every caller of process_stage2_mtd
+ * feeds |MTD| into (:209-213).  Per real amplitude map A [P x G]:
+ *   notch (:446-450): zc = round(P/2) + 1; rows max(1, zc - MTD_0v_num) .. min(P, zc + MTD_0v_num)
+ *     (1-based) get flag 0 and threshold 0;
+ *   segments (:423-439): columns 1..n1, n1+1..n1+n2, n1+n2+1..G (n1 = N_gate_narrow, n2 =
+ *     N_gate_medium) are processed on their own, each with edges of its own;
+ *   cell y of a segment of n columns (:481-505), r = refCells_R, s = saveCells_R:
+ *     L = y-(s+r) .. y-s-1, R = y+s+1 .. y+s+r; mL = mean(L) if y-(s+r) >= 1 else mean(R);
+ *     mR = mean(R) if y+s+r <= n else mean(L); u = max(mL, mR) (CFARmethod_R = 0) or min (1);
+ *     threshold = u * T_CFAR; flag = A >= threshold.
+ * mean = the r cells summed in ascending column order, divided by r.  Every operation is one
+ * correctly rounded IEEE operation in the plan's precision (double for RSP_C128, float for
+ * RSP_C64; T_CFAR and the amplitudes are rounded to it first), so the result is defined to the
+ * bit; thresholds and amplitudes leave the device widened to double.  Not k3_cfar: range only,
+ * per segment, >= instead of >, and the threshold matrix is an output. */
+typedef struct rsp_stage3_cfar_params {
+    int32_t refCells_R, saveCells_R, CFARmethod_R, MTD_0v_num;
+    double T_CFAR;
+} rsp_stage3_cfar_params;
+
+/* One flagged cell: 1-based Doppler row, range column and map (beam); the amplitude tested and its
+ * threshold.  Lists are ordered by beam, then as find() on [P x G]: r_idx outer, v_idx inner. */
+typedef struct rsp_stage3_hit {
+    int32_t v_idx, r_idx, beam_idx, reserved;
+    double amp, threshold;
+} rsp_stage3_hit;
+
+/* What the CFAR does with a map of P rows and these segments (rsp_stage3_describe). */
+typedef struct rsp_stage3_info {
+    int32_t P, G;
+    int32_t seg_first[3];     /* 1-based first column of the narrow / medium / long segment      */
+    int32_t seg_len[3];       /* their lengths (an empty segment has no cells and no constraint) */
+    int32_t notch_first, notch_last;   /* 1-based notched rows, clipped to 1..P (first > last: none) */
+    int32_t halo;             /* s + r: cells a window reaches on either side of its cell        */
+    int32_t max_halo;         /* the largest s + r the kernel's tile holds                       */
+    int32_t chunk;            /* range cells one workgroup of k_s3_cfar resolves per Doppler row  */
+    int32_t rows;             /* Doppler rows per workgroup                                      */
+} rsp_stage3_info;
+
+/* The checks of the calls below, with the same refusals and messages, and the layout they use,
+ * for prtNum of `cfg` and the gate counts of `pre` (the other fields are not read).  RSP_ERR_INVALID:
+ * refCells_R < 1, saveCells_R < 0, CFARmethod_R not 0 or 1, MTD_0v_num < 0, T_CFAR not finite or
+ * <= 0, a non-empty segment shorter than 2 (s + r) (the reference indexes out of range there),
+ * s + r beyond max_halo.  `info` may be NULL.  No HIP call is made. */
+int32_t rsp_stage3_describe(const rsp_sig_config* cfg, const rsp_precomputed* pre,
+                            const rsp_stage3_cfar_params* params, rsp_stage3_info* info);
+
+/* local_execute_cfar on host maps: amp is real double [P x G x n_maps] column-major with the
+ * plan's P and gate counts; flags (uint8) and threshold (double) have the same shape.  Any output
+ * may be NULL.  *n_hits = flagged cells of all maps; min(*n_hits, hits_cap) entries of `hits` are
+ * written, the first ones in order.  Synchronous; drains the queue first.  Refusals come before
+ * any device work. */
+int32_t rsp_stage3_cfar(rsp_plan* plan, const double* amp, int32_t n_maps, const rsp_stage3_cfar_params* params,
+                        uint8_t* flags, double* threshold, rsp_stage3_hit* hits, int64_t hits_cap, int64_t* n_hits);
+/* The same for maps of another shape: P rows and segments of gates[0], gates[1], gates[2] columns
+ * (local_execute_cfar takes any map; odd P included).  The plan gives the device and the precision. */
+int32_t rsp_stage3_cfar_shape(rsp_plan* plan, int32_t P, const int32_t* gates, const double* amp, int32_t n_maps,
+                              const rsp_stage3_cfar_params* params, uint8_t* flags, double* threshold,
+                              rsp_stage3_hit* hits, int64_t hits_cap, int64_t* n_hits);
+/* rsp_process_stage2, then the CFAR on |MTD_results| of all B beams without leaving the device
+ * (the magnitude routine of k2_pc's maps).  mtd_out complex [P x G x B]; amp_out (the map that
+ * was tested), flags, threshold [P x G x B]; hits as above with beam_idx = the beam.  Every output
+ * is optional: a call that asks for the hit list alone downloads nothing else. */
+int32_t rsp_process_stage2_cfar(rsp_plan* plan, const void* iq_beams, int32_t dtype,
+                                const rsp_stage3_cfar_params* params, double* mtd_out, double* amp_out,
+                                uint8_t* flags, double* threshold, rsp_stage3_hit* hits, int64_t hits_cap,
+                                int64_t* n_hits);
+/* The same on a gated input (iq_gated, n_gated, cols as rsp_process_stage2_gated). */
+int32_t rsp_process_stage2_gated_cfar(rsp_plan* plan, const void* iq_gated, int32_t dtype, int32_t n_gated,
+                                      const int32_t* cols, const rsp_stage3_cfar_params* params, double* mtd_out,
+                                      double* amp_out, uint8_t* flags, double* threshold, rsp_stage3_hit* hits,
+                                      int64_t hits_cap, int64_t* n_hits);
+/* Device time of k_s3_cfar over the plan's B beams of [P x G], by HIP events on the plan's stream,
+ * averaged over `iters` launches each: ms_out[0] the real-amplitude form writing flags and
+ * thresholds (rsp_stage3_cfar's launch), [1] the complex form writing amplitudes, flags and
+ * thresholds, [2] the complex form with the hit list alone.  bytes_out[i] = algorithmic HBM bytes
+ * of launch i (the hit records not counted).  The maps are the MTD result of the plan's last
+ * stage-2 call and its magnitudes (RSP_ERR_INVALID when there has been none). */
+int32_t rsp_profile_stage3(rsp_plan* plan, const rsp_stage3_cfar_params* params, int32_t iters, float* ms_out,
+                           int64_t* bytes_out);
 
 /* ---- measurement ----
  * Time each device stage `iters` times on the plan's stream with HIP events.  Each launch

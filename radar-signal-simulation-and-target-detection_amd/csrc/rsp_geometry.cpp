@@ -745,3 +745,66 @@ extern "C" int32_t rsp_plan_describe_k3(const rsp_sig_config* cfg, const rsp_cfa
     if (tiling) rsp_fill_k3_tiling(h.g, tiling);
     return RSP_OK;
 }
+
+// ---- stage-3 range CFAR (debug_simulated_data_processing_v2.m:419-511) ----
+int rsp_stage3_derive(int P, const int32_t* gates, const rsp_stage3_cfar_params* prm, S3Desc* out) {
+    if (!gates || !prm || !out) return fail(RSP_ERR_INVALID, "null argument");
+    const int64_t G = (int64_t)gates[0] + gates[1] + gates[2];
+    if (P < 1 || gates[0] < 0 || gates[1] < 0 || gates[2] < 0 || G < 1 || G > INT32_MAX)
+        return fail(RSP_ERR_INVALID, "bad map shape P=%d segments %d, %d, %d", P, gates[0], gates[1], gates[2]);
+    const int r = prm->refCells_R, s = prm->saveCells_R;
+    if (r < 1 || s < 0) return fail(RSP_ERR_INVALID, "bad CFAR window refCells_R=%d saveCells_R=%d (r >= 1, s >= 0)", r, s);
+    if (prm->CFARmethod_R != 0 && prm->CFARmethod_R != 1)
+        return fail(RSP_ERR_INVALID, "CFARmethod_R must be 0 (greatest of) or 1 (smallest of), got %d", prm->CFARmethod_R);
+    if (prm->MTD_0v_num < 0) return fail(RSP_ERR_INVALID, "MTD_0v_num must be >= 0, got %d", prm->MTD_0v_num);
+    if (!std::isfinite(prm->T_CFAR) || prm->T_CFAR <= 0) return fail(RSP_ERR_INVALID, "T_CFAR must be finite and > 0, got %g", prm->T_CFAR);
+    const int64_t H = (int64_t)r + s;
+    if (H > RSP_S3_HMAX)
+        return fail(RSP_ERR_INVALID, "CFAR window refCells_R + saveCells_R = %lld exceeds the kernel's tile halo %d", (long long)H,
+                    RSP_S3_HMAX);
+    S3Desc d{};
+    d.P = P;
+    d.G = (int)G;
+    int a = 0;
+    for (int k = 0; k < 3; ++k) {
+        if (gates[k] > 0 && gates[k] < 2 * H)
+            return fail(RSP_ERR_INVALID, "segment %d has %d columns, fewer than 2 (saveCells_R + refCells_R) = %lld", k, gates[k],
+                        (long long)(2 * H));
+        d.seg_a[k] = a;
+        d.seg_n[k] = gates[k];
+        a += gates[k];
+    }
+    d.r = r; d.s = s; d.H = (int)H;
+    d.method = prm->CFARmethod_R;
+    d.T = prm->T_CFAR;
+    // zero_v_center = round(P / 2) + 1, MATLAB round: half away from zero (:447)
+    const int64_t zc = (int64_t)std::floor(P / 2.0 + 0.5) + 1, z = prm->MTD_0v_num;
+    d.z0 = (int)std::max<int64_t>(1, zc - z) - 1;
+    d.z1 = (int)std::min<int64_t>(P, zc + z) - 1;
+    *out = d;
+    return RSP_OK;
+}
+
+extern "C" int32_t rsp_stage3_describe(const rsp_sig_config* cfg, const rsp_precomputed* pre,
+                                       const rsp_stage3_cfar_params* params, rsp_stage3_info* info) {
+    if (!cfg || !pre || !params) return fail(RSP_ERR_INVALID, "null argument");
+    if (pre->N_total_gate != pre->N_gate_narrow + pre->N_gate_medium + pre->N_gate_long)
+        return fail(RSP_ERR_INVALID, "gate counts inconsistent");
+    const int32_t gates[3] = {pre->N_gate_narrow, pre->N_gate_medium, pre->N_gate_long};
+    S3Desc d;
+    int rc = rsp_stage3_derive(cfg->prtNum, gates, params, &d);
+    if (rc || !info) return rc;
+    info->P = d.P;
+    info->G = d.G;
+    for (int k = 0; k < 3; ++k) {
+        info->seg_first[k] = d.seg_a[k] + 1;
+        info->seg_len[k] = d.seg_n[k];
+    }
+    info->notch_first = d.z0 + 1;
+    info->notch_last = d.z1 + 1;
+    info->halo = d.H;
+    info->max_halo = RSP_S3_HMAX;
+    info->chunk = RSP_S3_CH;
+    info->rows = RSP_S3_ROWS;
+    return RSP_OK;
+}

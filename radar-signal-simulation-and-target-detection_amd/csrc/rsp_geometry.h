@@ -194,6 +194,25 @@ struct PlanHost {
     std::vector<int> k2order;        // pulse-compression workgroup dispatch order
 };
 
+// Stage-3 range CFAR (k_s3_cfar, rsp_stage3.hip).  A workgroup resolves RSP_S3_ROWS Doppler rows
+// (4 waves, a row per wave and pass) of RSP_S3_CH range cells on the map's own column grid, each
+// row from a tile that holds the chunk and RSP_S3_HMAX cells on either side: s + r <= RSP_S3_HMAX
+// is the envelope.
+#define RSP_S3_CH 256
+#define RSP_S3_ROWS 16
+#define RSP_S3_HMAX 64
+struct S3Desc {          // kernel argument
+    int P, G;
+    int seg_a[3], seg_n[3];   // 0-based first column and length of each segment
+    int r, s, H;              // refCells_R, saveCells_R, s + r
+    int method;               // 0: greatest of, 1: smallest of
+    int z0, z1;               // 0-based notched rows, inclusive (z0 > z1: none)
+    double T;                 // T_CFAR
+};
+// The checks of the stage-3 calls and the descriptor for a map of P rows and segments of
+// gates[0..2] columns.  RSP_OK, or RSP_ERR_INVALID with the message set.
+int rsp_stage3_derive(int P, const int32_t* gates, const rsp_stage3_cfar_params* prm, S3Desc* out);
+
 // The checks of rsp_plan_create_ex that need no device and come before its device checks.
 int rsp_plan_check_args(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params* cluster,
                         const rsp_precomputed* pre, const rsp_plan_options* opt);

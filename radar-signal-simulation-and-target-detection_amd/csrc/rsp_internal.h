@@ -88,6 +88,13 @@ hipError_t launch_mtd_cols(const Geometry& g, const DevConsts& k, const void* pc
 // S4 + S4.1: tab holds RSP_MAX_SYNTH_TARGETS x (P + C) complex doubles (the per-target phasors)
 hipError_t launch_synth(const Geometry& g, const double* tx, const SynthTargets& tg, int nt, void* tab, int frame_idx,
                         uint64_t seed, double noise_scale, void* cube, hipStream_t s);
+// Stage-3 range CFAR (rsp_stage3.hip) of n_maps maps [n_maps][P][G], range fastest: `in` holds
+// complex values of the precision (cplx: the stage-2 result, magnitudes by cmag) or real
+// amplitudes.  Outputs, each optional: amp / thr as double, flags as bytes (same layout), hits
+// (rsp_stage3_hit records, any order, the first hits_cap of them) counted in *count, which the
+// caller zeroes.
+hipError_t launch_s3(const S3Desc& d, int prec, bool cplx, const void* in, int n_maps, double* amp, double* thr,
+                     uint8_t* flags, rsp_stage3_hit* hits, int* count, int hits_cap, hipStream_t s);
 // Queue read-back: count record + the detections of nf frames (device stride dcap + 1 records) into
 // mapped pinned host memory (stride hcap + 1), only the records that exist.
 hipError_t launch_dets_to_host(const void* dets, int dcap, void* host, int hcap, int nf, hipStream_t s);

@@ -20,14 +20,13 @@
 // reference's MATLAB arithmetic; the default) or float (complex64).  Complex values are
 // 2-wide ext_vector pairs (re, im) of T in registers, LDS and HBM alike.
 #include "rsp_internal.h"
+#include "rsp_cmag.h"
 #include "rsp_noise_math.h"
 #include <math.h>
 #include <algorithm>
 
 namespace {
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef double d2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -60,22 +59,7 @@ __device__ __forceinline__ V vtw(double c, double s) {   // exp(-+ i theta)
     typedef scal<V> S;
     return V{(S)c, (S)(INV ? s : -s)};
 }
-// |x| (fsf:184-185 abs): hardware square root for float (v_sqrt_f32, 1 ulp); for double the
-// compiler's own refinement of v_rsq_f64 (Goldschmidt step + two Newton corrections) without
-// its ldexp scaling and class checks, which guard only denormal / infinite inputs -- not the
-// magnitudes of a radar map; 0 stays 0.
-__device__ __forceinline__ float cmag(f2 x) { return __builtin_amdgcn_sqrtf(x.x * x.x + x.y * x.y); }
-__device__ __forceinline__ double cmag(d2 x) {
-    const double q = x.x * x.x + x.y * x.y;
-    const double r = __builtin_amdgcn_rsq(q);           // v_rsq_f64
-    double g = q * r, h = 0.5 * r;
-    const double r0 = __builtin_fma(-h, g, 0.5);
-    g = __builtin_fma(g, r0, g);
-    h = __builtin_fma(h, r0, h);
-    g = __builtin_fma(__builtin_fma(-g, g, q), h, g);
-    g = __builtin_fma(__builtin_fma(-g, g, q), h, g);
-    return q > 0.0 ? g : 0.0;
-}
+// |x| (fsf:184-185 abs): cmag, rsp_cmag.h (shared with the stage-3 CFAR)
 
 // Raw buffer resources (SRSRC): 32-bit byte offsets and hardware range checking.  An offset at
 // or past num_records reads 0 / drops the store, so masked lanes need no branch or select.

@@ -147,6 +147,15 @@ struct rsp_plan {
     void* d_cube = nullptr;       // staging cube for the synchronous paths
     void* d_aux = nullptr;        // second map for the stage-2 path
     void* d_smap = nullptr;       // rdm_for_cfar_all of the synchronous path (allocated on first request)
+    // stage-3 range CFAR (rsp_stage3_cfar, rsp_process_stage2_cfar): the segments' gate counts, whether
+    // d_aux holds a stage-2 result, and device buffers that grow on demand (freed with the plan)
+    int32_t gates[3] = {0, 0, 0};
+    bool aux_valid = false;
+    struct DevBuf {
+        void* p = nullptr;
+        size_t cap = 0;
+    };
+    DevBuf s3_in, s3_amp, s3_thr, s3_flags, s3_hits, s3_count;
     unsigned char* h_stage = nullptr;   // pinned staging for uploads
     size_t h_stage_bytes = 0;
     Lane lanes[RSP_LANES];
@@ -253,6 +262,8 @@ rsp_plan::~rsp_plan() {
     for (auto e : slot_free) if (e) (void)hipEventDestroy(e);
     if (up_stream) (void)hipStreamDestroy(up_stream);
     if (h_stage) (void)hipHostFree(h_stage);
+    for (DevBuf* b : {&s3_in, &s3_amp, &s3_thr, &s3_flags, &s3_hits, &s3_count})
+        if (b->p) (void)hipFree(b->p);
     for (void* p : dev_allocs) (void)hipFree(p);
 }
 
@@ -603,6 +614,156 @@ int run_sync_frame(rsp_plan* p, const void* d_in, int frame_idx, rsp_frame_out* 
     return RSP_OK;
 }
 
+// The device half of rsp_process_stage2: PC_results into lane 0's map, MTD_results into p->d_aux
+// (both [B][P][G] complex in the plan's precision); returns with the stream idle.
+int stage2_device(rsp_plan* p, const void* iq, int dtype) {
+    HIPCHK(hipSetDevice(p->device));
+    int rc = drain_all(p);
+    if (rc) return rc;
+    Lane& L = p->lanes[0];
+    Geometry gs = p->g;
+    gs.C = gs.B;   // input channels are the beams; K1 transposes only (no DBF, no MTD)
+    if ((rc = upload_cube(p, iq, dtype, gs.B, p->d_cube, L.stream))) return rc;
+    if (!p->d_aux && (rc = p->dalloc_bytes(&p->d_aux, p->rdm_elems * p->esz))) return rc;
+    const void* in[1] = {p->d_cube};
+    void* rdm[1] = {L.rdm};
+    const FramePtrs fp = lane_ptrs(p, L, in, 1, rdm);
+    HIPCHK(launch_k1(gs, p->k, fp, 1, 0, L.stream));
+    HIPCHK(launch_k2(gs, p->k, fp, 1, gs.B * gs.P, L.stream));      // PC rows (b, m) -> L.rdm
+    HIPCHK(launch_mtd_cols(gs, p->k, L.rdm, p->d_aux, L.stream));  // S7 over pulses
+    HIPCHK(hipStreamSynchronize(L.stream));
+    p->aux_valid = true;
+    return RSP_OK;
+}
+
+// Gated stage-2 input -> full-PRT [P x N x B] with the gated columns at their PRT positions
+// (zeros elsewhere), the checks of rsp_process_stage2_gated included.
+int stage2_regate(const rsp_plan* p, const void* iq, int dtype, int n_gated, const int32_t* cols,
+                  std::vector<unsigned char>& full) {
+    if (dtype != RSP_C64 && dtype != RSP_C128) return fail(RSP_ERR_INVALID, "unknown dtype %d", dtype);
+    static const int32_t kRefCols[6] = {83, 310, 311, 1033, 1034, 3486};   // main_simulate_echoes_with_array_v2.m:257-264
+    const int32_t* c = cols ? cols : kRefCols;
+    const int P = p->g.P, N = p->g.N, B = p->g.B;
+    int total = 0;
+    for (int k = 0; k < 3; ++k) {
+        if (c[2 * k] < 1 || c[2 * k + 1] < c[2 * k] || c[2 * k + 1] > N)
+            return fail(RSP_ERR_INVALID, "gate columns %d..%d of segment %d outside the %d-sample PRT", c[2 * k],
+                        c[2 * k + 1], k, N);
+        if (k > 0 && c[2 * k] <= c[2 * k - 1])   // ascending and disjoint, like v2:257-264
+            return fail(RSP_ERR_INVALID, "gate columns of segment %d (%d..%d) overlap or precede segment %d (..%d)", k,
+                        c[2 * k], c[2 * k + 1], k - 1, c[2 * k - 1]);
+        total += c[2 * k + 1] - c[2 * k] + 1;
+    }
+    if (total != n_gated) return fail(RSP_ERR_INVALID, "gated input has %d columns, the gate columns cover %d", n_gated, total);
+    // put the gated columns back at their PRT positions (zeros elsewhere): [P x N x B]
+    const size_t es = dtype == RSP_C128 ? 16 : 8, colb = (size_t)P * es;
+    full.assign((size_t)N * B * colb, 0);
+    const unsigned char* src = static_cast<const unsigned char*>(iq);
+    for (int b = 0; b < B; ++b) {
+        int ng = 0;
+        for (int k = 0; k < 3; ++k)
+            for (int col = c[2 * k] - 1; col < c[2 * k + 1]; ++col, ++ng)
+                memcpy(&full[((size_t)b * N + col) * colb], src + ((size_t)b * n_gated + ng) * colb, colb);
+    }
+    return RSP_OK;
+}
+
+// ---- stage-3 range CFAR ----
+int s3_reserve(rsp_plan::DevBuf& b, size_t bytes) {
+    if (b.cap >= bytes && b.p) return RSP_OK;
+    if (b.p) HIPCHK(hipFree(b.p));
+    b.p = nullptr;
+    b.cap = 0;
+    if (hipMalloc(&b.p, bytes) != hipSuccess) {
+        b.p = nullptr;
+        return fail(RSP_ERR_NOMEM, "hipMalloc(%zu bytes) failed", bytes);
+    }
+    b.cap = bytes;
+    return RSP_OK;
+}
+
+struct S3Out {   // host outputs of one CFAR call, each optional
+    double* amp;
+    uint8_t* flags;
+    double* thr;
+    rsp_stage3_hit* hits;
+    int64_t hits_cap;
+    int64_t* n_hits;
+};
+
+// device [n][P][G] -> MATLAB column-major [P x G x n]
+template <class V>
+int s3_to_matlab(const void* d_map, int P, int G, int n, V* out) {
+    const size_t cells = (size_t)n * P * G;
+    std::vector<V> m(cells);
+    HIPCHK(hipMemcpy(m.data(), d_map, cells * sizeof(V), hipMemcpyDeviceToHost));
+    for (int b = 0; b < n; ++b)
+        for (int v = 0; v < P; ++v) {
+            const V* src = &m[((size_t)b * P + v) * G];
+            V* dst = out + (size_t)v + (size_t)P * G * b;
+            for (int r = 0; r < G; ++r) dst[(size_t)P * r] = src[r];
+        }
+    return RSP_OK;
+}
+
+// The map count the kernel's 32-bit hit counter and grid admit
+int s3_check_cells(int P, int G, int n_maps) {
+    if (n_maps < 1 || n_maps > 65535 || (int64_t)n_maps * P * G >= ((int64_t)1 << 31) || (P + RSP_S3_ROWS - 1) / RSP_S3_ROWS > 65535)
+        return fail(RSP_ERR_INVALID, "%d maps of %d x %d cells: 1 .. 65535 maps and fewer than 2^31 cells in all", n_maps, P, G);
+    return RSP_OK;
+}
+
+// k_s3_cfar over n_maps device maps d_in (complex: the stage-2 result; else real amplitudes of the
+// plan's precision) on lane 0's stream, then the requested outputs to the host.
+int s3_run(rsp_plan* p, const S3Desc& d, bool cplx, const void* d_in, int n_maps, const S3Out& o) {
+    Lane& L = p->lanes[0];
+    const size_t cells = (size_t)n_maps * d.P * d.G;
+    int rc;
+    if (o.amp && (rc = s3_reserve(p->s3_amp, cells * 8))) return rc;
+    if (o.thr && (rc = s3_reserve(p->s3_thr, cells * 8))) return rc;
+    if (o.flags && (rc = s3_reserve(p->s3_flags, cells))) return rc;
+    if ((rc = s3_reserve(p->s3_count, 16))) return rc;
+    const bool list = o.hits && o.hits_cap > 0;
+    if (list && (rc = s3_reserve(p->s3_hits, sizeof(rsp_stage3_hit) * std::min<size_t>(cells, 65536)))) return rc;
+    int total = 0;
+    for (int pass = 0;; ++pass) {
+        const int cap = list ? (int)std::min<size_t>(p->s3_hits.cap / sizeof(rsp_stage3_hit), (size_t)INT32_MAX) : 0;
+        HIPCHK(hipMemsetAsync(p->s3_count.p, 0, 4, L.stream));
+        HIPCHK(launch_s3(d, p->g.prec, cplx, d_in, n_maps, o.amp ? (double*)p->s3_amp.p : nullptr,
+                         o.thr ? (double*)p->s3_thr.p : nullptr, o.flags ? (uint8_t*)p->s3_flags.p : nullptr,
+                         list ? (rsp_stage3_hit*)p->s3_hits.p : nullptr, (int*)p->s3_count.p, cap, L.stream));
+        HIPCHK(hipStreamSynchronize(L.stream));
+        HIPCHK(hipMemcpy(&total, p->s3_count.p, 4, hipMemcpyDeviceToHost));
+        if (!list || total <= cap) break;
+        if (pass > 0) return fail(RSP_ERR_DEVICE, "stage-3 hit count changed between two runs on the same map");
+        if ((rc = s3_reserve(p->s3_hits, sizeof(rsp_stage3_hit) * (size_t)total))) return rc;   // every hit, then again
+    }
+    if (o.n_hits) *o.n_hits = total;
+    if (o.amp && (rc = s3_to_matlab<double>(p->s3_amp.p, d.P, d.G, n_maps, o.amp))) return rc;
+    if (o.thr && (rc = s3_to_matlab<double>(p->s3_thr.p, d.P, d.G, n_maps, o.thr))) return rc;
+    if (o.flags && (rc = s3_to_matlab<uint8_t>(p->s3_flags.p, d.P, d.G, n_maps, o.flags))) return rc;
+    if (list && total > 0) {
+        // the device list is in no order: beam, then find() order on [P x G] (r outer, v inner)
+        std::vector<rsp_stage3_hit> h((size_t)total);
+        HIPCHK(hipMemcpy(h.data(), p->s3_hits.p, sizeof(rsp_stage3_hit) * (size_t)total, hipMemcpyDeviceToHost));
+        std::sort(h.begin(), h.end(), [](const rsp_stage3_hit& a, const rsp_stage3_hit& b) {
+            if (a.beam_idx != b.beam_idx) return a.beam_idx < b.beam_idx;
+            if (a.r_idx != b.r_idx) return a.r_idx < b.r_idx;
+            return a.v_idx < b.v_idx;
+        });
+        memcpy(o.hits, h.data(), sizeof(rsp_stage3_hit) * (size_t)std::min<int64_t>(total, o.hits_cap));
+    }
+    return RSP_OK;
+}
+
+int s3_fused(rsp_plan* p, const void* iq, int dtype, const rsp_stage3_cfar_params* prm, double* mtd_out, const S3Out& o) {
+    S3Desc d;
+    int rc = rsp_stage3_derive(p->g.P, p->gates, prm, &d);   // refusals before any device work
+    if (rc || (rc = s3_check_cells(d.P, d.G, p->g.B)) || (rc = stage2_device(p, iq, dtype))) return rc;
+    if (mtd_out && (rc = rdm_to_matlab(p, p->d_aux, mtd_out))) return rc;
+    return s3_run(p, d, true, p->d_aux, p->g.B, o);
+}
+
 const char* kStageNames[] = {"k1_dbf_mtd", "k2_pc", "k3_cfar"};
 
 }  // namespace
@@ -658,6 +819,7 @@ int32_t rsp_plan_create_ex(const rsp_sig_config* cfg, const rsp_cfar_params* cfa
     p->g = h.g;
     p->det_bound = h.det_bound;
     p->z_elems = h.z_elems; p->rdm_elems = h.rdm_elems; p->mag_elems = h.mag_elems;
+    p->gates[0] = pre->N_gate_narrow; p->gates[1] = pre->N_gate_medium; p->gates[2] = pre->N_gate_long;
 
     // ---- constants to the device, in the plan's precision
     DevConsts& k = p->k;
@@ -1007,22 +1169,9 @@ int32_t rsp_results_clear(rsp_plan* p) {
 
 int32_t rsp_process_stage2(rsp_plan* p, const void* iq, int32_t dtype, double* mtd_out, double* pc_out) {
     if (!p || !iq) return fail(RSP_ERR_INVALID, "null argument");
-    HIPCHK(hipSetDevice(p->device));
-    int rc = drain_all(p);
+    int rc = stage2_device(p, iq, dtype);
     if (rc) return rc;
-    Lane& L = p->lanes[0];
-    Geometry gs = p->g;
-    gs.C = gs.B;   // input channels are the beams; K1 transposes only (no DBF, no MTD)
-    if ((rc = upload_cube(p, iq, dtype, gs.B, p->d_cube, L.stream))) return rc;
-    if (!p->d_aux && (rc = p->dalloc_bytes(&p->d_aux, p->rdm_elems * p->esz))) return rc;
-    const void* in[1] = {p->d_cube};
-    void* rdm[1] = {L.rdm};
-    const FramePtrs fp = lane_ptrs(p, L, in, 1, rdm);
-    HIPCHK(launch_k1(gs, p->k, fp, 1, 0, L.stream));
-    HIPCHK(launch_k2(gs, p->k, fp, 1, gs.B * gs.P, L.stream));      // PC rows (b, m) -> L.rdm
-    HIPCHK(launch_mtd_cols(gs, p->k, L.rdm, p->d_aux, L.stream));  // S7 over pulses
-    HIPCHK(hipStreamSynchronize(L.stream));
-    if (pc_out && (rc = rdm_to_matlab(p, L.rdm, pc_out))) return rc;
+    if (pc_out && (rc = rdm_to_matlab(p, p->lanes[0].rdm, pc_out))) return rc;
     if (mtd_out && (rc = rdm_to_matlab(p, p->d_aux, mtd_out))) return rc;
     return RSP_OK;
 }
@@ -1030,32 +1179,135 @@ int32_t rsp_process_stage2(rsp_plan* p, const void* iq, int32_t dtype, double* m
 int32_t rsp_process_stage2_gated(rsp_plan* p, const void* iq, int32_t dtype, int32_t n_gated, const int32_t* cols,
                                  double* mtd_out, double* pc_out) {
     if (!p || !iq) return fail(RSP_ERR_INVALID, "null argument");
-    if (dtype != RSP_C64 && dtype != RSP_C128) return fail(RSP_ERR_INVALID, "unknown dtype %d", dtype);
-    static const int32_t kRefCols[6] = {83, 310, 311, 1033, 1034, 3486};   // main_simulate_echoes_with_array_v2.m:257-264
-    const int32_t* c = cols ? cols : kRefCols;
-    const int P = p->g.P, N = p->g.N, B = p->g.B;
-    int total = 0;
-    for (int k = 0; k < 3; ++k) {
-        if (c[2 * k] < 1 || c[2 * k + 1] < c[2 * k] || c[2 * k + 1] > N)
-            return fail(RSP_ERR_INVALID, "gate columns %d..%d of segment %d outside the %d-sample PRT", c[2 * k],
-                        c[2 * k + 1], k, N);
-        if (k > 0 && c[2 * k] <= c[2 * k - 1])   // ascending and disjoint, like v2:257-264
-            return fail(RSP_ERR_INVALID, "gate columns of segment %d (%d..%d) overlap or precede segment %d (..%d)", k,
-                        c[2 * k], c[2 * k + 1], k - 1, c[2 * k - 1]);
-        total += c[2 * k + 1] - c[2 * k] + 1;
-    }
-    if (total != n_gated) return fail(RSP_ERR_INVALID, "gated input has %d columns, the gate columns cover %d", n_gated, total);
-    // put the gated columns back at their PRT positions (zeros elsewhere): [P x N x B]
-    const size_t es = dtype == RSP_C128 ? 16 : 8, colb = (size_t)P * es;
-    std::vector<unsigned char> full((size_t)N * B * colb, 0);
-    const unsigned char* src = static_cast<const unsigned char*>(iq);
-    for (int b = 0; b < B; ++b) {
-        int ng = 0;
-        for (int k = 0; k < 3; ++k)
-            for (int col = c[2 * k] - 1; col < c[2 * k + 1]; ++col, ++ng)
-                memcpy(&full[((size_t)b * N + col) * colb], src + ((size_t)b * n_gated + ng) * colb, colb);
-    }
+    std::vector<unsigned char> full;
+    int rc = stage2_regate(p, iq, dtype, n_gated, cols, full);
+    if (rc) return rc;
     return rsp_process_stage2(p, full.data(), dtype, mtd_out, pc_out);
+}
+
+int32_t rsp_stage3_cfar_shape(rsp_plan* p, int32_t P, const int32_t* gates, const double* amp, int32_t n_maps,
+                              const rsp_stage3_cfar_params* prm, uint8_t* flags, double* threshold, rsp_stage3_hit* hits,
+                              int64_t hits_cap, int64_t* n_hits) {
+    if (!p || !gates || !amp || !prm) return fail(RSP_ERR_INVALID, "null argument");
+    if (hits_cap < 0) return fail(RSP_ERR_INVALID, "negative hits_cap");
+    S3Desc d;
+    int rc = rsp_stage3_derive(P, gates, prm, &d);   // refusals before any device work
+    if (rc || (rc = s3_check_cells(d.P, d.G, n_maps))) return rc;
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    // MATLAB column-major [P x G x n] -> [n][P][G] in the plan's precision
+    const size_t cells = (size_t)n_maps * d.P * d.G, rs = p->rsz;
+    std::vector<unsigned char> host(cells * rs);
+    for (int b = 0; b < n_maps; ++b)
+        for (int v = 0; v < d.P; ++v) {
+            const double* src = amp + (size_t)v + (size_t)d.P * d.G * b;
+            const size_t o = ((size_t)b * d.P + v) * d.G;
+            if (rs == 8) {
+                double* dst = reinterpret_cast<double*>(host.data()) + o;
+                for (int r = 0; r < d.G; ++r) dst[r] = src[(size_t)d.P * r];
+            } else {
+                float* dst = reinterpret_cast<float*>(host.data()) + o;
+                for (int r = 0; r < d.G; ++r) dst[r] = (float)src[(size_t)d.P * r];
+            }
+        }
+    if ((rc = s3_reserve(p->s3_in, cells * rs))) return rc;
+    HIPCHK(hipMemcpy(p->s3_in.p, host.data(), cells * rs, hipMemcpyHostToDevice));
+    const S3Out o{nullptr, flags, threshold, hits, hits_cap, n_hits};
+    return s3_run(p, d, false, p->s3_in.p, n_maps, o);
+}
+
+int32_t rsp_stage3_cfar(rsp_plan* p, const double* amp, int32_t n_maps, const rsp_stage3_cfar_params* prm, uint8_t* flags,
+                        double* threshold, rsp_stage3_hit* hits, int64_t hits_cap, int64_t* n_hits) {
+    if (!p) return fail(RSP_ERR_INVALID, "null argument");
+    return rsp_stage3_cfar_shape(p, p->g.P, p->gates, amp, n_maps, prm, flags, threshold, hits, hits_cap, n_hits);
+}
+
+int32_t rsp_process_stage2_cfar(rsp_plan* p, const void* iq, int32_t dtype, const rsp_stage3_cfar_params* prm,
+                                double* mtd_out, double* amp_out, uint8_t* flags, double* threshold, rsp_stage3_hit* hits,
+                                int64_t hits_cap, int64_t* n_hits) {
+    if (!p || !iq || !prm) return fail(RSP_ERR_INVALID, "null argument");
+    if (hits_cap < 0) return fail(RSP_ERR_INVALID, "negative hits_cap");
+    const S3Out o{amp_out, flags, threshold, hits, hits_cap, n_hits};
+    return s3_fused(p, iq, dtype, prm, mtd_out, o);
+}
+
+int32_t rsp_process_stage2_gated_cfar(rsp_plan* p, const void* iq, int32_t dtype, int32_t n_gated, const int32_t* cols,
+                                      const rsp_stage3_cfar_params* prm, double* mtd_out, double* amp_out, uint8_t* flags,
+                                      double* threshold, rsp_stage3_hit* hits, int64_t hits_cap, int64_t* n_hits) {
+    if (!p || !iq || !prm) return fail(RSP_ERR_INVALID, "null argument");
+    if (hits_cap < 0) return fail(RSP_ERR_INVALID, "negative hits_cap");
+    S3Desc d;
+    int rc = rsp_stage3_derive(p->g.P, p->gates, prm, &d);   // before the re-insertion's work too
+    if (rc) return rc;
+    std::vector<unsigned char> full;
+    if ((rc = stage2_regate(p, iq, dtype, n_gated, cols, full))) return rc;
+    const S3Out o{amp_out, flags, threshold, hits, hits_cap, n_hits};
+    return s3_fused(p, full.data(), dtype, prm, mtd_out, o);
+}
+
+int32_t rsp_profile_stage3(rsp_plan* p, const rsp_stage3_cfar_params* prm, int32_t iters, float* ms_out, int64_t* bytes_out) {
+    if (!p || !prm || iters < 1) return fail(RSP_ERR_INVALID, "bad argument");
+    S3Desc d;
+    int rc = rsp_stage3_derive(p->g.P, p->gates, prm, &d);
+    if (rc || (rc = s3_check_cells(d.P, d.G, p->g.B))) return rc;
+    if (!p->aux_valid) return fail(RSP_ERR_INVALID, "no stage-2 result on the device: call rsp_process_stage2 first");
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    Lane& L = p->lanes[0];
+    const int B = p->g.B;
+    const size_t cells = (size_t)B * d.P * d.G, rs = p->rsz;
+    if ((rc = s3_reserve(p->s3_amp, cells * 8)) || (rc = s3_reserve(p->s3_thr, cells * 8)) ||
+        (rc = s3_reserve(p->s3_flags, cells)) || (rc = s3_reserve(p->s3_count, 16)) || (rc = s3_reserve(p->s3_in, cells * rs)) ||
+        (rc = s3_reserve(p->s3_hits, sizeof(rsp_stage3_hit) * std::min<size_t>(cells, 65536))))
+        return rc;
+    double* amp = (double*)p->s3_amp.p;
+    double* thr = (double*)p->s3_thr.p;
+    uint8_t* fl = (uint8_t*)p->s3_flags.p;
+    rsp_stage3_hit* hits = (rsp_stage3_hit*)p->s3_hits.p;
+    int* cnt = (int*)p->s3_count.p;
+    const int cap = (int)std::min<size_t>(p->s3_hits.cap / sizeof(rsp_stage3_hit), (size_t)INT32_MAX);
+    {   // the real form's input: the magnitudes the complex form writes, in the plan's precision
+        HIPCHK(hipMemsetAsync(cnt, 0, 4, L.stream));
+        HIPCHK(launch_s3(d, p->g.prec, true, p->d_aux, B, amp, nullptr, nullptr, nullptr, cnt, 0, L.stream));
+        HIPCHK(hipStreamSynchronize(L.stream));
+        std::vector<double> a(cells);
+        HIPCHK(hipMemcpy(a.data(), amp, cells * 8, hipMemcpyDeviceToHost));
+        if (rs == 8) {
+            HIPCHK(hipMemcpy(p->s3_in.p, a.data(), cells * 8, hipMemcpyHostToDevice));
+        } else {
+            std::vector<float> f(a.begin(), a.end());
+            HIPCHK(hipMemcpy(p->s3_in.p, f.data(), cells * 4, hipMemcpyHostToDevice));
+        }
+    }
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    for (int s = 0; s < 3; ++s) {
+        auto run = [&]() -> hipError_t {
+            hipError_t e = hipMemsetAsync(cnt, 0, 4, L.stream);
+            if (e != hipSuccess) return e;
+            if (s == 0) return launch_s3(d, p->g.prec, false, p->s3_in.p, B, nullptr, thr, fl, nullptr, cnt, 0, L.stream);
+            if (s == 1) return launch_s3(d, p->g.prec, true, p->d_aux, B, amp, thr, fl, nullptr, cnt, 0, L.stream);
+            return launch_s3(d, p->g.prec, true, p->d_aux, B, nullptr, nullptr, nullptr, hits, cnt, cap, L.stream);
+        };
+        HIPCHK(run());
+        HIPCHK(hipEventRecord(e0, L.stream));
+        for (int i = 0; i < iters; ++i) HIPCHK(run());
+        HIPCHK(hipEventRecord(e1, L.stream));
+        HIPCHK(hipEventSynchronize(e1));
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+        if (ms_out) ms_out[s] = ms / iters;
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (bytes_out) {   // every cell read once (the halo re-reads are cache hits), every output cell written once
+        const int64_t n = (int64_t)cells;
+        bytes_out[0] = n * ((int64_t)rs + 8 + 1);
+        bytes_out[1] = n * ((int64_t)p->esz + 8 + 8 + 1);
+        bytes_out[2] = n * (int64_t)p->esz;
+    }
+    return RSP_OK;
 }
 
 int32_t rsp_profile_stages(rsp_plan* p, const void* const* d_cubes, int32_t n_cubes, int32_t iters, float* ms_out,

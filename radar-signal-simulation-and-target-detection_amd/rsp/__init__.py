@@ -19,7 +19,8 @@ import hashlib
 import numpy as np
 
 from .config import (named_config, make_config, default_cfar_params, default_cluster_params,
-                     v8_2_targets, evolve_targets, V8_FIR, stage2_config, debug_v3_config)
+                     v8_2_targets, evolve_targets, V8_FIR, stage2_config, debug_v3_config,
+                     debug_v2_cfar_config)
 from .precompute import precompute
 from .plan import Plan, process_targets_multi
 from ._abi import RspError
@@ -120,3 +121,25 @@ def process_stage2_mtd(iq_data, angle, config, precomputed_data=None, gate_cols=
     if iq.shape[1] == p.N:
         return p.process_stage2(iq)
     return p.process_stage2(iq, gate_cols=gate_cols if gate_cols is not None else REFERENCE_GATE_COLS)
+
+
+def local_execute_cfar(mtd_amplitude_map, cfar_params, config, device=0, precision='c128'):
+    """debug_simulated_data_processing_v2.m:419 -- ``[cfar_flag, threshold_matrix] =
+    local_execute_cfar(mtd_amplitude_map, cfar_params, config)``: the stage-3 range CFAR the
+    reference runs on ``abs(MTD_results)`` (:209-213), per pulse segment, with the zero-velocity
+    notch, greatest-of / smallest-of selection, the opposite window at a segment's edges and the
+    ``>=`` test (include/rsp.h restates it).
+
+    ``mtd_amplitude_map`` is real [P, G] or [P, G, B]; ``cfar_params`` has the reference's fields
+    refCells_R, saveCells_R, T_CFAR, CFARmethod_R, MTD_0v_num (None: ``config['cfar']``, which is
+    what the reference's executeCFAR_2D reads; config.debug_v2_cfar_config builds the script's);
+    the segment lengths are point_prt(2:3) of ``config`` (through config.stage2_config).  Returns
+    float64 arrays of the input's shape, as MATLAB does.  'c128' computes in double like MATLAB,
+    'c64' in single (thresholds widened to double)."""
+    if cfar_params is None:
+        cfar_params = config['cfar']
+    config = stage2_config(config)
+    segs = config['Sig_Config']['point_prt_segments']
+    p = _plan_for(config, default_cfar_params(), default_cluster_params(), _stage2_precompute(config), device, precision)
+    r = p.stage3_cfar(mtd_amplitude_map, cfar_params, segments=segs, want_hits=False)
+    return r['flags'].astype(np.float64), r['threshold']

@@ -86,6 +86,22 @@ class K3Tiling(ct.Structure):
                 ('n_tiles', ct.c_int32), ('n_bands', ct.c_int32), ('VB', ct.c_int32), ('rows', ct.c_int32)]
 
 
+class Stage3CfarParams(ct.Structure):
+    _fields_ = [('refCells_R', ct.c_int32), ('saveCells_R', ct.c_int32), ('CFARmethod_R', ct.c_int32),
+                ('MTD_0v_num', ct.c_int32), ('T_CFAR', ct.c_double)]
+
+
+class Stage3Hit(ct.Structure):
+    _fields_ = [('v_idx', ct.c_int32), ('r_idx', ct.c_int32), ('beam_idx', ct.c_int32), ('reserved', ct.c_int32),
+                ('amp', ct.c_double), ('threshold', ct.c_double)]
+
+
+class Stage3Info(ct.Structure):
+    _fields_ = [('P', ct.c_int32), ('G', ct.c_int32), ('seg_first', ct.c_int32 * 3), ('seg_len', ct.c_int32 * 3),
+                ('notch_first', ct.c_int32), ('notch_last', ct.c_int32), ('halo', ct.c_int32),
+                ('max_halo', ct.c_int32), ('chunk', ct.c_int32), ('rows', ct.c_int32)]
+
+
 RSP_PLAN_K1_TILED = 1
 RSP_PLAN_MONOPULSE_COMPLEX = 2
 
@@ -159,6 +175,7 @@ class MusicOut(ct.Structure):
 
 
 _P = ct.c_void_p
+_U8 = ct.POINTER(ct.c_uint8)
 PROTOTYPES = {
     'rsp_abi_version': (ct.c_int32, []),
     'rsp_last_error': (ct.c_char_p, []),
@@ -204,6 +221,20 @@ PROTOTYPES = {
     'rsp_results_rows': (ct.c_int32, [_P, _dp, ct.c_int64, ct.POINTER(ct.c_int64)]),
     'rsp_process_stage2': (ct.c_int32, [_P, _P, ct.c_int32, _dp, _dp]),
     'rsp_process_stage2_gated': (ct.c_int32, [_P, _P, ct.c_int32, ct.c_int32, ct.POINTER(ct.c_int32), _dp, _dp]),
+    'rsp_stage3_describe': (ct.c_int32, [ct.POINTER(SigConfig), ct.POINTER(Precomputed), ct.POINTER(Stage3CfarParams),
+                                         ct.POINTER(Stage3Info)]),
+    'rsp_stage3_cfar': (ct.c_int32, [_P, _dp, ct.c_int32, ct.POINTER(Stage3CfarParams), _U8, _dp,
+                                     ct.POINTER(Stage3Hit), ct.c_int64, ct.POINTER(ct.c_int64)]),
+    'rsp_stage3_cfar_shape': (ct.c_int32, [_P, ct.c_int32, ct.POINTER(ct.c_int32), _dp, ct.c_int32,
+                                           ct.POINTER(Stage3CfarParams), _U8, _dp, ct.POINTER(Stage3Hit), ct.c_int64,
+                                           ct.POINTER(ct.c_int64)]),
+    'rsp_process_stage2_cfar': (ct.c_int32, [_P, _P, ct.c_int32, ct.POINTER(Stage3CfarParams), _dp, _dp, _U8, _dp,
+                                             ct.POINTER(Stage3Hit), ct.c_int64, ct.POINTER(ct.c_int64)]),
+    'rsp_process_stage2_gated_cfar': (ct.c_int32, [_P, _P, ct.c_int32, ct.c_int32, ct.POINTER(ct.c_int32),
+                                                   ct.POINTER(Stage3CfarParams), _dp, _dp, _U8, _dp,
+                                                   ct.POINTER(Stage3Hit), ct.c_int64, ct.POINTER(ct.c_int64)]),
+    'rsp_profile_stage3': (ct.c_int32, [_P, ct.POINTER(Stage3CfarParams), ct.c_int32, ct.POINTER(ct.c_float),
+                                        ct.POINTER(ct.c_int64)]),
     'rsp_profile_stages': (ct.c_int32, [_P, ct.POINTER(_P), ct.c_int32, ct.c_int32, ct.POINTER(ct.c_float),
                                         ct.POINTER(ct.c_int64), ct.c_int32, ct.POINTER(ct.c_int32)]),
     'rsp_profile_stages_rdm': (ct.c_int32, [_P, ct.POINTER(_P), ct.c_int32, ct.POINTER(_P), ct.c_int32,

@@ -98,6 +98,22 @@ def stage2_config(config):
     return out
 
 
+def debug_v2_cfar_config(config):
+    """``config.cfar`` of debug_simulated_data_processing_v2.m:103-127, the fields the stage-3
+    range CFAR (local_execute_cfar, :419-511) reads: T_CFAR = 3, refCells_R = 5, saveCells_R = 14,
+    CFARmethod_R = 0 (greatest of), MTD_V = 3 m/s, and the zero-velocity notch half-width
+    MTD_0v_num = floor(MTD_V / deltaV) with deltaV = wavelength * (prf / prtNum) / 2 (:125-127).
+    For debug_v3_config() that is 14 (rows 153..181 of 332)."""
+    sc = config['Sig_Config']
+    prf = float(sc['prf']) if 'prf' in sc else 1.0 / float(sc['prt'])
+    wavelength = float(sc['wavelength']) if 'wavelength' in sc else float(sc.get('c', C_LIGHT)) / float(sc['fc'])
+    delta_doppler = prf / int(sc['prtNum'])
+    delta_v = wavelength * delta_doppler / 2
+    mtd_v = 3
+    return dict(T_CFAR=3.0, MTD_V=mtd_v, refCells_R=5, saveCells_R=14, T_CFAR_R=3.0, CFARmethod_R=0,
+                deltaDoppler=delta_doppler, deltaV=delta_v, MTD_0v_num=int(np.floor(mtd_v / delta_v)))
+
+
 def default_cfar_params():
     """v8:45-47."""
     return dict(refCells_V=5, guardCells_V=10, refCells_R=5, guardCells_R=10, T_CFAR=8.0, method='GOCA')

@@ -114,6 +114,36 @@ def describe_k3(config, cfar_params, cluster_params, precomputed_data, precision
     return _tiling_dict(t)
 
 
+HIT_DTYPE = np.dtype([('v_idx', np.int32), ('r_idx', np.int32), ('beam_idx', np.int32), ('reserved', np.int32),
+                      ('amp', np.float64), ('threshold', np.float64)])   # rsp_stage3_hit
+STAGE3_WANT = ('mtd', 'amp', 'flags', 'threshold', 'hits')
+
+
+def _stage3_params(cfar):
+    """rsp_stage3_cfar_params from the reference's config.cfar field names
+    (debug_simulated_data_processing_v2.m:103-127)."""
+    return _abi.Stage3CfarParams(refCells_R=int(cfar['refCells_R']), saveCells_R=int(cfar['saveCells_R']),
+                                 CFARmethod_R=int(cfar['CFARmethod_R']), MTD_0v_num=int(cfar['MTD_0v_num']),
+                                 T_CFAR=float(cfar['T_CFAR']))
+
+
+def describe_stage3(P, segments, cfar):
+    """What the stage-3 range CFAR does with a map of ``P`` Doppler rows and range segments of
+    ``segments`` = (narrow, medium, long) columns, without a device (rsp_stage3_describe):
+    ``seg_first`` (1-based) and ``seg_len`` of each segment, the notched rows ``notch`` = (first,
+    last) 1-based and clipped to 1..P, the window's ``halo`` = s + r, the kernel's ``max_halo``,
+    ``chunk`` (range cells per workgroup) and ``rows``.  Refusals raise RspError with the code and
+    message the CFAR calls give."""
+    n1, n2, n3 = (int(x) for x in segments)
+    cfg = _abi.SigConfig(prtNum=int(P))
+    pre = _abi.Precomputed(N_gate_narrow=n1, N_gate_medium=n2, N_gate_long=n3, N_total_gate=n1 + n2 + n3)
+    prm, info = _stage3_params(cfar), _abi.Stage3Info()
+    check(lib().rsp_stage3_describe(ct.byref(cfg), ct.byref(pre), ct.byref(prm), ct.byref(info)))
+    return dict(P=info.P, G=info.G, seg_first=tuple(info.seg_first), seg_len=tuple(info.seg_len),
+                notch=(info.notch_first, info.notch_last), halo=info.halo, max_halo=info.max_halo,
+                chunk=info.chunk, rows=info.rows)
+
+
 class Plan:
     """One device plan = the reference's per-frame kernel bound to fixed config/precompute.
 
@@ -268,6 +298,119 @@ class Plan:
                 raise ValueError('iq shape %r: expected (P, n, B) with P=%d B=%d' % (iq.shape, self.P, self.B))
             check(lib().rsp_process_stage2_gated(self.h, a.ctypes.data_as(ct.c_void_p), dt, iq.shape[1], cols, mo, po))
         return mtd, pc
+
+    # ---- stage-3 range CFAR of the stage-2 path ---------------------------------------------
+    @staticmethod
+    def _hits_buf(cap):
+        buf = np.zeros(max(int(cap), 1), HIT_DTYPE)
+        return buf, buf.ctypes.data_as(ct.POINTER(_abi.Stage3Hit))
+
+    def stage3_cfar(self, amp, cfar, segments=None, hits_cap=None, want_hits=True):
+        """local_execute_cfar (debug_simulated_data_processing_v2.m:419-511) on real amplitude maps
+        ``amp`` [P, G] or [P, G, n] (rsp_stage3_cfar; include/rsp.h restates the semantics).
+        ``cfar``: refCells_R, saveCells_R, T_CFAR, CFARmethod_R, MTD_0v_num.  ``segments``:
+        (narrow, medium, long) column counts of a map whose shape is not the plan's
+        (rsp_stage3_cfar_shape); None: the plan's P and gate counts.  Returns ``flags`` (uint8) and
+        ``threshold`` (float64) shaped like ``amp``, ``n_hits`` and ``hits``: a HIT_DTYPE array in
+        beam-then-find() order, all of them, or the first ``hits_cap``."""
+        a = np.asarray(amp, np.float64)
+        shape = a.shape
+        if a.ndim == 2:
+            a = a[:, :, None]
+        if a.ndim != 3:
+            raise ValueError('amp must be [P, G] or [P, G, n], got shape %r' % (shape,))
+        P, G, n = a.shape
+        if segments is None:
+            if (P, G) != (self.P, self.G):
+                raise ValueError('amp shape %r: expected (P, G) = %r (or give segments)' % (shape, (self.P, self.G)))
+        elif sum(int(x) for x in segments) != G:
+            raise ValueError('segments %r do not add up to the %d columns of amp' % (tuple(segments), G))
+        a = np.asfortranarray(a)
+        prm = _stage3_params(cfar)
+        flags = np.empty((P, G, n), np.uint8, order='F')
+        thr = np.empty((P, G, n), np.float64, order='F')
+        fp_, tp = flags.ctypes.data_as(ct.POINTER(ct.c_uint8)), _dptr(thr)
+        total = ct.c_int64()
+
+        def call(cap, hp, fp_, tp):
+            if segments is None:
+                check(lib().rsp_stage3_cfar(self.h, _dptr(a), n, ct.byref(prm), fp_, tp, hp, cap, ct.byref(total)))
+            else:
+                gates = (ct.c_int32 * 3)(*[int(x) for x in segments])
+                check(lib().rsp_stage3_cfar_shape(self.h, P, gates, _dptr(a), n, ct.byref(prm), fp_, tp, hp, cap,
+                                                  ct.byref(total)))
+
+        cap = (int(hits_cap) if hits_cap is not None else max(4096, a.size // 8)) if want_hits else 0
+        hits, hp = self._hits_buf(cap)
+        call(cap, hp if cap else None, fp_, tp)
+        if want_hits and hits_cap is None and total.value > cap:   # the whole list: once more, for the list alone
+            cap = total.value
+            hits, hp = self._hits_buf(cap)
+            call(cap, hp, None, None)
+        return dict(flags=flags.reshape(shape, order='F'), threshold=thr.reshape(shape, order='F'),
+                    n_hits=total.value, hits=hits[:min(total.value, cap)])
+
+    def process_stage2_cfar(self, iq_beams, cfar, gate_cols=None, want=STAGE3_WANT, hits_cap=None):
+        """process_stage2_mtd followed by the stage-3 range CFAR on |MTD_results| of every beam,
+        without leaving the device (rsp_process_stage2_cfar / _gated_cfar).  ``iq_beams`` and
+        ``gate_cols`` as ``process_stage2``; ``cfar`` as ``stage3_cfar``.  ``want`` names the
+        outputs to bring back: 'mtd' (complex [P, G, B]), 'amp' (the map that was tested), 'flags'
+        (uint8), 'threshold', 'hits' (HIT_DTYPE array, beam then find() order; with ``hits_cap``
+        its first entries); ``n_hits`` always.  A call that wants the hits alone downloads nothing
+        else."""
+        want = set(want)
+        if not want <= set(STAGE3_WANT):
+            raise ValueError('want: unknown output(s) %r' % (sorted(want - set(STAGE3_WANT)),))
+        iq = np.asarray(iq_beams)
+        if iq.dtype == np.complex64:
+            a, dt = np.asfortranarray(iq), _abi.RSP_C64
+        else:
+            a, dt = np.asfortranarray(iq, np.complex128), _abi.RSP_C128
+        shp = (self.P, self.G, self.B)
+        if gate_cols is None and iq.shape != (self.P, self.N, self.B):
+            raise ValueError('iq shape %r != (P, N, B) = %r' % (iq.shape, (self.P, self.N, self.B)))
+        if gate_cols is not None and (iq.ndim != 3 or iq.shape[0] != self.P or iq.shape[2] != self.B):
+            raise ValueError('iq shape %r: expected (P, n, B) with P=%d B=%d' % (iq.shape, self.P, self.B))
+        prm = _stage3_params(cfar)
+        res, ptr = {}, {}
+        for name, dtype in (('mtd', np.complex128), ('amp', np.float64), ('flags', np.uint8), ('threshold', np.float64)):
+            if name in want:
+                res[name] = np.empty(shp, dtype, order='F')
+                ptr[name] = res[name].ctypes.data_as(ct.POINTER(ct.c_uint8 if name == 'flags' else ct.c_double))
+            else:
+                ptr[name] = None
+        total = ct.c_int64()
+        iqp = a.ctypes.data_as(ct.c_void_p)
+
+        def call(cap, hp, ptr):
+            tail = (ct.byref(prm), ptr['mtd'], ptr['amp'], ptr['flags'], ptr['threshold'], hp, cap, ct.byref(total))
+            if gate_cols is None:
+                check(lib().rsp_process_stage2_cfar(self.h, iqp, dt, *tail))
+            else:
+                cols = (ct.c_int32 * 6)(*[int(x) for fl in gate_cols for x in fl])
+                check(lib().rsp_process_stage2_gated_cfar(self.h, iqp, dt, iq.shape[1], cols, *tail))
+
+        cap = (int(hits_cap) if hits_cap is not None else max(4096, self.P * self.G * self.B // 8)) if 'hits' in want else 0
+        hits, hp = self._hits_buf(cap)
+        call(cap, hp if cap else None, ptr)
+        if 'hits' in want and hits_cap is None and total.value > cap:
+            cap = total.value
+            hits, hp = self._hits_buf(cap)
+            call(cap, hp, dict.fromkeys(ptr))
+        res['n_hits'] = total.value
+        if 'hits' in want:
+            res['hits'] = hits[:min(total.value, cap)]
+        return res
+
+    def profile_stage3(self, cfar, iters=20):
+        """HIP-event time of k_s3_cfar over the B beams of the plan's last stage-2 result
+        (rsp_profile_stage3): {'real': (ms, bytes), 'fused_all': ..., 'fused_hits': ...} -- the
+        real-amplitude form writing flags and thresholds, the complex form writing amplitudes,
+        flags and thresholds, and the complex form with the hit list alone."""
+        prm = _stage3_params(cfar)
+        ms, by = (ct.c_float * 3)(), (ct.c_int64 * 3)()
+        check(lib().rsp_profile_stage3(self.h, ct.byref(prm), int(iters), ms, by))
+        return {k: (ms[i], by[i]) for i, k in enumerate(('real', 'fused_all', 'fused_hits'))}
 
     # ---- device-resident queue -------------------------------------------------------------
     def device_alloc(self, nbytes):
