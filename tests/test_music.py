@@ -16,6 +16,8 @@ Complex single (precision 'c64': f32 MFMA covariance, one-wave fp32 eigensolver)
     0.02 dB; peaks the same except that a peak whose oracle height is within 0.02 dB of another
     candidate may trade places with it.
 Parity beyond the oracle is unpinned: the reference holds no MUSIC fixtures and MATLAB is absent.
+The rest of the plan's envelope (N = 2..63, K mod 4, M = 1..8, S = 3..4096, plateaus, batch position)
+is pinned by tests/test_music_shapes.py, to the same tolerances.
 """
 import numpy as np
 import pytest
