@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "rsp_geometry.h"
+#include "rsp_music_geometry.h"
 
 #define RSP_LANES 4          // max streams of the throughput queue (batches in flight)
 #define RSP_NLANES 3         // streams the throughput queue uses (<= RSP_LANES)
@@ -98,3 +99,9 @@ hipError_t launch_s3(const S3Desc& d, int prec, bool cplx, const void* in, int n
 // Queue read-back: count record + the detections of nf frames (device stride dcap + 1 records) into
 // mapped pinned host memory (stride hcap + 1), only the records that exist.
 hipError_t launch_dets_to_host(const void* dets, int dcap, void* host, int hcap, int nf, hipStream_t s);
+// MUSIC (rsp_music.hip): one stage (MusicStage) of a call's route over n_inst instances, and the
+// snapshot synthesis.  buf: the plan's device buffers by MusicBuf; dX: snapshots in the plan's precision.
+hipError_t launch_music_stage(int stage, const MusicDesc& d, const MusicRoute& r, void* const* buf, const void* dX,
+                              int n_inst, hipStream_t s);
+hipError_t launch_music_synth(const MusicDesc& d, const MusicSynth& sy, void* const* buf, int n_inst, int inst0,
+                              uint64_t seed, void* dX, hipStream_t s);

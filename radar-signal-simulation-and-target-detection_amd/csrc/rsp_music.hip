@@ -14,24 +14,17 @@
 //
 // Planar arrays (MUSIC_2D.m, rsp_music_create_2d; complex double): the same covariance, then
 // k_music_sub64 (signal subspace), k_music_scan2d (the theta x phi scan) and k_music_peaks2d
-// (P_dB, imregionalmax, the M largest) -- see the section before the host code.
+// (P_dB, imregionalmax, the M largest) -- see the section before the launchers.  The plan and the
+// C-ABI are rsp_music_plan.cpp's, every host decision rsp_music_geometry.{h,cpp}'s.
 #include "rsp.h"
 #include "rsp_internal.h"
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
+#include <type_traits>
 
-int rsp_set_error(int code, const char* fmt, ...);   // rsp_plan.cpp
-
-#define MU_NMAX 64
-#define MU_MMAX 8
+// MU_NMAX, MU_MMAX, MU_SCAN_MAX, M2_SMAX, the peaks row (MU_PK_*) and the LDS formulae: rsp_music_geometry.h
 #define MU_THREADS 256
 #define MU_LDA (MU_NMAX + 1)   // LDS row stride (complex) of A and V: column walks hit 2 banks apart
-#define MU_SCAN_MAX 4096
 #define MU_TAG_SRC 0x4D555341u     // 'MUSA' (oracle/music.py TAG_SRC)
 #define MU_TAG_NOISE 0x4D55534Eu   // 'MUSN' (oracle/music.py TAG_NOISE)
 
@@ -287,11 +280,6 @@ __device__ __forceinline__ int wmin_i(int v) {
 
 #define MU_ITER 3            // inverse-iteration solves per signal vector
 #define MU_SPW (MU_SCAN_MAX / 64)
-
-__host__ __device__ constexpr size_t mu_eig_lds_bytes(int M) {
-    return (size_t)MU_NMAX * MU_NMAX * 8 + MU_NMAX * 8 + 4 * MU_NMAX * 4 + (size_t)5 * M * MU_NMAX * 4 +
-           (size_t)M * MU_NMAX * 8 + MU_NMAX * 16;
-}
 
 template <int M>   // signal subspace dimension (compile time: the M-vector loops unroll exactly)
 __global__ __launch_bounds__(64) void k_music_eig(int N, int S, const float2* __restrict__ R,
@@ -585,7 +573,7 @@ __global__ __launch_bounds__(64) void k_music_eig(int N, int S, const float2* __
         if (pk) pkm |= 1ull << t;
         npk += __popcll(__builtin_amdgcn_ballot_w64(pk));
     }
-    int* po = peaks_out + (size_t)blockIdx.x * (MU_MMAX + 1);
+    int* po = peaks_out + (size_t)blockIdx.x * MU_PK_ROW;
     if (lane == 0) po[0] = npk;
     for (int r = 0; r < MU_MMAX; ++r) {
         int sel = 0;
@@ -794,15 +782,7 @@ __global__ __launch_bounds__(MU_THREADS, 2) void k_music_cov64(int N, int K, con
 #ifndef ME_WPS
 #define ME_WPS 4     // waves per SIMD the register budget is sized for (4 instances per CU)
 #endif
-#define ME_VW 68                         // padded length of a v / w buffer
-#define ME_PX(j) ((j) + ((j) >> 4))      // row j's slot in it
-// the inverse iteration's [5][64][M] LU / y array; the back-transform stages a wave's 16
-// reflectors ([16][ME_VW] complex) in the same space once the vectors have left it
-__host__ __device__ constexpr int me_lu_doubles(int M) { return 5 * 64 * M > 32 * ME_VW ? 5 * 64 * M : 32 * ME_VW; }
-__host__ __device__ constexpr size_t me_lds_bytes(int M, int S) {
-    return (size_t)4 * ME_VW * 16 + 64 * 16 + 8 * 16 + 3 * 68 * 8 + 64 * 8 + (size_t)me_lu_doubles(M) * 8 + (size_t)M * 64 * 16 +
-           ((size_t)S + 8) * 8 + 8 * 16;
-}
+#define ME_PX(j) ((j) + ((j) >> 4))      // row j's slot in a v / w buffer (ME_VW)
 
 // ---- Fast path of a peaks-only call (the caller reads no eigenvalues, M <= 4): the signal
 // subspace span{q_1..q_M} of R -- all that den(s) = |a - Q_s Q_s^H a|^2 needs (MUSIC_1D.m:31-37)
@@ -1484,7 +1464,7 @@ __device__ __forceinline__ void me_eig_body(int N, int S, int neig, double spec_
     if constexpr (SUB) {   // Q_s (rows >= n are zero on both paths) and the path taken; the scan is k_music_scan2d's
         double2* __restrict__ qo = qs_out + (size_t)blockIdx.x * M * 64;
         for (int e = t; e < M * 64; e += ME_THREADS) qo[e] = Qs[e];
-        if (t == 0 && M < MU_MMAX) peaks_out[(size_t)blockIdx.x * (MU_MMAX + 1) + MU_MMAX] = fast ? 1 : 0;
+        if (t == 0 && M < MU_MMAX) peaks_out[(size_t)blockIdx.x * MU_PK_ROW + MU_PK_FAST] = fast ? 1 : 0;
         return;
     }
     if (!have_den) pmax = den_pmax();
@@ -1514,7 +1494,7 @@ __device__ __forceinline__ void me_eig_body(int N, int S, int neig, double spec_
     npk = (int)wsumd((double)npk);
     if (lane == 0) ired[w] = npk;
     __syncthreads();
-    int* po = peaks_out + (size_t)blockIdx.x * (MU_MMAX + 1);
+    int* po = peaks_out + (size_t)blockIdx.x * MU_PK_ROW;
     if (t == 0) {
         po[0] = (ired[0] + ired[1]) + (ired[2] + ired[3]);
     }
@@ -1551,7 +1531,7 @@ __device__ __forceinline__ void me_eig_body(int N, int S, int neig, double spec_
     }
     if (t == 0) {
         for (int rk = M; rk < MU_MMAX; ++rk) po[1 + rk] = 0;
-        if (M < MU_MMAX) po[MU_MMAX] = fast ? 1 : 0;   // the slot past the M peaks: which path ran (rsp_music_fast_count)
+        if (M < MU_MMAX) po[MU_PK_FAST] = fast ? 1 : 0;   // the slot past the M peaks: which path ran (rsp_music_fast_count)
     }
     ME_STAMP(6);
 #undef ME_STAMP
@@ -1667,7 +1647,6 @@ __global__ __launch_bounds__(M2_THREADS) void k_music_scan2d(int nx, int ny, int
 // Then n_peaks = the mask's pixel count and the M largest
 // by value, ties to the lower linear index (find order + stable sort, :120-124), as 1-based
 // linear indices r + n_theta (c - 1) (sub2ind, :123).
-#define M2_SMAX 65536
 __global__ __launch_bounds__(M2_THREADS) void k_music_peaks2d(int nt, int np, int M, double* spec,
                                                             int* __restrict__ peaks_out) {
     __shared__ unsigned mk[2][M2_SMAX / 32];
@@ -1752,7 +1731,7 @@ __global__ __launch_bounds__(M2_THREADS) void k_music_peaks2d(int nt, int np, in
     for (int wd = t; wd < nw; wd += M2_THREADS) npk += __popc(mf[wd]);
     if (npk) atomicAdd(&cnt, npk);
     __syncthreads();
-    int* po = peaks_out + (size_t)blockIdx.x * (MU_MMAX + 1);
+    int* po = peaks_out + (size_t)blockIdx.x * MU_PK_ROW;
     if (t == 0) po[0] = cnt;
     for (int rk = 0; rk < M; ++rk) {
         double bv = -1.0e300;
@@ -1793,590 +1772,69 @@ __global__ __launch_bounds__(M2_THREADS) void k_music_peaks2d(int nt, int np, in
 }  // namespace
 
 // =======================================================================================
-// Host side: plan + C-ABI (include/rsp.h, MUSIC section)
+// Launchers (rsp_internal.h).  The route (rsp_music_geometry.h) decides; these only dispatch.
 // =======================================================================================
-struct rsp_music_plan {
-    int device = 0;
-    int N = 0, K = 0, M = 0, S = 0, Spad = 0, max_batch = 0;
-    bool f64 = true;              // RSP_C128 (MATLAB's complex double, default) or RSP_C64
-    size_t xsz = 16;              // bytes of one snapshot sample
-    double dl = 0.0;
-    hipStream_t stream = nullptr;
-    void* d_S1T = nullptr;        // steering table [64][Spad] (float2 / double2), zero rows for c >= N
-    void* d_R = nullptr;          // [max_batch][64][64] complex
-    void* d_X = nullptr;          // host-path staging [max_batch][K][N] (lazy)
-    void* d_spec = nullptr;       // [max_batch][S] float / double
-    void* d_eig = nullptr;        // [max_batch][N] float / double
-    int* d_peaks = nullptr;       // [max_batch][MU_MMAX + 1]
-    double2* d_src = nullptr;     // synthesis: source steering [MU_MMAX][N]
-    double* d_amp = nullptr;      // [MU_MMAX]
-    unsigned long long* d_trace = nullptr;   // RSP_MUSIC_TRACE: [max_batch][8] phase stamps (f32 eig)
-    hipEvent_t ev[5] = {};
-    int last_inst = 0;            // instances of the last eig launch (rsp_music_fast_count)
-    // planar-array plans (rsp_music_create_2d): N = nx ny, S = n_theta n_phi, no S1T
-    bool planar = false;
-    int nx = 0, ny = 0, n_theta = 0, n_phi = 0;
-    double dxl = 0.0, dyl = 0.0;
-    double2* d_exy = nullptr;     // [S][2]: (ex, ey) of grid point r + n_theta c (k_music_scan2d)
-    double2* d_qs = nullptr;      // [max_batch][M][64] signal subspace (k_music_sub64)
-};
-
-namespace {
-
-#define MUCHK(expr)                                                                                    \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess)                                                                          \
-            return rsp_set_error(RSP_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                                 __FILE__, __LINE__);                                                  \
-    } while (0)
-
-// What a launch's caller reads (music_run): only the peak indices (the block-power fast path may
-// replace the eigen-decomposition), also the pseudo-spectrum (full path: the spectrum is then the
-// eigensolver's to rounding), or also all N eigenvalues (full path, every eigenvalue).
-enum MusicWant { MU_WANT_PEAKS = 0, MU_WANT_SPECTRUM = 1, MU_WANT_EIGS = 2 };
-
-template <int MC>
-hipError_t launch_eig64(rsp_music_plan* p, int n_inst, int want) {
-    const size_t lds = me_lds_bytes(MC, p->S);
-    // neig: eigenvalues the kernel finds (all N when the caller reads them, else the M signal ones)
-    const int neig = want == MU_WANT_EIGS ? p->N : p->M;
-    // the fast-path instantiation for peaks-only and spectrum calls: a call that reads the
-    // eigenvalues never takes it, whatever N and M are (an N <= 4 plan asks for neig = N <= 4 too)
-    const bool fast = (want == MU_WANT_PEAKS || want == MU_WANT_SPECTRUM) && MC <= 4;
-    // spectrum calls keep the fast subspace only where it bounds P_dB's error by 1e-8 dB
-    const double spec_tol = want == MU_WANT_SPECTRUM ? 1e-8 : 0.0;
-    const void* kf = fast ? reinterpret_cast<const void*>(k_music_eig64<MC, true>)
-                          : reinterpret_cast<const void*>(k_music_eig64<MC, false>);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
+// f(std::integral_constant<int, M>): the one place a plan's M becomes a template argument
+template <int MC = 1, class F>
+static void mu_with_m(int M, F&& f) {
+    if constexpr (MC <= MU_MMAX) {
+        if (M == MC) f(std::integral_constant<int, MC>());
+        else mu_with_m<MC + 1>(M, f);
     }
-    if (fast)
-        hipLaunchKernelGGL((k_music_eig64<MC, true>), dim3(n_inst), dim3(ME_THREADS), lds, p->stream, p->N, p->S, neig,
-                           spec_tol, (const double2*)p->d_R, (const double2*)p->d_S1T, p->Spad, (double*)p->d_spec,
-                           (double*)p->d_eig, p->d_peaks, p->d_trace);
-    else
-        hipLaunchKernelGGL((k_music_eig64<MC, false>), dim3(n_inst), dim3(ME_THREADS), lds, p->stream, p->N, p->S,
-                           neig, 0.0, (const double2*)p->d_R, (const double2*)p->d_S1T, p->Spad, (double*)p->d_spec,
-                           (double*)p->d_eig, p->d_peaks, p->d_trace);
-    return hipGetLastError();
 }
 
-// want (MusicWant): MU_WANT_EIGS computes every eigenvalue (the caller reads them); otherwise only
-// the M signal eigenvalues the vectors and the spectrum need (complex double), and MU_WANT_PEAKS
-// allows the fast path
-int music_run(rsp_music_plan* p, const void* dX, int n_inst, bool timed, float* ms, int want) {
-    if (n_inst < 1 || n_inst > p->max_batch)
-        return rsp_set_error(RSP_ERR_INVALID, "n_inst %d outside 1..max_batch %d", n_inst, p->max_batch);
-    MUCHK(hipSetDevice(p->device));
-    if (timed) MUCHK(hipEventRecord(p->ev[0], p->stream));
-    if (p->f64)
-        hipLaunchKernelGGL(k_music_cov64, dim3(n_inst), dim3(MU_THREADS), 0, p->stream, p->N, p->K,
-                           (const double2*)dX, (double2*)p->d_R);
-    else if (p->N % 4 == 0)
-        hipLaunchKernelGGL(k_music_cov<true>, dim3(n_inst), dim3(MU_THREADS), 0, p->stream, p->N, p->K,
-                           (const float2*)dX, (float2*)p->d_R);
-    else
-        hipLaunchKernelGGL(k_music_cov<false>, dim3(n_inst), dim3(MU_THREADS), 0, p->stream, p->N, p->K,
-                           (const float2*)dX, (float2*)p->d_R);
-    MUCHK(hipGetLastError());
-    if (timed) MUCHK(hipEventRecord(p->ev[1], p->stream));
-    p->last_inst = n_inst;
-    if (p->f64) {
-        switch (p->M) {
-#define MU_EIG64(MC) \
-    case MC: MUCHK(launch_eig64<MC>(p, n_inst, want)); break;
-            MU_EIG64(1) MU_EIG64(2) MU_EIG64(3) MU_EIG64(4) MU_EIG64(5) MU_EIG64(6) MU_EIG64(7) MU_EIG64(8)
-#undef MU_EIG64
+hipError_t launch_music_stage(int stage, const MusicDesc& d, const MusicRoute& r, void* const* buf, const void* dX,
+                              int n_inst, hipStream_t s) {
+    const dim3 grid(n_inst);
+    int* peaks = (int*)buf[MB_PEAKS];
+    unsigned long long* trace = (unsigned long long*)buf[MB_TRACE];
+    hipError_t e = hipSuccess;
+    if (stage == MU_ST_COV) {
+        if (r.cov == MU_COV_F64) {
+            hipLaunchKernelGGL(k_music_cov64, grid, dim3(MU_THREADS), 0, s, d.N, d.K, (const double2*)dX, (double2*)buf[MB_R]);
+        } else {
+            auto k = r.cov == MU_COV_F32_VEC4 ? k_music_cov<true> : k_music_cov<false>;
+            hipLaunchKernelGGL(k, grid, dim3(MU_THREADS), 0, s, d.N, d.K, (const float2*)dX, (float2*)buf[MB_R]);
         }
-    } else {
-        switch (p->M) {
-#define MU_EIG(MC)                                                                                               \
-    case MC:                                                                                                     \
-        hipLaunchKernelGGL(k_music_eig<MC>, dim3(n_inst), dim3(64), mu_eig_lds_bytes(MC), p->stream, p->N, p->S, \
-                           (const float2*)p->d_R, (const float2*)p->d_S1T, p->Spad, (float*)p->d_spec,            \
-                           (float*)p->d_eig, p->d_peaks, p->d_trace);                                             \
-        break;
-            MU_EIG(1) MU_EIG(2) MU_EIG(3) MU_EIG(4) MU_EIG(5) MU_EIG(6) MU_EIG(7) MU_EIG(8)
-#undef MU_EIG
-        }
-    }
-    MUCHK(hipGetLastError());
-    if (timed) {
-        MUCHK(hipEventRecord(p->ev[2], p->stream));
-        MUCHK(hipEventSynchronize(p->ev[2]));
-        MUCHK(hipEventElapsedTime(&ms[0], p->ev[0], p->ev[1]));
-        MUCHK(hipEventElapsedTime(&ms[1], p->ev[1], p->ev[2]));
-    }
-    return RSP_OK;
-}
-
-// The planar-array path (MUSIC_2D.m:52-124): covariance, signal subspace, scan, dB + peaks.  A
-// peaks-only call (M <= 4) may keep the block-power subspace; a call that reads the spectrum or
-// the eigenvalues runs the full eigensolver (the fast path's 1e-12 subspace bound is turned into
-// a P_dB bound from den_min inside k_music_eig64 only, and the 2-D scan does not live there).
-template <int MC>
-hipError_t launch_planar(rsp_music_plan* p, int n_inst, int want, bool timed) {
-    const int neig = want == MU_WANT_EIGS ? p->N : p->M;
-    const size_t lds = me_lds_bytes(MC, 0);
-    hipError_t e;
-    if (want == MU_WANT_PEAKS && MC <= 4)
-        hipLaunchKernelGGL((k_music_sub64<MC, true>), dim3(n_inst), dim3(ME_THREADS), lds, p->stream, p->N, neig,
-                           (const double2*)p->d_R, p->d_qs, (double*)p->d_eig, p->d_peaks, p->d_trace);
-    else
-        hipLaunchKernelGGL((k_music_sub64<MC, false>), dim3(n_inst), dim3(ME_THREADS), lds, p->stream, p->N, neig,
-                           (const double2*)p->d_R, p->d_qs, (double*)p->d_eig, p->d_peaks, p->d_trace);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (timed && (e = hipEventRecord(p->ev[2], p->stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_music_scan2d<MC>, dim3((n_inst + M2_IB - 1) / M2_IB, (p->S + M2_THREADS - 1) / M2_THREADS),
-                       dim3(M2_THREADS), 0, p->stream, p->nx, p->ny, p->S, n_inst, (const double2*)p->d_exy,
-                       (const double2*)p->d_qs, (double*)p->d_spec);
-    return hipGetLastError();
-}
-
-int music_run_planar(rsp_music_plan* p, const void* dX, int n_inst, bool timed, float* ms, int want) {
-    if (n_inst < 1 || n_inst > p->max_batch)
-        return rsp_set_error(RSP_ERR_INVALID, "n_inst %d outside 1..max_batch %d", n_inst, p->max_batch);
-    MUCHK(hipSetDevice(p->device));
-    if (timed) MUCHK(hipEventRecord(p->ev[0], p->stream));
-    hipLaunchKernelGGL(k_music_cov64, dim3(n_inst), dim3(MU_THREADS), 0, p->stream, p->N, p->K, (const double2*)dX,
-                       (double2*)p->d_R);
-    MUCHK(hipGetLastError());
-    if (timed) MUCHK(hipEventRecord(p->ev[1], p->stream));
-    p->last_inst = n_inst;
-    switch (p->M) {
-#define MU_PLANAR(MC) \
-    case MC: MUCHK(launch_planar<MC>(p, n_inst, want, timed)); break;
-        MU_PLANAR(1) MU_PLANAR(2) MU_PLANAR(3) MU_PLANAR(4) MU_PLANAR(5) MU_PLANAR(6) MU_PLANAR(7) MU_PLANAR(8)
-#undef MU_PLANAR
-    }
-    if (timed) MUCHK(hipEventRecord(p->ev[3], p->stream));
-    hipLaunchKernelGGL(k_music_peaks2d, dim3(n_inst), dim3(M2_THREADS), 0, p->stream, p->n_theta, p->n_phi, p->M,
-                       (double*)p->d_spec, p->d_peaks);
-    MUCHK(hipGetLastError());
-    if (timed) {
-        MUCHK(hipEventRecord(p->ev[4], p->stream));
-        MUCHK(hipEventSynchronize(p->ev[4]));
-        for (int q = 0; q < 4; ++q) MUCHK(hipEventElapsedTime(&ms[q], p->ev[q], p->ev[q + 1]));
-    }
-    return RSP_OK;
-}
-
-// device results -> caller (double; a complex-single plan's are widened)
-int music_fetch(rsp_music_plan* p, int n_inst, rsp_music_out* out) {
-    if (!out) return RSP_OK;
-    const int N = p->N, M = p->M, S = p->S;
-    const size_t rs = p->f64 ? 8 : 4;
-    std::vector<unsigned char> spec, eig, rc;
-    if (out->spectrum_db) {
-        if (p->f64)
-            MUCHK(hipMemcpyAsync(out->spectrum_db, p->d_spec, (size_t)n_inst * S * 8, hipMemcpyDeviceToHost, p->stream));
-        else {
-            spec.resize((size_t)n_inst * S * rs);
-            MUCHK(hipMemcpyAsync(spec.data(), p->d_spec, spec.size(), hipMemcpyDeviceToHost, p->stream));
-        }
-    }
-    if (out->eigenvalues) {
-        if (p->f64)
-            MUCHK(hipMemcpyAsync(out->eigenvalues, p->d_eig, (size_t)n_inst * N * 8, hipMemcpyDeviceToHost, p->stream));
-        else {
-            eig.resize((size_t)n_inst * N * rs);
-            MUCHK(hipMemcpyAsync(eig.data(), p->d_eig, eig.size(), hipMemcpyDeviceToHost, p->stream));
-        }
-    }
-    std::vector<int> pk;
-    if (out->peak_idx || out->n_peaks) {
-        pk.resize((size_t)n_inst * (MU_MMAX + 1));
-        MUCHK(hipMemcpyAsync(pk.data(), p->d_peaks, pk.size() * sizeof(int), hipMemcpyDeviceToHost, p->stream));
-    }
-    if (out->covariance) {
-        rc.resize((size_t)n_inst * MU_NMAX * MU_NMAX * 2 * rs);
-        MUCHK(hipMemcpyAsync(rc.data(), p->d_R, rc.size(), hipMemcpyDeviceToHost, p->stream));
-    }
-    MUCHK(hipStreamSynchronize(p->stream));
-    if (!spec.empty())
-        for (size_t e = 0; e < (size_t)n_inst * S; ++e) out->spectrum_db[e] = reinterpret_cast<const float*>(spec.data())[e];
-    if (!eig.empty())
-        for (size_t e = 0; e < (size_t)n_inst * N; ++e) out->eigenvalues[e] = reinterpret_cast<const float*>(eig.data())[e];
-    for (int i = 0; i < n_inst && !pk.empty(); ++i) {
-        if (out->n_peaks) out->n_peaks[i] = pk[(size_t)i * (MU_MMAX + 1)];
-        if (out->peak_idx)
-            for (int m = 0; m < M; ++m) out->peak_idx[(size_t)i * M + m] = pk[(size_t)i * (MU_MMAX + 1) + 1 + m];
-    }
-    if (out->covariance)   // N x N column-major complex double per instance
-        for (int i = 0; i < n_inst; ++i)
-            for (int b = 0; b < N; ++b)
-                for (int a = 0; a < N; ++a) {
-                    const size_t e = (size_t)i * MU_NMAX * MU_NMAX + a + MU_NMAX * b;
-                    double* o = out->covariance + 2 * ((size_t)i * N * N + a + (size_t)N * b);
-                    if (p->f64) {
-                        const double* v = reinterpret_cast<const double*>(rc.data()) + 2 * e;
-                        o[0] = v[0];
-                        o[1] = v[1];
-                    } else {
-                        const float* v = reinterpret_cast<const float*>(rc.data()) + 2 * e;
-                        o[0] = v[0];
-                        o[1] = v[1];
-                    }
-                }
-    return RSP_OK;
-}
-
-// k_music_synth over the source steering table src [n_src][N] (the line array's or the planar one's)
-template <class SC>
-int music_synth(rsp_music_plan* p, const SC* sc, const std::vector<double2>& src, int n_inst, int inst0, uint64_t seed,
-                void* d_X) {
-    const int N = p->N, Ms = sc->n_src;
-    double amp[MU_MMAX];
-    for (int m = 0; m < MU_MMAX; ++m) amp[m] = m < Ms ? sc->amplitudes[m] : 0.0;
-    MUCHK(hipMemcpyAsync(p->d_src, src.data(), src.size() * sizeof(double2), hipMemcpyHostToDevice, p->stream));
-    MUCHK(hipMemcpyAsync(p->d_amp, amp, sizeof amp, hipMemcpyHostToDevice, p->stream));
-    const double nsc_fixed = std::sqrt(1.0 / std::pow(10.0, sc->snr_db / 10.0) / 2.0);
-    if (p->f64)
-        hipLaunchKernelGGL(k_music_synth<double2>, dim3(n_inst), dim3(MU_THREADS), 0, p->stream, N, p->K, Ms, inst0,
-                           seed, p->d_src, p->d_amp, sc->complex_sources, sc->snr_measured ? 1 : 0, sc->snr_db,
-                           nsc_fixed, (double2*)d_X);
-    else
-        hipLaunchKernelGGL(k_music_synth<float2>, dim3(n_inst), dim3(MU_THREADS), 0, p->stream, N, p->K, Ms, inst0,
-                           seed, p->d_src, p->d_amp, sc->complex_sources, sc->snr_measured ? 1 : 0, sc->snr_db,
-                           nsc_fixed, (float2*)d_X);
-    MUCHK(hipGetLastError());
-    MUCHK(hipStreamSynchronize(p->stream));   // the host staging above is stack memory
-    return RSP_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int32_t rsp_music_create_2d(const rsp_music2d_config* cfg, int32_t device, rsp_music_plan** out) {
-    if (!cfg || !out || !cfg->phi_rad || !cfg->theta_rad) return rsp_set_error(RSP_ERR_INVALID, "null argument");
-    *out = nullptr;
-    const int nx = cfg->nx, ny = cfg->ny, K = cfg->num_snapshots, M = cfg->num_sources;
-    const int np = cfg->n_phi, nt = cfg->n_theta;
-    if (nx < 1 || ny < 1 || nx > MU_NMAX || ny > MU_NMAX || nx * ny < 2 || nx * ny > MU_NMAX)
-        return rsp_set_error(RSP_ERR_UNSUPPORTED, "nx*ny = %d*%d outside 2..%d", nx, ny, MU_NMAX);
-    const int N = nx * ny;
-    if (M < 1 || M >= N || M > MU_MMAX)
-        return rsp_set_error(RSP_ERR_UNSUPPORTED, "num_sources %d outside 1..min(%d, nx*ny-1)", M, MU_MMAX);
-    if (np < 3 || np > 1024 || nt < 3 || nt > 1024 || np * nt > M2_SMAX)
-        return rsp_set_error(RSP_ERR_UNSUPPORTED, "grid n_phi %d x n_theta %d: each 3..1024, at most %d points", np, nt,
-                             M2_SMAX);
-    if (cfg->precision == RSP_C64)
-        return rsp_set_error(RSP_ERR_UNSUPPORTED, "2-D MUSIC is complex double only (precision RSP_C128)");
-    if (cfg->precision != RSP_C128)
-        return rsp_set_error(RSP_ERR_INVALID, "precision must be RSP_C128, got %d", cfg->precision);
-    if (K < 1) return rsp_set_error(RSP_ERR_INVALID, "num_snapshots %d < 1", K);
-    if (cfg->max_batch < 1) return rsp_set_error(RSP_ERR_INVALID, "max_batch %d < 1", cfg->max_batch);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return rsp_set_error(RSP_ERR_DEVICE, "HIP device %d not available (%d devices)", device, ndev);
-    rsp_music_plan* p = new rsp_music_plan();
-    p->device = device;
-    p->planar = true;
-    p->nx = nx; p->ny = ny; p->n_phi = np; p->n_theta = nt;
-    p->N = N; p->K = K; p->M = M; p->S = nt * np; p->Spad = 0;
-    p->max_batch = cfg->max_batch;
-    p->dxl = cfg->dx_over_lambda;
-    p->dyl = cfg->dy_over_lambda;
-    auto bail = [&](int rc) { rsp_music_destroy(p); return rc; };
-    if (hipSetDevice(device) != hipSuccess) return bail(rsp_set_error(RSP_ERR_DEVICE, "hipSetDevice(%d)", device));
-    if (hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess)
-        return bail(rsp_set_error(RSP_ERR_DEVICE, "hipStreamCreate failed"));
-    for (auto& e : p->ev)
-        if (hipEventCreate(&e) != hipSuccess) return bail(rsp_set_error(RSP_ERR_DEVICE, "hipEventCreate failed"));
-    const size_t B = (size_t)p->max_batch;
-    struct { void** ptr; size_t bytes; } allocs[] = {
-        {(void**)&p->d_exy, (size_t)p->S * 2 * sizeof(double2)},
-        {(void**)&p->d_qs, B * M * MU_NMAX * sizeof(double2)},
-        {&p->d_R, B * MU_NMAX * MU_NMAX * sizeof(double2)},
-        {&p->d_spec, B * p->S * sizeof(double)},
-        {&p->d_eig, B * N * sizeof(double)},
-        {(void**)&p->d_peaks, B * (MU_MMAX + 1) * sizeof(int)},
-        {(void**)&p->d_src, (size_t)MU_MMAX * MU_NMAX * sizeof(double2)},
-        {(void**)&p->d_amp, (size_t)MU_MMAX * sizeof(double)},
-    };
-    for (auto& a : allocs)
-        if (hipMalloc(a.ptr, a.bytes) != hipSuccess)
-            return bail(rsp_set_error(RSP_ERR_NOMEM, "hipMalloc(%zu bytes) failed", a.bytes));
-    // per grid point r + n_theta c (theta fastest: Theta_vec, Phi_vec of MUSIC_2D.m:82-84) the two
-    // unit steps of the separable steering vector (MUSIC_2D.m:87-89)
-    std::vector<double2> exy((size_t)p->S * 2);
-    for (int c = 0; c < np; ++c)
-        for (int r = 0; r < nt; ++r) {
-            const double ct = std::cos(cfg->theta_rad[r]);
-            const double ax = 2.0 * M_PI * p->dxl * (ct * std::cos(cfg->phi_rad[c]));
-            const double ay = 2.0 * M_PI * p->dyl * (ct * std::sin(cfg->phi_rad[c]));
-            const size_t g = (size_t)r + (size_t)nt * c;
-            exy[2 * g] = make_double2(std::cos(ax), std::sin(ax));
-            exy[2 * g + 1] = make_double2(std::cos(ay), std::sin(ay));
-        }
-    if (hipMemcpy(p->d_exy, exy.data(), exy.size() * sizeof(double2), hipMemcpyHostToDevice) != hipSuccess)
-        return bail(rsp_set_error(RSP_ERR_DEVICE, "steering upload failed"));
-#ifdef RSP_DEBUG_KNOBS
-    const char* tr = getenv("RSP_MUSIC_TRACE");
-    if (tr && atoi(tr) && hipMalloc(&p->d_trace, B * 8 * sizeof(unsigned long long)) != hipSuccess)
-        return bail(rsp_set_error(RSP_ERR_NOMEM, "trace buffer"));
-#endif
-    *out = p;
-    return RSP_OK;
-}
-
-int32_t rsp_music_synthesize_device_2d(rsp_music_plan* p, const rsp_music2d_scene* sc, int32_t n_inst, int32_t inst0,
-                                       uint64_t seed, void* d_X) {
-    if (!p || !sc || !d_X) return rsp_set_error(RSP_ERR_INVALID, "null argument");
-    if (!p->planar) return rsp_set_error(RSP_ERR_INVALID, "rsp_music_synthesize_device_2d on a line-array plan");
-    if (sc->n_src < 1 || sc->n_src > MU_MMAX)
-        return rsp_set_error(RSP_ERR_UNSUPPORTED, "n_src %d outside 1..%d", sc->n_src, MU_MMAX);
-    if (n_inst < 1) return rsp_set_error(RSP_ERR_INVALID, "n_inst %d < 1", n_inst);
-    MUCHK(hipSetDevice(p->device));
-    const int N = p->N, Ms = sc->n_src;
-    std::vector<double2> src((size_t)Ms * N);
-    for (int m = 0; m < Ms; ++m) {   // S(:, m), element iy + ny ix (MUSIC_2D.m:17-19,41-42)
-        const double ct = std::cos(sc->elev_rad[m]);
-        const double A = ct * std::cos(sc->azim_rad[m]), Bq = ct * std::sin(sc->azim_rad[m]);
-        for (int ix = 0; ix < p->nx; ++ix)
-            for (int iy = 0; iy < p->ny; ++iy) {
-                const double ph = 2.0 * M_PI * (p->dxl * ix * A + p->dyl * iy * Bq);
-                src[(size_t)m * N + iy + p->ny * ix] = make_double2(std::cos(ph), std::sin(ph));
+    } else if (stage == MU_ST_EIG) {
+        mu_with_m(d.M, [&](auto mc) {
+            constexpr int MC = decltype(mc)::value;
+            if (r.eig == MU_EIG_F32) {
+                hipLaunchKernelGGL(k_music_eig<MC>, grid, dim3(64), r.lds, s, d.N, d.S, (const float2*)buf[MB_R],
+                                   (const float2*)buf[MB_S1T], d.Spad, (float*)buf[MB_SPEC], (float*)buf[MB_EIG], peaks, trace);
+            } else if (r.eig == MU_EIG_F64) {
+                auto k = r.fast ? k_music_eig64<MC, true> : k_music_eig64<MC, false>;
+                if (r.raise_lds)
+                    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds);
+                if (e == hipSuccess)
+                    hipLaunchKernelGGL(k, grid, dim3(ME_THREADS), r.lds, s, d.N, d.S, r.neig, r.spec_tol, (const double2*)buf[MB_R],
+                                       (const double2*)buf[MB_S1T], d.Spad, (double*)buf[MB_SPEC], (double*)buf[MB_EIG], peaks, trace);
+            } else {
+                auto k = r.fast ? k_music_sub64<MC, true> : k_music_sub64<MC, false>;
+                hipLaunchKernelGGL(k, grid, dim3(ME_THREADS), r.lds, s, d.N, r.neig, (const double2*)buf[MB_R],
+                                   (double2*)buf[MB_QS], (double*)buf[MB_EIG], peaks, trace);
             }
+        });
+    } else if (stage == MU_ST_SCAN2D) {
+        mu_with_m(d.M, [&](auto mc) {
+            hipLaunchKernelGGL(k_music_scan2d<decltype(mc)::value>,
+                               dim3((n_inst + M2_IB - 1) / M2_IB, (d.S + M2_THREADS - 1) / M2_THREADS), dim3(M2_THREADS), 0, s,
+                               d.nx, d.ny, d.S, n_inst, (const double2*)buf[MB_EXY], (const double2*)buf[MB_QS], (double*)buf[MB_SPEC]);
+        });
+    } else {
+        hipLaunchKernelGGL(k_music_peaks2d, grid, dim3(M2_THREADS), 0, s, d.n_theta, d.n_phi, d.M, (double*)buf[MB_SPEC], peaks);
     }
-    return music_synth(p, sc, src, n_inst, inst0, seed, d_X);
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
-int32_t rsp_music_profile_2d(rsp_music_plan* p, const void* d_X, int32_t n_inst, int32_t iters, int32_t what,
-                             float* ms_out) {
-    if (!p || !d_X || !ms_out || iters < 1) return rsp_set_error(RSP_ERR_INVALID, "bad argument");
-    if (!p->planar) return rsp_set_error(RSP_ERR_INVALID, "rsp_music_profile_2d on a line-array plan");
-    if (what != RSP_MUSIC_PEAKS && what != RSP_MUSIC_SPECTRUM && what != RSP_MUSIC_EIGENVALUES)
-        return rsp_set_error(RSP_ERR_INVALID, "unknown profile form %d", what);
-    const int want = what == RSP_MUSIC_EIGENVALUES ? MU_WANT_EIGS
-                   : what == RSP_MUSIC_SPECTRUM ? MU_WANT_SPECTRUM : MU_WANT_PEAKS;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int it = 0; it < iters; ++it) {
-        float ms[4];
-        int rc = music_run_planar(p, d_X, n_inst, true, ms, want);
-        if (rc) return rc;
-        for (int q = 0; q < 4; ++q) acc[q] += ms[q];
-    }
-    for (int q = 0; q < 4; ++q) ms_out[q] = (float)(acc[q] / iters);
-    return RSP_OK;
-}
-
-int32_t rsp_music_create(const rsp_music_config* cfg, int32_t device, rsp_music_plan** out) {
-    if (!cfg || !out || !cfg->scan_rad) return rsp_set_error(RSP_ERR_INVALID, "null argument");
-    *out = nullptr;
-    const int N = cfg->channel_num, K = cfg->num_snapshots, M = cfg->num_sources, S = cfg->n_scan;
-    if (N < 2 || N > MU_NMAX) return rsp_set_error(RSP_ERR_UNSUPPORTED, "channel_num %d outside 2..%d", N, MU_NMAX);
-    if (M < 1 || M >= N || M > MU_MMAX)
-        return rsp_set_error(RSP_ERR_UNSUPPORTED, "num_sources %d outside 1..min(%d, channel_num-1)", M, MU_MMAX);
-    if (K < 1) return rsp_set_error(RSP_ERR_INVALID, "num_snapshots %d < 1", K);
-    if (S < 3 || S > MU_SCAN_MAX) return rsp_set_error(RSP_ERR_UNSUPPORTED, "n_scan %d outside 3..%d", S, MU_SCAN_MAX);
-    if (cfg->max_batch < 1) return rsp_set_error(RSP_ERR_INVALID, "max_batch %d < 1", cfg->max_batch);
-    if (cfg->precision != RSP_C128 && cfg->precision != RSP_C64)
-        return rsp_set_error(RSP_ERR_INVALID, "precision must be RSP_C128 or RSP_C64, got %d", cfg->precision);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return rsp_set_error(RSP_ERR_DEVICE, "HIP device %d not available (%d devices)", device, ndev);
-    rsp_music_plan* p = new rsp_music_plan();
-    p->device = device;
-    p->N = N; p->K = K; p->M = M; p->S = S; p->Spad = (S + 7) & ~3;
-    p->max_batch = cfg->max_batch;
-    p->dl = cfg->d_over_lambda;
-    p->f64 = cfg->precision == RSP_C128;
-    p->xsz = p->f64 ? 16 : 8;
-    auto bail = [&](int rc) { rsp_music_destroy(p); return rc; };
-    if (hipSetDevice(device) != hipSuccess) return bail(rsp_set_error(RSP_ERR_DEVICE, "hipSetDevice(%d)", device));
-    if (hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess)
-        return bail(rsp_set_error(RSP_ERR_DEVICE, "hipStreamCreate failed"));
-    for (auto& e : p->ev)
-        if (hipEventCreate(&e) != hipSuccess) return bail(rsp_set_error(RSP_ERR_DEVICE, "hipEventCreate failed"));
-    const size_t B = (size_t)p->max_batch, cs = p->xsz, rs = p->xsz / 2;
-    struct { void** ptr; size_t bytes; } allocs[] = {
-        {&p->d_S1T, (size_t)MU_NMAX * p->Spad * cs},
-        {&p->d_R, B * MU_NMAX * MU_NMAX * cs},
-        {&p->d_spec, B * S * rs},
-        {&p->d_eig, B * N * rs},
-        {(void**)&p->d_peaks, B * (MU_MMAX + 1) * sizeof(int)},
-        {(void**)&p->d_src, (size_t)MU_MMAX * MU_NMAX * sizeof(double2)},
-        {(void**)&p->d_amp, (size_t)MU_MMAX * sizeof(double)},
+hipError_t launch_music_synth(const MusicDesc& d, const MusicSynth& sy, void* const* buf, int n_inst, int inst0,
+                              uint64_t seed, void* dX, hipStream_t s) {
+    auto go = [&](auto* X) {
+        hipLaunchKernelGGL(k_music_synth<std::remove_pointer_t<decltype(X)>>, dim3(n_inst), dim3(MU_THREADS), 0, s, d.N, d.K,
+                           sy.n_src, inst0, seed, (const double2*)buf[MB_SRC], (const double*)buf[MB_AMP], sy.complex_src,
+                           sy.snr_measured, sy.snr_db, sy.nsc_fixed, X);
     };
-    for (auto& a : allocs)
-        if (hipMalloc(a.ptr, a.bytes) != hipSuccess)
-            return bail(rsp_set_error(RSP_ERR_NOMEM, "hipMalloc(%zu bytes) failed", a.bytes));
-    // S1 = exp(1j k z sin(phi_list')) (MUSIC_1D.m:36) in double (rounded to float for a complex-single
-    // plan); stored transposed [channel][angle]
-    std::vector<double2> s1((size_t)MU_NMAX * p->Spad, make_double2(0.0, 0.0));
-    for (int c = 0; c < N; ++c)
-        for (int s = 0; s < S; ++s) {
-            const double ph = 2.0 * M_PI * p->dl * c * std::sin(cfg->scan_rad[s]);
-            s1[(size_t)c * p->Spad + s] = make_double2(std::cos(ph), std::sin(ph));
-        }
-    hipError_t e;
-    if (p->f64) {
-        e = hipMemcpy(p->d_S1T, s1.data(), s1.size() * sizeof(double2), hipMemcpyHostToDevice);
-    } else {
-        std::vector<float2> s1f(s1.size());
-        for (size_t i = 0; i < s1.size(); ++i) s1f[i] = make_float2((float)s1[i].x, (float)s1[i].y);
-        e = hipMemcpy(p->d_S1T, s1f.data(), s1f.size() * sizeof(float2), hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) return bail(rsp_set_error(RSP_ERR_DEVICE, "steering upload failed"));
-#ifdef RSP_DEBUG_KNOBS   // diagnostic builds only: the shipped library reads no environment variable
-    const char* tr = getenv("RSP_MUSIC_TRACE");
-    if (tr && atoi(tr) && hipMalloc(&p->d_trace, B * 8 * sizeof(unsigned long long)) != hipSuccess)
-        return bail(rsp_set_error(RSP_ERR_NOMEM, "trace buffer"));
-#endif
-    *out = p;
-    return RSP_OK;
+    if (d.f64) go((double2*)dX);
+    else go((float2*)dX);
+    return hipGetLastError();
 }
-
-int32_t rsp_music_destroy(rsp_music_plan* p) {
-    if (!p) return RSP_OK;
-    (void)hipSetDevice(p->device);
-    if (p->stream) (void)hipStreamSynchronize(p->stream);
-    void* bufs[] = {p->d_S1T, p->d_R, p->d_X, p->d_spec, p->d_eig, p->d_peaks, p->d_src, p->d_amp, p->d_trace,
-                    p->d_exy, p->d_qs};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    for (auto& e : p->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (p->stream) (void)hipStreamDestroy(p->stream);
-    delete p;
-    return RSP_OK;
-}
-
-int32_t rsp_music_synthesize_device(rsp_music_plan* p, const rsp_music_scene* sc, int32_t n_inst, int32_t inst0,
-                                    uint64_t seed, void* d_X) {
-    if (!p || !sc || !d_X) return rsp_set_error(RSP_ERR_INVALID, "null argument");
-    if (p->planar) return rsp_set_error(RSP_ERR_INVALID, "rsp_music_synthesize_device on a planar-array plan");
-    if (sc->n_src < 1 || sc->n_src > MU_MMAX)
-        return rsp_set_error(RSP_ERR_UNSUPPORTED, "n_src %d outside 1..%d", sc->n_src, MU_MMAX);
-    if (n_inst < 1) return rsp_set_error(RSP_ERR_INVALID, "n_inst %d < 1", n_inst);
-    MUCHK(hipSetDevice(p->device));
-    const int N = p->N, Ms = sc->n_src;
-    std::vector<double2> src((size_t)Ms * N);
-    for (int m = 0; m < Ms; ++m)   // S = exp(1j k z sin(phi')) (MUSIC_1D.m:21)
-        for (int c = 0; c < N; ++c) {
-            const double ph = 2.0 * M_PI * p->dl * c * std::sin(sc->angles_rad[m]);
-            src[(size_t)m * N + c] = make_double2(std::cos(ph), std::sin(ph));
-        }
-    return music_synth(p, sc, src, n_inst, inst0, seed, d_X);
-}
-
-int32_t rsp_music_process_device(rsp_music_plan* p, const void* d_X, int32_t n_inst, rsp_music_out* out) {
-    if (!p || !d_X) return rsp_set_error(RSP_ERR_INVALID, "null argument");
-    const int want = !out ? MU_WANT_PEAKS
-                          : out->eigenvalues ? MU_WANT_EIGS : out->spectrum_db ? MU_WANT_SPECTRUM : MU_WANT_PEAKS;
-    int rc = p->planar ? music_run_planar(p, d_X, n_inst, false, nullptr, want)
-                       : music_run(p, d_X, n_inst, false, nullptr, want);
-    if (rc) return rc;
-    if (!out) {
-        MUCHK(hipStreamSynchronize(p->stream));
-        return RSP_OK;
-    }
-    return music_fetch(p, n_inst, out);
-}
-
-int32_t rsp_music_process(rsp_music_plan* p, const void* X, int32_t dtype, int32_t n_inst, rsp_music_out* out) {
-    if (!p || !X) return rsp_set_error(RSP_ERR_INVALID, "null argument");
-    if (n_inst < 1 || n_inst > p->max_batch)
-        return rsp_set_error(RSP_ERR_INVALID, "n_inst %d outside 1..max_batch %d", n_inst, p->max_batch);
-    if (dtype != RSP_C64 && dtype != RSP_C128) return rsp_set_error(RSP_ERR_INVALID, "unknown dtype %d", dtype);
-    MUCHK(hipSetDevice(p->device));
-    const size_t elems = (size_t)n_inst * p->K * p->N;
-    if (!p->d_X) {
-        const size_t bytes = (size_t)p->max_batch * p->K * p->N * p->xsz;
-        if (hipMalloc(&p->d_X, bytes) != hipSuccess)
-            return rsp_set_error(RSP_ERR_NOMEM, "hipMalloc(%zu bytes) failed", bytes);
-    }
-    if ((dtype == RSP_C128) == p->f64) {
-        MUCHK(hipMemcpy(p->d_X, X, elems * p->xsz, hipMemcpyHostToDevice));
-    } else if (p->f64) {   // complex single snapshots into a complex-double plan: widen
-        std::vector<double2> h(elems);
-        const float* x = (const float*)X;
-        for (size_t i = 0; i < elems; ++i) h[i] = make_double2(x[2 * i], x[2 * i + 1]);
-        MUCHK(hipMemcpy(p->d_X, h.data(), elems * sizeof(double2), hipMemcpyHostToDevice));
-    } else {
-        std::vector<float2> h(elems);
-        const double* x = (const double*)X;
-        for (size_t i = 0; i < elems; ++i) h[i] = make_float2((float)x[2 * i], (float)x[2 * i + 1]);
-        MUCHK(hipMemcpy(p->d_X, h.data(), elems * sizeof(float2), hipMemcpyHostToDevice));
-    }
-    return rsp_music_process_device(p, p->d_X, n_inst, out);
-}
-
-int32_t rsp_music_profile(rsp_music_plan* p, const void* d_X, int32_t n_inst, int32_t iters, float* ms_out) {
-    return rsp_music_profile_ex(p, d_X, n_inst, iters, RSP_MUSIC_PEAKS, ms_out);
-}
-
-int32_t rsp_music_profile_ex(rsp_music_plan* p, const void* d_X, int32_t n_inst, int32_t iters, int32_t what,
-                             float* ms_out) {
-    if (!p || !d_X || !ms_out || iters < 1) return rsp_set_error(RSP_ERR_INVALID, "bad argument");
-    if (p->planar) return rsp_set_error(RSP_ERR_INVALID, "planar-array plan: use rsp_music_profile_2d (four stages)");
-    if (what != RSP_MUSIC_PEAKS && what != RSP_MUSIC_SPECTRUM && what != RSP_MUSIC_EIGENVALUES)
-        return rsp_set_error(RSP_ERR_INVALID, "unknown profile form %d", what);
-    const int want = what == RSP_MUSIC_EIGENVALUES ? MU_WANT_EIGS
-                   : what == RSP_MUSIC_SPECTRUM ? MU_WANT_SPECTRUM : MU_WANT_PEAKS;
-    double acc[2] = {0.0, 0.0};
-    for (int it = 0; it < iters; ++it) {
-        float ms[2];
-        int rc = music_run(p, d_X, n_inst, true, ms, want);
-        if (rc) return rc;
-        acc[0] += ms[0];
-        acc[1] += ms[1];
-    }
-    ms_out[0] = (float)(acc[0] / iters);
-    ms_out[1] = (float)(acc[1] / iters);
-    if (p->d_trace) {   // mean phase durations of the last launch (s_memrealtime: 100 MHz)
-        std::vector<unsigned long long> t((size_t)n_inst * 8);
-        MUCHK(hipMemcpy(t.data(), p->d_trace, t.size() * sizeof(t[0]), hipMemcpyDeviceToHost));
-        double ph[6] = {0, 0, 0, 0, 0, 0};
-        for (int i = 0; i < n_inst; ++i)
-            for (int q = 0; q < 6; ++q) ph[q] += (double)(t[(size_t)i * 8 + q + 1] - t[(size_t)i * 8 + q]) * 0.01 / n_inst;
-        double tf = 0;   // stamp 7 (complex double): dlagtf's end, inside the inverse-iteration phase
-        for (int i = 0; i < n_inst && p->f64; ++i) tf += (double)(t[(size_t)i * 8 + 7] - t[(size_t)i * 8 + 2]) * 0.01 / n_inst;
-        fprintf(stderr, "k_music_eig%s phases (us/instance): tridiag %.2f eigenvalues %.2f inviter %.2f (dlagtf %.2f) backxf %.2f spectrum %.2f peaks %.2f\n",
-                p->f64 ? "64" : "",
-                ph[0], ph[1], ph[2], tf, ph[3], ph[4], ph[5]);
-    }
-    return RSP_OK;
-}
-
-int32_t rsp_music_device_alloc(rsp_music_plan* p, int64_t bytes, void** d_ptr) {
-    if (!p || !d_ptr || bytes <= 0) return rsp_set_error(RSP_ERR_INVALID, "bad argument");
-    MUCHK(hipSetDevice(p->device));
-    if (hipMalloc(d_ptr, (size_t)bytes) != hipSuccess)
-        return rsp_set_error(RSP_ERR_NOMEM, "hipMalloc(%lld bytes) failed", (long long)bytes);
-    return RSP_OK;
-}
-
-int32_t rsp_music_device_free(rsp_music_plan* p, void* d_ptr) {
-    if (!p) return rsp_set_error(RSP_ERR_INVALID, "null plan");
-    MUCHK(hipSetDevice(p->device));
-    MUCHK(hipStreamSynchronize(p->stream));
-    MUCHK(hipFree(d_ptr));
-    return RSP_OK;
-}
-
-int32_t rsp_music_fast_count(rsp_music_plan* p, int32_t* n_fast) {
-    if (!p || !n_fast) return rsp_set_error(RSP_ERR_INVALID, "bad argument");
-    *n_fast = 0;
-    if (!p->f64 || p->M >= MU_MMAX || p->last_inst < 1) return RSP_OK;   // only complex double, M <= 4, sets it
-    MUCHK(hipSetDevice(p->device));
-    MUCHK(hipStreamSynchronize(p->stream));
-    std::vector<int> pk((size_t)p->last_inst * (MU_MMAX + 1));
-    MUCHK(hipMemcpy(pk.data(), p->d_peaks, pk.size() * sizeof(int), hipMemcpyDeviceToHost));
-    for (int i = 0; i < p->last_inst; ++i) *n_fast += pk[(size_t)i * (MU_MMAX + 1) + MU_MMAX] == 1;
-    return RSP_OK;
-}
-
-int32_t rsp_music_device_download(rsp_music_plan* p, void* h_dst, const void* d_src, int64_t bytes) {
-    if (!p || !h_dst || !d_src || bytes < 0) return rsp_set_error(RSP_ERR_INVALID, "bad argument");
-    MUCHK(hipSetDevice(p->device));
-    MUCHK(hipStreamSynchronize(p->stream));
-    MUCHK(hipMemcpy(h_dst, d_src, (size_t)bytes, hipMemcpyDeviceToHost));
-    return RSP_OK;
-}
-
-}  // extern "C"

@@ -140,27 +140,28 @@ class MusicPlan:
         _abi.check(self._lib.rsp_music_process_device(self._h, ct.c_void_p(d_X), n_inst, ct.byref(st)))
         return self._finish(o)
 
+    def _device_into(self, d_X, n_inst, peaks, n_peaks, spec=None, eig=None):
+        """Device run into caller arrays; spec / eig None: not read."""
+        st = _abi.MusicOut(None if spec is None else spec.ctypes.data_as(_abi._dp),
+                           None if eig is None else eig.ctypes.data_as(_abi._dp),
+                           peaks.ctypes.data_as(ct.POINTER(ct.c_int32)), n_peaks.ctypes.data_as(ct.POINTER(ct.c_int32)), None)
+        _abi.check(self._lib.rsp_music_process_device(self._h, ct.c_void_p(d_X), n_inst, ct.byref(st)))
+
     def peaks_device(self, d_X, n_inst, peaks, n_peaks):
         """Device run returning only the peak indices (into caller arrays): the bench's step."""
-        st = _abi.MusicOut(None, None, peaks.ctypes.data_as(ct.POINTER(ct.c_int32)),
-                           n_peaks.ctypes.data_as(ct.POINTER(ct.c_int32)), None)
-        _abi.check(self._lib.rsp_music_process_device(self._h, ct.c_void_p(d_X), n_inst, ct.byref(st)))
+        self._device_into(d_X, n_inst, peaks, n_peaks)
 
     def eig_device(self, d_X, n_inst, eig, peaks, n_peaks):
         """Device run returning all N eigenvalues (descending, MUSIC_1D.m:29-33) and the peak indices
         into caller arrays: the form of the 3-output rsp_mex('music') / music_1d_calllib.m call,
         which always runs the full eigensolver (bench.py --want-eig)."""
-        st = _abi.MusicOut(None, eig.ctypes.data_as(_abi._dp), peaks.ctypes.data_as(ct.POINTER(ct.c_int32)),
-                           n_peaks.ctypes.data_as(ct.POINTER(ct.c_int32)), None)
-        _abi.check(self._lib.rsp_music_process_device(self._h, ct.c_void_p(d_X), n_inst, ct.byref(st)))
+        self._device_into(d_X, n_inst, peaks, n_peaks, eig=eig)
 
     def spectrum_device(self, d_X, n_inst, spec, peaks, n_peaks):
         """Device run returning the pseudo-spectrum P_dB ([n_inst, n_scan], MUSIC_1D.m:41) and the peak
         indices into caller arrays, without the eigenvalues: the form of the 2-output rsp_mex('music')
         call and of MUSIC_1D.m's plot (bench.py --want-spectrum)."""
-        st = _abi.MusicOut(spec.ctypes.data_as(_abi._dp), None, peaks.ctypes.data_as(ct.POINTER(ct.c_int32)),
-                           n_peaks.ctypes.data_as(ct.POINTER(ct.c_int32)), None)
-        _abi.check(self._lib.rsp_music_process_device(self._h, ct.c_void_p(d_X), n_inst, ct.byref(st)))
+        self._device_into(d_X, n_inst, peaks, n_peaks, spec=spec)
 
     def fast_count(self):
         """Instances of the last call answered by the block-power fast path (rsp_music_fast_count)."""
@@ -168,13 +169,14 @@ class MusicPlan:
         _abi.check(self._lib.rsp_music_fast_count(self._h, ct.byref(n)))
         return n.value
 
+    # the forms of call the profile entries time (``what``)
+    FORMS = {'peaks': _abi.RSP_MUSIC_PEAKS, 'spectrum': _abi.RSP_MUSIC_SPECTRUM, 'eigenvalues': _abi.RSP_MUSIC_EIGENVALUES}
+
     def profile(self, d_X, n_inst, iters=20, what='peaks'):
         """HIP-event times of the two stages for the form of call ``what``: 'peaks' (the bench's
         step), 'spectrum' (spectrum_db read) or 'eigenvalues' (all N eigenvalues read)."""
-        forms = {'peaks': _abi.RSP_MUSIC_PEAKS, 'spectrum': _abi.RSP_MUSIC_SPECTRUM,
-                 'eigenvalues': _abi.RSP_MUSIC_EIGENVALUES}
         ms = (ct.c_float * 2)()
-        _abi.check(self._lib.rsp_music_profile_ex(self._h, ct.c_void_p(d_X), n_inst, iters, forms[what], ms))
+        _abi.check(self._lib.rsp_music_profile_ex(self._h, ct.c_void_p(d_X), n_inst, iters, self.FORMS[what], ms))
         return {'cov_ms': ms[0], 'eig_ms': ms[1]}
 
 
@@ -236,10 +238,8 @@ class MusicPlan2D(MusicPlan):
     def profile(self, d_X, n_inst, iters=20, what='peaks'):
         """HIP-event times of the four stages (covariance, signal subspace, scan, dB + peaks) for the
         form of call ``what``: 'peaks', 'spectrum' or 'eigenvalues'."""
-        forms = {'peaks': _abi.RSP_MUSIC_PEAKS, 'spectrum': _abi.RSP_MUSIC_SPECTRUM,
-                 'eigenvalues': _abi.RSP_MUSIC_EIGENVALUES}
         ms = (ct.c_float * 4)()
-        _abi.check(self._lib.rsp_music_profile_2d(self._h, ct.c_void_p(d_X), n_inst, iters, forms[what], ms))
+        _abi.check(self._lib.rsp_music_profile_2d(self._h, ct.c_void_p(d_X), n_inst, iters, self.FORMS[what], ms))
         return {'cov_ms': ms[0], 'subspace_ms': ms[1], 'scan_ms': ms[2], 'peaks_ms': ms[3]}
 
 

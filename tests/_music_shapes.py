@@ -3,7 +3,7 @@
 Everything here is host arithmetic on ``oracle/music.py`` (complex128, ``np.linalg.eigh``): the case
 table, the scene every case shares, the duplicated scan grid of the plateau case, the margins that
 decide where a device answer must equal the oracle's exactly, and the restated LDS arithmetic of
-``me_lds_bytes`` (csrc/rsp_music.hip).  No device code is touched.
+``me_lds_bytes`` (csrc/rsp_music_geometry.h).  No device code is touched.
 """
 import functools
 
@@ -140,7 +140,7 @@ def f32_restatement(X, M, scan):
     return w[order].astype(np.float64), (np.float32(10.0) * np.log10(P / P.max())).astype(np.float64)
 
 
-# ---- csrc/rsp_music.hip: me_lds_bytes (dynamic LDS of k_music_eig64), restated
+# ---- csrc/rsp_music_geometry.h: me_lds_bytes (dynamic LDS of k_music_eig64), restated
 ME_VW = 68
 
 

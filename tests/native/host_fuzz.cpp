@@ -1,9 +1,12 @@
-// Host-only driver of librsp's plain-C++ parts (rsp_mat.cpp, rsp_host.cpp, rsp_geometry.cpp) for
-// the AddressSanitizer / UBSan build of tests/test_host_asan.py.  Status codes are ignored: only
-// memory errors (reported by the sanitizers, exit code != 0) fail the test.
+// Host-only driver of librsp's plain-C++ parts (rsp_mat.cpp, rsp_host.cpp, rsp_geometry.cpp,
+// rsp_music_geometry.cpp) for the AddressSanitizer / UBSan build of tests/test_host_asan.py.  Status
+// codes are ignored: only memory errors (reported by the sanitizers, exit code != 0) fail the test.
 //   host_fuzz mat FILE...     every MAT entry point on every file
 //   host_fuzz cluster SEED    S10/S11 and inter-frame clustering on random lists
 //   host_fuzz geometry SEED   rsp_plan_describe on random plan arguments, most of them valid
+//   host_fuzz music SEED      the MUSIC host module on random line and planar plans, most of them valid
+//   host_fuzz music-route line|planar c128|c64 N M S peaks|spectrum|eigs
+//                             prints the route of one call (planar: nx = N, ny = 1, an S x 3 grid)
 #include <cmath>
 #include <complex>
 #include <cstdio>
@@ -13,6 +16,7 @@
 #include <vector>
 
 #include "rsp.h"
+#include "rsp_music_geometry.h"
 
 static int mat(int argc, char** argv) {
     for (int i = 2; i < argc; ++i) {
@@ -161,10 +165,178 @@ static int geometry(unsigned seed) {
     return 0;
 }
 
+// One MUSIC configuration of either kind; every array exactly as long as rsp.h says it is read.
+struct MusicCase {
+    bool planar = false;
+    int N = 8, nx = 4, ny = 2, K = 16, M = 2, S = 67, nt = 9, np = 11, batch = 4, prec = RSP_C128;
+    bool null_grid = false;
+};
+
+static int music_describe_case(const MusicCase& c, const std::vector<double>& g1, const std::vector<double>& g2,
+                               rsp_music_config* lc, rsp_music2d_config* pc, MusicDesc* d) {
+    if (c.planar) {
+        *pc = rsp_music2d_config{c.nx, c.ny, c.K, c.M, c.np, c.nt, 0.5, 0.4, g1.data(), c.null_grid ? nullptr : g2.data(),
+                                 c.batch, c.prec};
+        return music_describe(pc, d);
+    }
+    *lc = rsp_music_config{c.N, c.K, c.M, c.S, 0.5, c.null_grid ? nullptr : g1.data(), c.batch, c.prec};
+    return music_describe(lc, d);
+}
+
+// Everything the device-free module does for one accepted plan
+static void music_exercise(std::mt19937_64& g, const MusicDesc& d, const rsp_music_config* lc, const rsp_music2d_config* pc) {
+    auto ri = [&](int lo, int hi) { return std::uniform_int_distribution<int>(lo, hi)(g); };
+    std::uniform_real_distribution<double> u(-1.0, 1.0);
+    size_t bytes[MB_COUNT];
+    music_buffer_bytes(d, bytes);
+    const std::vector<double> tab = d.planar ? music_table(d, pc) : music_table(d, lc);
+    std::vector<unsigned char> stage;
+    music_in_precision(d, tab.data(), RSP_C128, tab.size(), stage);
+    if (tab.size() * (d.xsz() / 2) != bytes[d.planar ? MB_EXY : MB_S1T]) abort();   // the table fills its buffer exactly
+    for (int want = MU_WANT_PEAKS; want <= MU_WANT_EIGS; ++want) {
+        const MusicRoute r = music_route(d, want);
+        if (r.lds > RSP_LDS_BYTES || r.neig < 1 || r.neig > d.N) abort();
+    }
+    int want = 0;
+    music_want_of_form(ri(-1, 3), &want);
+    // scenes of both kinds on this plan (one of them is refused), n_src 0 and 9 among them
+    rsp_music_scene ls = {ri(0, 9), ri(0, 1), ri(0, 1), 0, 10.0 * u(g), {}, {}};
+    rsp_music2d_scene ps = {ri(0, 9), 1, ri(0, 1), 0, 10.0 * u(g), {}, {}, {}};
+    for (int m = 0; m < 8; ++m) {
+        ls.angles_rad[m] = ps.azim_rad[m] = 1.5 * u(g);
+        ps.elev_rad[m] = 1.5 * u(g);
+        ls.amplitudes[m] = ps.amplitudes[m] = 1.0 + 0.5 * u(g);
+    }
+    MusicSynth sy;
+    music_scene(d, &ls, ri(0, 3), &sy);
+    music_scene(d, &ps, ri(0, 3), &sy);
+    // results: device-shaped random buffers into exactly sized outputs, every combination of nulls
+    const int n_inst = ri(1, d.max_batch);
+    std::vector<double> spec((size_t)n_inst * d.S), eig((size_t)n_inst * d.N), cov((size_t)2 * n_inst * d.N * d.N);
+    std::vector<int32_t> pidx((size_t)n_inst * d.M), npk(n_inst);
+    for (int mask = 0; mask < 32; ++mask) {
+        rsp_music_out out = {mask & 1 ? spec.data() : nullptr, mask & 2 ? eig.data() : nullptr, mask & 4 ? pidx.data() : nullptr,
+                             mask & 8 ? npk.data() : nullptr, mask & 16 ? cov.data() : nullptr};
+        if (music_want(&out) != (mask & 2 ? MU_WANT_EIGS : mask & 1 ? MU_WANT_SPECTRUM : MU_WANT_PEAKS)) abort();
+        MusicFetch f;
+        music_fetch_plan(d, n_inst, &out, &f);
+        for (int c = 0; c < f.n; ++c) {
+            if (f.copy[c].bytes > bytes[f.copy[c].buf]) abort();   // never more than the device buffer holds
+            unsigned char* dst = (unsigned char*)f.copy[c].dst;
+            for (size_t b = 0; b < f.copy[c].bytes; ++b) dst[b] = (unsigned char)g();
+        }
+        music_unpack(d, n_inst, f, &out);
+        if (!f.stage[2].empty()) music_fast_count((const int*)f.stage[2].data(), n_inst);
+    }
+    music_want(nullptr);
+    // host snapshots of either type into the plan's precision
+    const size_t reals = (size_t)2 * n_inst * d.K * d.N;
+    std::vector<double> xd(reals);
+    std::vector<float> xf(reals);
+    for (size_t i = 0; i < reals; ++i) xf[i] = (float)(xd[i] = u(g));
+    music_in_precision(d, xd.data(), RSP_C128, reals, stage);
+    music_in_precision(d, xf.data(), RSP_C64, reals, stage);
+}
+
+static int music(unsigned seed) {
+    std::mt19937_64 g(seed);
+    auto ri = [&](int lo, int hi) { return std::uniform_int_distribution<int>(lo, hi)(g); };
+    std::uniform_real_distribution<double> u(-1.0, 1.0);
+    // the envelope's corners, accepted, first: N = 2 and 64, M = N - 1 and 8, S = 3 and 4096, a 1024 x 64 grid
+    std::vector<MusicCase> cases(8);
+    cases[0].N = 2; cases[0].M = 1;
+    cases[1].N = 64; cases[1].M = 8; cases[1].S = 4096;
+    cases[2].N = 5; cases[2].M = 4; cases[2].S = 3; cases[2].prec = RSP_C64;
+    cases[3].N = 64; cases[3].M = 7; cases[3].S = 4095; cases[3].prec = RSP_C64;
+    cases[4].planar = true; cases[4].nx = 2; cases[4].ny = 1; cases[4].M = 1; cases[4].nt = 1024; cases[4].np = 64;
+    cases[5].planar = true; cases[5].nx = 8; cases[5].ny = 8; cases[5].M = 8; cases[5].nt = 3; cases[5].np = 3;
+    cases[6].planar = true; cases[6].nx = 1; cases[6].ny = 64; cases[6].M = 7; cases[6].nt = 64; cases[6].np = 1024;
+    cases[7].planar = true; cases[7].nx = 3; cases[7].ny = 1; cases[7].M = 2;
+    const int n_forced = (int)cases.size();
+    for (int rep = 0; rep < 300; ++rep) {
+        MusicCase c;
+        c.planar = rep < 32 ? rep >= 16 : ri(0, 1);   // every refusal below at least once for either kind
+        c.nx = ri(1, 8); c.ny = ri(c.nx == 1 ? 2 : 1, 8);
+        c.N = c.planar ? c.nx * c.ny : ri(0, 3) ? ri(2, 20) : ri(2, 64);
+        c.M = ri(1, std::min(8, c.N - 1));
+        c.K = ri(1, 40);
+        c.S = ri(0, 7) ? ri(3, 300) : ri(3, 4096);
+        c.nt = ri(3, 40); c.np = ri(3, 40);
+        c.batch = ri(1, 4);
+        c.prec = c.planar || ri(0, 1) ? RSP_C128 : RSP_C64;
+        switch (rep < 32 ? rep % 16 : ri(0, 63)) {   // deliberately out of range (one in four of the random ones)
+            case 0: c.N = 1; c.nx = c.ny = 1; break;
+            case 1: c.N = 65; c.nx = 5; c.ny = 13; break;           // nx*ny = 65
+            case 2: c.M = 0; break;
+            case 3: c.M = c.N; break;
+            case 4: c.M = 9; c.N = 16; c.nx = c.ny = 4; break;
+            case 5: c.K = 0; break;
+            case 6: c.S = 2; c.nt = 2; break;
+            case 7: c.S = 4097; c.np = 1025; c.nt = 3; break;       // grid 1025 x 3
+            case 8: c.nt = 1024; c.np = 65; break;                  // grid 1024 x 65
+            case 9: c.null_grid = true; break;
+            case 10: c.prec = 7; break;
+            case 11: c.prec = RSP_C64; c.planar = true; break;      // C64 planar
+            case 12: c.batch = 0; break;
+            case 13: c.nx = 65; c.ny = 1; c.N = 65; break;
+            case 14: c.nx = 0; c.N = 0; break;
+            case 15: c.nt = 1025; c.np = 3; break;
+            default: break;
+        }
+        cases.push_back(c);
+    }
+    int n_ok = 0;
+    for (size_t i = 0; i < cases.size(); ++i) {
+        const MusicCase& c = cases[i];
+        // grids of exactly the lengths the tables read
+        std::vector<double> g1(std::max(1, c.planar ? c.np : c.S)), g2(std::max(1, c.nt));
+        for (auto& v : g1) v = 1.6 * u(g);
+        for (auto& v : g2) v = 1.6 * u(g);
+        rsp_music_config lc;
+        rsp_music2d_config pc;
+        MusicDesc d;
+        const int rc = music_describe_case(c, g1, g2, &lc, &pc, &d);
+        if (rc != RSP_OK && (int)i < n_forced) abort();   // the corners are inside the envelope
+        if (rc != RSP_OK) continue;
+        ++n_ok;
+        music_exercise(g, d, &lc, &pc);
+    }
+    printf("music seed %u: %d of %d configurations accepted\n", seed, n_ok, (int)cases.size());
+    music_describe((const rsp_music_config*)nullptr, nullptr);
+    music_describe((const rsp_music2d_config*)nullptr, nullptr);
+    return 0;
+}
+
+static int music_route_of(char** a) {
+    MusicCase c;
+    c.planar = !strcmp(a[0], "planar");
+    c.prec = !strcmp(a[1], "c64") ? RSP_C64 : RSP_C128;
+    c.N = c.nx = atoi(a[2]); c.ny = 1;
+    c.M = atoi(a[3]);
+    c.S = c.nt = atoi(a[4]); c.np = 3;
+    const int want = !strcmp(a[5], "eigs") ? MU_WANT_EIGS : !strcmp(a[5], "spectrum") ? MU_WANT_SPECTRUM : MU_WANT_PEAKS;
+    const std::vector<double> g1(std::max(3, c.S), 0.0), g2(std::max(3, c.nt), 0.0);
+    rsp_music_config lc;
+    rsp_music2d_config pc;
+    MusicDesc d;
+    if (music_describe_case(c, g1, g2, &lc, &pc, &d) != RSP_OK) {
+        printf("refused=1\n");
+        return 0;
+    }
+    const MusicRoute r = music_route(d, want);
+    static const char* cov[] = {"f64", "f32_vec4", "f32"};
+    static const char* eig[] = {"k_music_eig", "k_music_eig64", "k_music_sub64"};
+    printf("stages=%d cov=%s eig=%s fast=%d neig=%d spec_tol=%g lds=%zu raise_lds=%d fast_flag=%d\n", r.n_stages, cov[r.cov],
+           eig[r.eig], (int)r.fast, r.neig, r.spec_tol, r.lds, (int)r.raise_lds, (int)r.fast_flag);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc >= 2 && !strcmp(argv[1], "mat")) return mat(argc, argv);
     if (argc >= 3 && !strcmp(argv[1], "cluster")) return cluster((unsigned)atoi(argv[2]));
     if (argc >= 3 && !strcmp(argv[1], "geometry")) return geometry((unsigned)atoi(argv[2]));
-    fprintf(stderr, "usage: host_fuzz mat FILE... | cluster SEED | geometry SEED\n");
+    if (argc >= 3 && !strcmp(argv[1], "music")) return music((unsigned)atoi(argv[2]));
+    if (argc >= 8 && !strcmp(argv[1], "music-route")) return music_route_of(argv + 2);
+    fprintf(stderr, "usage: host_fuzz mat FILE... | cluster SEED | geometry SEED | music SEED | music-route ...\n");
     return 2;
 }

@@ -3,8 +3,9 @@
 csrc/rsp_mat.cpp (the MAT Level-5 reader/writer that parses untrusted frame files) and
 csrc/rsp_host.cpp (error sink, S10/S11 clustering of fun_process_single_frame.m:302-407,
 inter-frame association of main_simulate_echoes_with_array_v8_3.m:253-352) and
-csrc/rsp_geometry.cpp (plan geometry, K1 routing and host tables: rsp_plan_describe) are compiled
-with g++ -fsanitize=address,undefined together with tests/native/host_fuzz.cpp and driven over:
+csrc/rsp_geometry.cpp (plan geometry, K1 routing and host tables: rsp_plan_describe) and
+csrc/rsp_music_geometry.cpp (the MUSIC plans' checks, sizes, tables, routes and host conversions) are
+compiled with g++ -fsanitize=address,undefined together with tests/native/host_fuzz.cpp and driven over:
   * the reference's MATLAB-written files and scipy-written frames;
   * crafted malformed files: a small-form element claiming 8 inline bytes (the overflow the
     round-1 review found), truncations at every 7th byte, dims larger than the data, a corrupt
@@ -13,7 +14,15 @@ with g++ -fsanitize=address,undefined together with tests/native/host_fuzz.cpp a
   * 2500 random plan argument sets per seed (C <= 32, B <= 16, even P <= 1100, N <= 8192, power-of-two
     and other N_fft, matched-filter spectra of random short filters), one in four deliberately out
     of range: segment starts at 0 and past N, gate sums off by one, no FIR taps, gates beyond
-    N_fft, an all-zero filter.
+    N_fft, an all-zero filter;
+  * per seed, the corners of the MUSIC envelope (N = 2 and 64, M = N - 1 and 8, S = 3 and 4096, a
+    1024 x 64 grid) and 300 random line and planar MUSIC configurations, every refusal of the two create
+    functions among them (N = 1 and 65, nx*ny = 65, M = 0, N and 9, K = 0, S = 2 and 4097, grids
+    1024 x 65 and 1025 x 3, null grids, precision 7, a complex-single planar plan): for each accepted
+    one every table, the route of all three forms of call, both kinds of scene, the unpacking of
+    random device-shaped results (batch 1..4, every combination of null outputs, both precisions)
+    and host snapshots widened and narrowed.
+test_music_routes pins the routing decisions through the same program (host_fuzz music-route).
 Only sanitizer reports (non-zero exit) fail; the functions' status codes are not checked here
 (tests/test_matio.py does that).
 """
@@ -42,7 +51,7 @@ def fuzz_bin(tmp_path_factory):
     cmd = ['g++', '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined',
            '-fno-omit-frame-pointer', '-I', os.path.join(ROOT, 'include'),
            os.path.join(CSRC, 'rsp_mat.cpp'), os.path.join(CSRC, 'rsp_host.cpp'),
-           os.path.join(CSRC, 'rsp_geometry.cpp'),
+           os.path.join(CSRC, 'rsp_geometry.cpp'), os.path.join(CSRC, 'rsp_music_geometry.cpp'), '-I', CSRC,
            os.path.join(HERE, 'native', 'host_fuzz.cpp'), '-o', exe, '-lz', '-lpthread']
     subprocess.run(cmd, check=True)
     return exe
@@ -54,6 +63,7 @@ def _run(exe, *args):
     r = subprocess.run([exe] + list(args), capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0 and 'ERROR: AddressSanitizer' not in r.stderr and 'runtime error' not in r.stderr, \
         r.stderr[-3000:]
+    return r.stdout
 
 
 def _header():
@@ -126,6 +136,63 @@ def test_clustering_under_asan(fuzz_bin, seed):
 @pytest.mark.parametrize('seed', [1, 2])
 def test_plan_geometry_under_asan(fuzz_bin, seed):
     _run(fuzz_bin, 'geometry', str(seed))
+
+
+@pytest.mark.parametrize('seed', [1, 2])
+def test_music_host_under_asan(fuzz_bin, seed):
+    _run(fuzz_bin, 'music', str(seed))
+
+
+def _route(exe, kind, prec, N, M, S, want):
+    """The route of one call as host_fuzz music-route prints it: a dict of strings."""
+    out = _run(exe, 'music-route', kind, prec, str(N), str(M), str(S), want)
+    return dict(kv.split('=') for kv in out.split())
+
+
+def test_music_routes(fuzz_bin):
+    """The decisions of music_route (csrc/rsp_music_geometry.cpp) as the library has always made them."""
+    from _music_shapes import CASES, me_lds_bytes
+    full = dict(eig='k_music_eig64', fast='0', spec_tol='0')
+    for M in (1, 2, 3, 4):
+        r = _route(fuzz_bin, 'line', 'c128', 16, M, 67, 'peaks')
+        assert (r['eig'], r['fast'], r['neig'], r['spec_tol']) == ('k_music_eig64', '1', str(M), '0'), r
+        assert (r['stages'], r['cov']) == ('2', 'f64'), r
+        r = _route(fuzz_bin, 'line', 'c128', 16, M, 67, 'spectrum')
+        assert (r['eig'], r['fast'], r['neig'], r['spec_tol']) == ('k_music_eig64', '1', str(M), '1e-08'), r
+    for N, M in ((2, 1), (4, 3), (16, 2), (16, 4), (16, 5), (64, 8)):
+        r = _route(fuzz_bin, 'line', 'c128', N, M, 67, 'eigs')   # N <= 4 (neig = N <= 4) included
+        assert dict(r, **full) == r and r['neig'] == str(N), r
+    for M in (5, 6, 7, 8):
+        for want in ('peaks', 'spectrum', 'eigs'):
+            r = _route(fuzz_bin, 'line', 'c128', 16, M, 67, want)
+            assert dict(r, **full) == r and r['neig'] == ('16' if want == 'eigs' else str(M)), r
+    for N in (4, 5, 6, 7, 8, 63, 64):
+        for want in ('peaks', 'spectrum', 'eigs'):
+            r = _route(fuzz_bin, 'line', 'c64', N, 2, 67, want)
+            assert (r['eig'], r['fast'], r['fast_flag']) == ('k_music_eig', '0', '0'), r
+            assert r['cov'] == ('f32_vec4' if N % 4 == 0 else 'f32'), r
+    for M in range(1, 9):
+        for want in ('peaks', 'spectrum', 'eigs'):
+            r = _route(fuzz_bin, 'planar', 'c128', 16, M, 17, want)
+            assert (r['stages'], r['cov'], r['eig']) == ('4', 'f64', 'k_music_sub64'), r
+            assert r['fast'] == ('1' if want == 'peaks' and M <= 4 else '0') and r['spec_tol'] == '0', r
+            assert int(r['lds']) == me_lds_bytes(M, 0) and r['raise_lds'] == '0', r
+    # the dynamic LDS of k_music_eig64 over the shape table; past 64 KiB for exactly the two long scans
+    lds = {}
+    for case, (N, K, M, S) in CASES.items():
+        r = _route(fuzz_bin, 'line', 'c128', N, M, S, 'peaks')
+        assert int(r['lds']) == me_lds_bytes(M, S), (case, r)
+        assert r['raise_lds'] == ('1' if me_lds_bytes(M, S) > 64 * 1024 else '0'), (case, r)
+        lds[(M, S)] = (int(r['lds']), r['raise_lds'])
+    assert lds[(7, 4096)] == (65696, '1') and lds[(8, 4095)] == (69272, '1')
+    assert sorted(k for k, v in lds.items() if v[1] == '1') == [(7, 4096), (8, 4095)]
+    # the fast flag: complex double and M < 8, line or planar
+    for kind in ('line', 'planar'):
+        for M in range(1, 9):
+            assert _route(fuzz_bin, kind, 'c128', 16, M, 17, 'peaks')['fast_flag'] == ('1' if M < 8 else '0')
+    refused = {'refused': '1'}   # no route for what the create functions refuse
+    assert _route(fuzz_bin, 'planar', 'c64', 16, 2, 17, 'peaks') == refused
+    assert _route(fuzz_bin, 'line', 'c128', 16, 9, 17, 'peaks') == refused
 
 
 def test_malformed_small_element_is_an_error(tmp_path):

@@ -129,20 +129,22 @@ def test_duplicated_grid_reference():
 
 def test_long_scan_cases_exceed_64k_of_lds():
     """k_music_eig64's dynamic LDS (me_lds_bytes): M = 7 with S = 4096 needs 65 696 B and M = 8 with
-    S = 4095 needs 69 272 B, so launch_eig64 raises the kernel's dynamic-LDS limit for exactly these
-    two cases; every other case stays within 64 KiB.  The restated formula is the source's."""
+    S = 4095 needs 69 272 B, so music_route has the launcher raise the kernel's dynamic-LDS limit for
+    exactly these two cases; every other case stays within 64 KiB.  The restated formula is the source's
+    (tests/test_host_asan.py::test_music_routes compares the compiled one)."""
     assert ms.me_lds_bytes(7, 4096) == 65696
     assert ms.me_lds_bytes(8, 4095) == 69272
     for case, (N, K, M, S) in CASES.items():
         assert (ms.me_lds_bytes(M, S) > 64 * 1024) == (case in ms.LONG_SCAN), case
-    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), '..',
-                            'radar-signal-simulation-and-target-detection_amd', 'csrc', 'rsp_music.hip')).read()
-    flat = re.sub(r'\s+', ' ', src)
+    csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..',
+                        'radar-signal-simulation-and-target-detection_amd', 'csrc')
+    flat = re.sub(r'\s+', ' ', open(os.path.join(csrc, 'rsp_music_geometry.h')).read())
     assert '#define ME_VW 68 ' in flat
     assert ('me_lu_doubles(int M) { return 5 * 64 * M > 32 * ME_VW ? 5 * 64 * M : 32 * ME_VW; }') in flat
     assert ('return (size_t)4 * ME_VW * 16 + 64 * 16 + 8 * 16 + 3 * 68 * 8 + 64 * 8 + (size_t)me_lu_doubles(M) * 8 + '
             '(size_t)M * 64 * 16 + ((size_t)S + 8) * 8 + 8 * 16;') in flat
-    assert 'if (lds > 64 * 1024) {' in flat
+    assert 'r.raise_lds = r.lds > 64 * 1024;' in open(os.path.join(csrc, 'rsp_music_geometry.cpp')).read()
+    assert 'if (r.raise_lds) e = hipFuncSetAttribute(' in re.sub(r'\s+', ' ', open(os.path.join(csrc, 'rsp_music.hip')).read())
 
 
 def test_f32_restatement_is_far_inside_the_complex_single_tolerances():
