@@ -121,6 +121,17 @@ RSP_HD inline long long k3_map_bytes(const Geometry& g, int real_bytes) {
     return (long long)g.B * g.P * g.G * real_bytes;
 }
 
+struct SynthTarget {          // per-target constants of S4 (fsf:51-73), host-computed
+    int delay;                // delay_samples
+    double amp;
+    double fd_prt;            // doppler_freq * prt   (phase per pulse / 2pi)
+    double dphi;              // channel phase step (rad)
+};
+#define RSP_MAX_SYNTH_TARGETS 64
+struct SynthTargets {         // by value in the kernel arguments (2 KiB): no upload, no sync
+    SynthTarget t[RSP_MAX_SYNTH_TARGETS];
+};
+
 // Frequencies per wave-uniform set of the factored slow-time DFT's Q-point stage (k1_dft_rq)
 #define RQ_RK 6
 // Complex LDS entries of k1_dft_rq's tables, twQ | W_P^i.  Pass 2 prefetches the table rows of

@@ -69,17 +69,6 @@ struct DevConsts {
     double deltaR, deltaV;
 };
 
-struct SynthTarget {          // per-target constants of S4 (fsf:51-73), host-computed
-    int delay;                // delay_samples
-    double amp;
-    double fd_prt;            // doppler_freq * prt   (phase per pulse / 2pi)
-    double dphi;              // channel phase step (rad)
-};
-#define RSP_MAX_SYNTH_TARGETS 64
-struct SynthTargets {         // by value in the kernel arguments (2 KiB): no upload, no sync
-    SynthTarget t[RSP_MAX_SYNTH_TARGETS];
-};
-
 // Launchers (rsp_kernels.hip).  `mode` bits for K1: 1 = apply DBF, 2 = apply MTD.
 hipError_t launch_k1(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, int mode, hipStream_t s);
 hipError_t launch_stream_copy(const void* in, void* out, size_t n16, int ncu, hipStream_t s);

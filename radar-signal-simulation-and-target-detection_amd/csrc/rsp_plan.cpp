@@ -3,6 +3,7 @@
 // include/rsp.h, the device-resident frame queue, and the host stages S10/S11 (two-level BFS
 // clustering, fsf:302-407).
 #include "rsp.h"
+#include "rsp_frame_host.h"
 #include "rsp_internal.h"
 
 #include <algorithm>
@@ -21,9 +22,8 @@
 #include <thread>
 #include <vector>
 
-// Error sink and host-only stages live in rsp_host.cpp (plain C++, built and sanitized
-// without HIP); these are their hidden entry points.
-__attribute__((visibility("hidden"))) int rsp_set_error(int code, const char* fmt, ...);
+// Error sink (declared in rsp_frame_host.h) and host-only stages live in rsp_host.cpp (plain C++,
+// built and sanitized without HIP); this is their hidden entry point.
 __attribute__((visibility("hidden"))) void rsp_cluster_frame(const rsp_cluster_params& cp, std::vector<rsp_detection>& dets,
                                                              std::vector<rsp_target>& final_targets);
 
@@ -45,8 +45,7 @@ namespace {
     } while (0)
 
 using cd = std::complex<double>;
-
-double mround(double x) { return x < 0 ? -std::floor(-x + 0.5) : std::floor(x + 0.5); }
+using cf = std::complex<float>;
 
 struct Lane {
     hipStream_t stream = nullptr;   // the lane's stream: its batches' kernels and detection read-back
@@ -134,8 +133,7 @@ struct rsp_plan {
     Geometry g{};
     DevConsts k{};
     rsp_cluster_params cl{};
-    double deltaR = 0, deltaV = 0;
-    double p_signal_unscaled = 0, c = 0, fs = 0, wavelength = 0, d = 0, prt = 0;
+    SynthConsts sc{};   // what S4 reads of the configuration
     int F = 1;
     int det_bound = 1;   // cells under test per frame: the most detections a frame can have
     size_t esz = 16;   // bytes of one complex element (16: complex128, 8: complex64)
@@ -213,36 +211,24 @@ struct rsp_plan {
         if (!h.empty()) HIPCHK(hipMemcpy(*p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
         return RSP_OK;
     }
+    // n doubles into device memory as the plan's real type: narrowed for a complex-single plan
+    int put_reals(void* d, const double* h, size_t n) {
+        std::vector<float> v(g.prec == RSP_PREC_F64 ? 0 : n);
+        if (g.prec != RSP_PREC_F64) rsp_convert_reals(h, RSP_C128, n, v.data());
+        if (n) HIPCHK(hipMemcpy(d, g.prec == RSP_PREC_F64 ? (const void*)h : v.data(), n * rsz, hipMemcpyHostToDevice));
+        return RSP_OK;
+    }
     // complex / real tables in the plan's precision
+    int upload_reals(const void** p, const double* h, size_t n) {
+        void* q = nullptr;
+        int rc = dalloc_bytes(&q, std::max<size_t>(n, 1) * rsz);
+        *p = q;
+        return rc ? rc : put_reals(q, h, n);
+    }
     int upload_c(const void** p, const std::vector<cd>& h) {
-        if (g.prec == RSP_PREC_F64) {
-            double* q;
-            std::vector<double> v(2 * h.size());
-            for (size_t i = 0; i < h.size(); ++i) { v[2 * i] = h[i].real(); v[2 * i + 1] = h[i].imag(); }
-            int rc = upload(&q, v);
-            *p = q;
-            return rc;
-        }
-        float* q;
-        std::vector<float> v(2 * h.size());
-        for (size_t i = 0; i < h.size(); ++i) { v[2 * i] = (float)h[i].real(); v[2 * i + 1] = (float)h[i].imag(); }
-        int rc = upload(&q, v);
-        *p = q;
-        return rc;
+        return upload_reals(p, reinterpret_cast<const double*>(h.data()), 2 * h.size());
     }
-    int upload_r(const void** p, const std::vector<double>& h) {
-        if (g.prec == RSP_PREC_F64) {
-            double* q;
-            int rc = upload(&q, h);
-            *p = q;
-            return rc;
-        }
-        float* q;
-        std::vector<float> v(h.begin(), h.end());
-        int rc = upload(&q, v);
-        *p = q;
-        return rc;
-    }
+    int upload_r(const void** p, const std::vector<double>& h) { return upload_reals(p, h.data(), h.size()); }
 };
 
 rsp_plan::~rsp_plan() {
@@ -322,6 +308,16 @@ int setup_lane(rsp_plan* p, Lane& L) {
 // frame writes its map.  The synchronous paths (rsp_process_* with out->rdm, process_stage2)
 // run one frame into the lane's own map L.rdm.  With RSP_PLAN_MONOPULSE_COMPLEX K3's S9 reads
 // the complex map, so every frame writes one: the caller's, or the lane's own (F frames).
+// Each frame's count (zeroed by K1, bumped by K3) and detections in the lane's device lists as they
+// are now: again after a growth.
+void lane_det_ptrs(const Lane& L, int nf, FramePtrs& fp) {
+    for (int f = 0; f < nf; ++f) {
+        DevDet* rec = L.dets + (size_t)(L.dcap + 1) * f;
+        fp.count[f] = reinterpret_cast<int*>(rec);
+        fp.dets[f] = rec + 1;
+    }
+}
+
 FramePtrs lane_ptrs(const rsp_plan* p, const Lane& L, const void* const* in, int nf, void* const* rdm) {
     FramePtrs fp{};
     for (int f = 0; f < nf; ++f) {
@@ -329,11 +325,16 @@ FramePtrs lane_ptrs(const rsp_plan* p, const Lane& L, const void* const* in, int
         fp.z[f] = (char*)L.z + p->z_elems * p->esz * f;
         fp.rdm[f] = rdm && rdm[f] ? rdm[f] : (p->g.mono_c ? (char*)L.rdm + p->rdm_elems * p->esz * f : nullptr);
         fp.mag[f] = (char*)L.mag + p->mag_elems * p->rsz * f;
-        DevDet* rec = L.dets + (size_t)(L.dcap + 1) * f;
-        fp.count[f] = reinterpret_cast<int*>(rec);   // zeroed by K1, bumped by K3
-        fp.dets[f] = rec + 1;
     }
+    lane_det_ptrs(L, nf, fp);
     return fp;
+}
+
+// K3 of nf frames on the lane's stream, its detection lists at the lane's present capacity
+hipError_t launch_k3_lane(const rsp_plan* p, const Lane& L, const FramePtrs& fp, int nf) {
+    Geometry g3 = p->g;
+    g3.max_dets = L.dcap;
+    return launch_k3(g3, p->k, fp, nf, L.stream);
 }
 
 // Enqueue K1 -> K2 -> K3 for nf frames on lane L, plus the async detection read-back.
@@ -355,9 +356,7 @@ int launch_batch(rsp_plan* p, Lane& L, const void* const* in, const int* ids, in
     if (L.timed) HIPCHK(hipEventRecord(L.tev[1], L.stream));
     HIPCHK(launch_k2(p->g, p->k, fp, nf, p->g.B * p->g.P, L.stream));
     if (L.timed) HIPCHK(hipEventRecord(L.tev[2], L.stream));
-    Geometry g3 = p->g;
-    g3.max_dets = L.dcap;
-    HIPCHK(launch_k3(g3, p->k, fp, nf, L.stream));
+    HIPCHK(launch_k3_lane(p, L, fp, nf));
     if (L.timed) HIPCHK(hipEventRecord(L.tev[3], L.stream));
     // every frame's count and detections into the lane's mapped pinned lists (only what exists)
     HIPCHK(launch_dets_to_host(L.dets, L.dcap, L.h_dets_dev, L.hcap, nf, L.stream));
@@ -396,15 +395,9 @@ int harvest(rsp_plan* p, Lane& L, std::vector<std::vector<rsp_detection>>* keep_
     if (regrow) {   // rare: grow the device lists, run K3 again with them, read back directly
         if ((rc = lane_dets_alloc(p, L, std::min(p->det_bound, pow2_at_least(maxc))))) return rc;
         FramePtrs fp = L.fp;
-        for (int f = 0; f < L.nf; ++f) {
-            DevDet* rec = L.dets + (size_t)(L.dcap + 1) * f;
-            fp.count[f] = reinterpret_cast<int*>(rec);
-            fp.dets[f] = rec + 1;
-        }
+        lane_det_ptrs(L, L.nf, fp);
         HIPCHK(hipMemset2DAsync(L.dets, sizeof(DevDet) * (L.dcap + 1), 0, sizeof(int), L.nf, L.stream));
-        Geometry g3 = p->g;
-        g3.max_dets = L.dcap;
-        HIPCHK(launch_k3(g3, p->k, fp, L.nf, L.stream));
+        HIPCHK(launch_k3_lane(p, L, fp, L.nf));
         HIPCHK(hipStreamSynchronize(L.stream));
         L.fp = fp;
     }
@@ -516,15 +509,7 @@ int upload_cube(rsp_plan* p, const void* cube, int dtype, int nch, void* d_dst, 
     if ((dtype == RSP_C128) != f64) {
         int rc = ensure_stage(p, elems * p->esz);
         if (rc) return rc;
-        if (f64) {
-            const float* a = (const float*)cube;
-            double* o = (double*)p->h_stage;
-            for (size_t i = 0; i < 2 * elems; ++i) o[i] = a[i];
-        } else {
-            const double* a = (const double*)cube;
-            float* o = (float*)p->h_stage;
-            for (size_t i = 0; i < 2 * elems; ++i) o[i] = (float)a[i];
-        }
+        rsp_convert_reals(cube, dtype, 2 * elems, p->h_stage);
         src = p->h_stage;
     }
     HIPCHK(hipMemcpy2DAsync(d_dst, (size_t)p->g.cpitch * p->esz, src, slab * p->esz, slab * p->esz, nch,
@@ -533,47 +518,23 @@ int upload_cube(rsp_plan* p, const void* cube, int dtype, int nch, void* d_dst, 
     return RSP_OK;
 }
 
-// [B][P][G] complex device maps -> MATLAB column-major [P x G x B] complex double
-int rdm_to_matlab(rsp_plan* p, const void* d_map, double* out) {
-    const int P = p->g.P, G = p->g.G, B = p->g.B;
-    const size_t n = p->rdm_elems;
-    std::vector<double> m(2 * n);
-    if (p->g.prec == RSP_PREC_F64) {
-        HIPCHK(hipMemcpy(m.data(), d_map, n * 16, hipMemcpyDeviceToHost));
-    } else {
-        std::vector<float> t(2 * n);
-        HIPCHK(hipMemcpy(t.data(), d_map, n * 8, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < 2 * n; ++i) m[i] = t[i];
-    }
-    for (int b = 0; b < B; ++b)
-        for (int v = 0; v < P; ++v)
-            for (int r = 0; r < G; ++r) {
-                const size_t i = ((size_t)b * P + v) * G + r;
-                const size_t o = (size_t)v + (size_t)P * ((size_t)r + (size_t)G * b);
-                out[2 * o] = m[2 * i];
-                out[2 * o + 1] = m[2 * i + 1];
-            }
+// n device maps [P][G] of element type S -> MATLAB column-major [P x G x n] of D (rsp_transpose_planes)
+template <class S, class D>
+int maps_to_matlab(const void* d_map, int P, int G, int n, D* out) {
+    std::vector<S> m((size_t)n * P * G);
+    HIPCHK(hipMemcpy(m.data(), d_map, m.size() * sizeof(S), hipMemcpyDeviceToHost));
+    rsp_transpose_planes(m.data(), P, G, n, out);
     return RSP_OK;
 }
 
-// [B-1][P][G] real device maps (K3's S) -> MATLAB column-major [P x G x (B-1)] double
-int smap_to_matlab(rsp_plan* p, const void* d_map, double* out) {
-    const int P = p->g.P, G = p->g.G, NP = p->g.B - 1;
-    const size_t n = (size_t)NP * P * G;
-    std::vector<double> m(n);
-    if (p->g.prec == RSP_PREC_F64) {
-        HIPCHK(hipMemcpy(m.data(), d_map, n * 8, hipMemcpyDeviceToHost));
-    } else {
-        std::vector<float> t(n);
-        HIPCHK(hipMemcpy(t.data(), d_map, n * 4, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n; ++i) m[i] = t[i];
-    }
-    for (int q = 0; q < NP; ++q)
-        for (int v = 0; v < P; ++v)
-            for (int r = 0; r < G; ++r)
-                out[(size_t)v + (size_t)P * ((size_t)r + (size_t)G * q)] = m[((size_t)q * P + v) * G + r];
-    return RSP_OK;
+// ... of the plan's shape and precision, widened: complex maps (the RD maps, [B]) as W = cd and
+// N = cf, real ones (K3's S, [B - 1]) as double and float
+template <class W, class N>
+int plan_maps_to_matlab(const rsp_plan* p, const void* d_map, int n, double* out) {
+    return p->g.prec == RSP_PREC_F64 ? maps_to_matlab<W>(d_map, p->g.P, p->g.G, n, (W*)out)
+                                     : maps_to_matlab<N>(d_map, p->g.P, p->g.G, n, (W*)out);
 }
+int rdm_out(const rsp_plan* p, const void* d_map, double* out) { return plan_maps_to_matlab<cd, cf>(p, d_map, p->g.B, out); }
 
 int run_sync_frame(rsp_plan* p, const void* d_in, int frame_idx, rsp_frame_out* out) {
     int rc = drain_all(p);
@@ -596,20 +557,16 @@ int run_sync_frame(rsp_plan* p, const void* d_in, int frame_idx, rsp_frame_out* 
     p->last_dets = std::move(dets[0]);
     p->last_targets = fr.targets;
     if (out) {
-        const std::vector<rsp_detection>& d = p->last_dets;
-        out->n_dets = (int)d.size();
-        if (out->dets) memcpy(out->dets, d.data(), sizeof(rsp_detection) * std::min<int>(out->dets_cap, (int)d.size()));
-        out->n_targets = (int)fr.targets.size();
-        if (out->targets)
-            memcpy(out->targets, fr.targets.data(), sizeof(rsp_target) * std::min<int>(out->targets_cap, (int)fr.targets.size()));
-        if (out->rdm && (rc = rdm_to_matlab(p, L.rdm, out->rdm))) return rc;
-        if (smap && (rc = smap_to_matlab(p, smap, out->cfar_maps))) return rc;   // device-produced (fsf:184-187)
-        if (out->dets && (int)d.size() > out->dets_cap)
-            return fail(RSP_ERR_OVERFLOW, "%d detections exceed dets_cap %d (all of them: rsp_last_detections)",
-                        (int)d.size(), out->dets_cap);
-        if (out->targets && (int)fr.targets.size() > out->targets_cap)
-            return fail(RSP_ERR_OVERFLOW, "%d targets exceed targets_cap %d (all of them: rsp_last_targets)",
-                        (int)fr.targets.size(), out->targets_cap);
+        // both lists are copied and the maps written before an overflow is reported; the targets
+        // first, so that with both lists short the message that stays is the detections'
+        const int nt = (int)fr.targets.size(), nd = (int)p->last_dets.size();
+        const int rt = rsp_capped_copy(out->targets, fr.targets.data(), nt, out->targets_cap, &out->n_targets,
+                                       "%d targets exceed targets_cap %d (all of them: rsp_last_targets)", nt, out->targets_cap);
+        const int rd = rsp_capped_copy(out->dets, p->last_dets.data(), nd, out->dets_cap, &out->n_dets,
+                                       "%d detections exceed dets_cap %d (all of them: rsp_last_detections)", nd, out->dets_cap);
+        if (out->rdm && (rc = rdm_out(p, L.rdm, out->rdm))) return rc;
+        if (smap && (rc = plan_maps_to_matlab<double, float>(p, smap, p->g.B - 1, out->cfar_maps))) return rc;   // device-produced (fsf:184-187)
+        return rd ? rd : rt;
     }
     return RSP_OK;
 }
@@ -636,38 +593,6 @@ int stage2_device(rsp_plan* p, const void* iq, int dtype) {
     return RSP_OK;
 }
 
-// Gated stage-2 input -> full-PRT [P x N x B] with the gated columns at their PRT positions
-// (zeros elsewhere), the checks of rsp_process_stage2_gated included.
-int stage2_regate(const rsp_plan* p, const void* iq, int dtype, int n_gated, const int32_t* cols,
-                  std::vector<unsigned char>& full) {
-    if (dtype != RSP_C64 && dtype != RSP_C128) return fail(RSP_ERR_INVALID, "unknown dtype %d", dtype);
-    static const int32_t kRefCols[6] = {83, 310, 311, 1033, 1034, 3486};   // main_simulate_echoes_with_array_v2.m:257-264
-    const int32_t* c = cols ? cols : kRefCols;
-    const int P = p->g.P, N = p->g.N, B = p->g.B;
-    int total = 0;
-    for (int k = 0; k < 3; ++k) {
-        if (c[2 * k] < 1 || c[2 * k + 1] < c[2 * k] || c[2 * k + 1] > N)
-            return fail(RSP_ERR_INVALID, "gate columns %d..%d of segment %d outside the %d-sample PRT", c[2 * k],
-                        c[2 * k + 1], k, N);
-        if (k > 0 && c[2 * k] <= c[2 * k - 1])   // ascending and disjoint, like v2:257-264
-            return fail(RSP_ERR_INVALID, "gate columns of segment %d (%d..%d) overlap or precede segment %d (..%d)", k,
-                        c[2 * k], c[2 * k + 1], k - 1, c[2 * k - 1]);
-        total += c[2 * k + 1] - c[2 * k] + 1;
-    }
-    if (total != n_gated) return fail(RSP_ERR_INVALID, "gated input has %d columns, the gate columns cover %d", n_gated, total);
-    // put the gated columns back at their PRT positions (zeros elsewhere): [P x N x B]
-    const size_t es = dtype == RSP_C128 ? 16 : 8, colb = (size_t)P * es;
-    full.assign((size_t)N * B * colb, 0);
-    const unsigned char* src = static_cast<const unsigned char*>(iq);
-    for (int b = 0; b < B; ++b) {
-        int ng = 0;
-        for (int k = 0; k < 3; ++k)
-            for (int col = c[2 * k] - 1; col < c[2 * k + 1]; ++col, ++ng)
-                memcpy(&full[((size_t)b * N + col) * colb], src + ((size_t)b * n_gated + ng) * colb, colb);
-    }
-    return RSP_OK;
-}
-
 // ---- stage-3 range CFAR ----
 int s3_reserve(rsp_plan::DevBuf& b, size_t bytes) {
     if (b.cap >= bytes && b.p) return RSP_OK;
@@ -691,25 +616,10 @@ struct S3Out {   // host outputs of one CFAR call, each optional
     int64_t* n_hits;
 };
 
-// device [n][P][G] -> MATLAB column-major [P x G x n]
-template <class V>
-int s3_to_matlab(const void* d_map, int P, int G, int n, V* out) {
-    const size_t cells = (size_t)n * P * G;
-    std::vector<V> m(cells);
-    HIPCHK(hipMemcpy(m.data(), d_map, cells * sizeof(V), hipMemcpyDeviceToHost));
-    for (int b = 0; b < n; ++b)
-        for (int v = 0; v < P; ++v) {
-            const V* src = &m[((size_t)b * P + v) * G];
-            V* dst = out + (size_t)v + (size_t)P * G * b;
-            for (int r = 0; r < G; ++r) dst[(size_t)P * r] = src[r];
-        }
-    return RSP_OK;
-}
-
-// The map count the kernel's 32-bit hit counter and grid admit
-int s3_check_cells(int P, int G, int n_maps) {
-    if (n_maps < 1 || n_maps > 65535 || (int64_t)n_maps * P * G >= ((int64_t)1 << 31) || (P + RSP_S3_ROWS - 1) / RSP_S3_ROWS > 65535)
-        return fail(RSP_ERR_INVALID, "%d maps of %d x %d cells: 1 .. 65535 maps and fewer than 2^31 cells in all", n_maps, P, G);
+// The argument checks every stage-3 entry starts with
+int s3_args(const rsp_plan* p, const void* in, const rsp_stage3_cfar_params* prm, int64_t hits_cap) {
+    if (!p || !in || !prm) return fail(RSP_ERR_INVALID, "null argument");
+    if (hits_cap < 0) return fail(RSP_ERR_INVALID, "negative hits_cap");
     return RSP_OK;
 }
 
@@ -739,19 +649,13 @@ int s3_run(rsp_plan* p, const S3Desc& d, bool cplx, const void* d_in, int n_maps
         if ((rc = s3_reserve(p->s3_hits, sizeof(rsp_stage3_hit) * (size_t)total))) return rc;   // every hit, then again
     }
     if (o.n_hits) *o.n_hits = total;
-    if (o.amp && (rc = s3_to_matlab<double>(p->s3_amp.p, d.P, d.G, n_maps, o.amp))) return rc;
-    if (o.thr && (rc = s3_to_matlab<double>(p->s3_thr.p, d.P, d.G, n_maps, o.thr))) return rc;
-    if (o.flags && (rc = s3_to_matlab<uint8_t>(p->s3_flags.p, d.P, d.G, n_maps, o.flags))) return rc;
+    if (o.amp && (rc = maps_to_matlab<double>(p->s3_amp.p, d.P, d.G, n_maps, o.amp))) return rc;
+    if (o.thr && (rc = maps_to_matlab<double>(p->s3_thr.p, d.P, d.G, n_maps, o.thr))) return rc;
+    if (o.flags && (rc = maps_to_matlab<uint8_t>(p->s3_flags.p, d.P, d.G, n_maps, o.flags))) return rc;
     if (list && total > 0) {
-        // the device list is in no order: beam, then find() order on [P x G] (r outer, v inner)
-        std::vector<rsp_stage3_hit> h((size_t)total);
+        std::vector<rsp_stage3_hit> h((size_t)total);   // the device list is in no order
         HIPCHK(hipMemcpy(h.data(), p->s3_hits.p, sizeof(rsp_stage3_hit) * (size_t)total, hipMemcpyDeviceToHost));
-        std::sort(h.begin(), h.end(), [](const rsp_stage3_hit& a, const rsp_stage3_hit& b) {
-            if (a.beam_idx != b.beam_idx) return a.beam_idx < b.beam_idx;
-            if (a.r_idx != b.r_idx) return a.r_idx < b.r_idx;
-            return a.v_idx < b.v_idx;
-        });
-        memcpy(o.hits, h.data(), sizeof(rsp_stage3_hit) * (size_t)std::min<int64_t>(total, o.hits_cap));
+        rsp_s3_sorted_hits(h.data(), total, o.hits, o.hits_cap);
     }
     return RSP_OK;
 }
@@ -759,9 +663,36 @@ int s3_run(rsp_plan* p, const S3Desc& d, bool cplx, const void* d_in, int n_maps
 int s3_fused(rsp_plan* p, const void* iq, int dtype, const rsp_stage3_cfar_params* prm, double* mtd_out, const S3Out& o) {
     S3Desc d;
     int rc = rsp_stage3_derive(p->g.P, p->gates, prm, &d);   // refusals before any device work
-    if (rc || (rc = s3_check_cells(d.P, d.G, p->g.B)) || (rc = stage2_device(p, iq, dtype))) return rc;
-    if (mtd_out && (rc = rdm_to_matlab(p, p->d_aux, mtd_out))) return rc;
+    if (rc || (rc = rsp_s3_check_cells(d.P, d.G, p->g.B)) || (rc = stage2_device(p, iq, dtype))) return rc;
+    if (mtd_out && (rc = rdm_out(p, p->d_aux, mtd_out))) return rc;
     return s3_run(p, d, true, p->d_aux, p->g.B, o);
+}
+
+// The profile entries' measurement: run() once to warm up, then iters times between two events on
+// stream s; *ms_per_iter = elapsed / iters.  run returns a status; the first one that is not RSP_OK
+// ends the measurement and is returned.  The events are destroyed on every way out.
+template <class F>
+int time_launches(hipStream_t s, int iters, F run, float* ms_per_iter) {
+    struct Events {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events() {
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+        }
+    } ev;
+    HIPCHK(hipEventCreate(&ev.e0));
+    HIPCHK(hipEventCreate(&ev.e1));
+    int rc = run();
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(ev.e0, s));
+    for (int i = 0; i < iters; ++i)
+        if ((rc = run())) return rc;
+    HIPCHK(hipEventRecord(ev.e1, s));
+    HIPCHK(hipEventSynchronize(ev.e1));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    *ms_per_iter = ms / iters;
+    return RSP_OK;
 }
 
 const char* kStageNames[] = {"k1_dbf_mtd", "k2_pc", "k3_cfar"};
@@ -812,8 +743,7 @@ int32_t rsp_plan_create_ex(const rsp_sig_config* cfg, const rsp_cfar_params* cfa
     p->device = device;
     p->F = opt->frames_per_launch;
     p->cl = *cluster;
-    p->c = cfg->c; p->fs = cfg->fs; p->wavelength = cfg->wavelength; p->d = cfg->element_spacing; p->prt = cfg->prt;
-    p->p_signal_unscaled = pre->P_signal_unscaled;
+    p->sc = SynthConsts{cfg->c, cfg->fs, cfg->wavelength, cfg->element_spacing, cfg->prt, pre->P_signal_unscaled};
     p->esz = opt->precision == RSP_C128 ? 16 : 8;
     p->rsz = p->esz / 2;
     p->g = h.g;
@@ -902,14 +832,8 @@ static int synth_into(rsp_plan* p, const rsp_target_in* t, int nt, int frame_idx
     if (!p->d_tx) return fail(RSP_ERR_INVALID, "plan has no tx_pulse (synthesis path needs precomputed_data.tx_pulse)");
     if (nt < 0 || nt > RSP_MAX_SYNTH_TARGETS)
         return fail(RSP_ERR_INVALID, "0..%d targets supported, got %d", RSP_MAX_SYNTH_TARGETS, nt);
-    SynthTargets tg{};
-    for (int i = 0; i < nt; ++i) {   // fsf:51-72
-        const double delay = 2.0 * t[i].Range / p->c;
-        tg.t[i].delay = (int)mround(delay / (1.0 / p->fs));
-        tg.t[i].fd_prt = 2.0 * t[i].Velocity / p->wavelength * p->prt;
-        tg.t[i].amp = std::sqrt(std::pow(10.0, t[i].SNR_dB / 10.0) * p_noise / p->p_signal_unscaled);
-        tg.t[i].dphi = 2.0 * M_PI * p->d * std::sin(t[i].ElevationAngle * M_PI / 180.0) / p->wavelength;
-    }
+    SynthTargets tg;
+    rsp_synth_targets(p->sc, t, nt, p_noise, &tg);
     // the targets travel in the kernel arguments; the phasor tables are rewritten in stream order
     HIPCHK(launch_synth(p->g, p->d_tx, tg, nt, p->d_stab, frame_idx, seed, std::sqrt(p_noise / 2.0), d_cube, s));
     if (sync) HIPCHK(hipStreamSynchronize(s));   // the caller may read the cube from another stream
@@ -930,20 +854,9 @@ int32_t rsp_profile_synthesis(rsp_plan* p, const rsp_target_in* t, int32_t nt, i
     int rc = drain_all(p);
     if (rc) return rc;
     hipStream_t s = p->lanes[0].stream;
-    if ((rc = synth_into(p, t, nt, 1, 20250101, 1.0, d_cube, s, false))) return rc;   // warm-up
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, s));
-    for (int i = 0; i < iters && !rc; ++i) rc = synth_into(p, t, nt, 1 + i, 20250101, 1.0, d_cube, s, false);
-    HIPCHK(hipEventRecord(e1, s));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (rc) return rc;
-    *ms_out = ms / iters;
+    int k = 0;   // frame 1 warms up, then frames 1 .. iters
+    auto run = [&] { return synth_into(p, t, nt, std::max(k++, 1), 20250101, 1.0, d_cube, s, false); };
+    if ((rc = time_launches(s, iters, run, ms_out))) return rc;
     if (bytes_out) *bytes_out = (int64_t)p->g.C * p->g.N * p->g.P * (int64_t)p->esz;
     return RSP_OK;
 }
@@ -1064,10 +977,10 @@ int32_t rsp_process_targets_multi(rsp_plan* const* plans, int32_t n_plans, const
             if ((rc = drain_all(p))) return rc;
             for (int j = f0; j < f1; ++j) {   // results come back in enqueue order
                 const FrameResult& r = p->results[j - f0];
-                n_out[j] = (int32_t)r.targets.size();
-                memcpy(out + (size_t)j * cap, r.targets.data(), sizeof(rsp_target) * std::min<size_t>(cap, r.targets.size()));
-                if ((int)r.targets.size() > cap) return fail(RSP_ERR_OVERFLOW, "frame %d: %d targets > cap %d", frame_idx[j],
-                                                             (int)r.targets.size(), cap);
+                const int nt = (int)r.targets.size();
+                if ((rc = rsp_capped_copy(out + (size_t)j * cap, r.targets.data(), nt, cap, n_out + j,
+                                          "frame %d: %d targets > cap %d", frame_idx[j], nt, cap)))
+                    return rc;
             }
             p->results.clear();
             return RSP_OK;
@@ -1099,19 +1012,13 @@ int32_t rsp_drain(rsp_plan* p) {
 int32_t rsp_last_detections(const rsp_plan* p, rsp_detection* dets, int32_t cap, int32_t* n) {
     if (!p || !n || cap < 0 || (cap > 0 && !dets)) return fail(RSP_ERR_INVALID, "bad argument");
     const int m = (int)p->last_dets.size();
-    *n = m;
-    if (dets) memcpy(dets, p->last_dets.data(), sizeof(rsp_detection) * std::min(cap, m));
-    if (dets && m > cap) return fail(RSP_ERR_OVERFLOW, "%d detections > cap %d", m, cap);
-    return RSP_OK;
+    return rsp_capped_copy(dets, p->last_dets.data(), m, cap, n, "%d detections > cap %d", m, cap);
 }
 
 int32_t rsp_last_targets(const rsp_plan* p, rsp_target* targets, int32_t cap, int32_t* n) {
     if (!p || !n || cap < 0 || (cap > 0 && !targets)) return fail(RSP_ERR_INVALID, "bad argument");
     const int m = (int)p->last_targets.size();
-    *n = m;
-    if (targets) memcpy(targets, p->last_targets.data(), sizeof(rsp_target) * std::min(cap, m));
-    if (targets && m > cap) return fail(RSP_ERR_OVERFLOW, "%d targets > cap %d", m, cap);
-    return RSP_OK;
+    return rsp_capped_copy(targets, p->last_targets.data(), m, cap, n, "%d targets > cap %d", m, cap);
 }
 
 int32_t rsp_results_count(const rsp_plan* p, int32_t* n_frames, int64_t* n_targets) {
@@ -1131,30 +1038,15 @@ int32_t rsp_results_get(const rsp_plan* p, int32_t i, int32_t* frame_idx, rsp_ta
     if (i < 0 || i >= (int)p->results.size()) return fail(RSP_ERR_INVALID, "result index out of range");
     const FrameResult& r = p->results[i];
     if (frame_idx) *frame_idx = r.frame_idx;
-    if (n_targets) *n_targets = (int32_t)r.targets.size();
     if (n_dets) *n_dets = r.n_dets;
-    if (targets) memcpy(targets, r.targets.data(), sizeof(rsp_target) * std::min<size_t>(cap, r.targets.size()));
-    if (targets && (int)r.targets.size() > cap) return fail(RSP_ERR_OVERFLOW, "cap too small");
-    return RSP_OK;
+    return rsp_capped_copy(targets, r.targets.data(), (int64_t)r.targets.size(), cap, n_targets, "cap too small");
 }
 
 int32_t rsp_results_rows(const rsp_plan* p, double* rows, int64_t cap, int64_t* n_rows) {
     if (!p || !n_rows) return fail(RSP_ERR_INVALID, "bad argument");
     p->results_ready();
     int64_t n = 0;
-    for (const FrameResult& r : p->results) {
-        const size_t nt = r.targets.size();
-        for (size_t i = 0; i < std::max<size_t>(nt, 1); ++i, ++n) {
-            if (!rows || n >= cap) continue;
-            double* o = rows + 5 * n;
-            o[0] = r.frame_idx;
-            if (nt) {
-                o[1] = r.targets[i].Range; o[2] = r.targets[i].Velocity; o[3] = r.targets[i].Angle; o[4] = r.targets[i].Power;
-            } else {   // an empty frame stays visible as one NaN row
-                o[1] = o[2] = o[3] = o[4] = std::nan("");
-            }
-        }
-    }
+    for (const FrameResult& r : p->results) rsp_result_rows(r.frame_idx, r.targets.data(), r.targets.size(), rows, cap, &n);
     *n_rows = n;
     if (rows && n > cap) return fail(RSP_ERR_OVERFLOW, "%lld rows > cap %lld", (long long)n, (long long)cap);
     return RSP_OK;   // rows == NULL: a size query
@@ -1171,8 +1063,8 @@ int32_t rsp_process_stage2(rsp_plan* p, const void* iq, int32_t dtype, double* m
     if (!p || !iq) return fail(RSP_ERR_INVALID, "null argument");
     int rc = stage2_device(p, iq, dtype);
     if (rc) return rc;
-    if (pc_out && (rc = rdm_to_matlab(p, p->lanes[0].rdm, pc_out))) return rc;
-    if (mtd_out && (rc = rdm_to_matlab(p, p->d_aux, mtd_out))) return rc;
+    if (pc_out && (rc = rdm_out(p, p->lanes[0].rdm, pc_out))) return rc;
+    if (mtd_out && (rc = rdm_out(p, p->d_aux, mtd_out))) return rc;
     return RSP_OK;
 }
 
@@ -1180,7 +1072,7 @@ int32_t rsp_process_stage2_gated(rsp_plan* p, const void* iq, int32_t dtype, int
                                  double* mtd_out, double* pc_out) {
     if (!p || !iq) return fail(RSP_ERR_INVALID, "null argument");
     std::vector<unsigned char> full;
-    int rc = stage2_regate(p, iq, dtype, n_gated, cols, full);
+    int rc = rsp_stage2_regate(p->g.P, p->g.N, p->g.B, iq, dtype, n_gated, cols, full);
     if (rc) return rc;
     return rsp_process_stage2(p, full.data(), dtype, mtd_out, pc_out);
 }
@@ -1188,28 +1080,17 @@ int32_t rsp_process_stage2_gated(rsp_plan* p, const void* iq, int32_t dtype, int
 int32_t rsp_stage3_cfar_shape(rsp_plan* p, int32_t P, const int32_t* gates, const double* amp, int32_t n_maps,
                               const rsp_stage3_cfar_params* prm, uint8_t* flags, double* threshold, rsp_stage3_hit* hits,
                               int64_t hits_cap, int64_t* n_hits) {
-    if (!p || !gates || !amp || !prm) return fail(RSP_ERR_INVALID, "null argument");
-    if (hits_cap < 0) return fail(RSP_ERR_INVALID, "negative hits_cap");
     S3Desc d;
-    int rc = rsp_stage3_derive(P, gates, prm, &d);   // refusals before any device work
-    if (rc || (rc = s3_check_cells(d.P, d.G, n_maps))) return rc;
+    int rc = s3_args(p, gates && amp ? amp : nullptr, prm, hits_cap);
+    if (rc || (rc = rsp_stage3_derive(P, gates, prm, &d))) return rc;   // refusals before any device work
+    if ((rc = rsp_s3_check_cells(d.P, d.G, n_maps))) return rc;
     HIPCHK(hipSetDevice(p->device));
     if ((rc = drain_all(p))) return rc;
     // MATLAB column-major [P x G x n] -> [n][P][G] in the plan's precision
     const size_t cells = (size_t)n_maps * d.P * d.G, rs = p->rsz;
     std::vector<unsigned char> host(cells * rs);
-    for (int b = 0; b < n_maps; ++b)
-        for (int v = 0; v < d.P; ++v) {
-            const double* src = amp + (size_t)v + (size_t)d.P * d.G * b;
-            const size_t o = ((size_t)b * d.P + v) * d.G;
-            if (rs == 8) {
-                double* dst = reinterpret_cast<double*>(host.data()) + o;
-                for (int r = 0; r < d.G; ++r) dst[r] = src[(size_t)d.P * r];
-            } else {
-                float* dst = reinterpret_cast<float*>(host.data()) + o;
-                for (int r = 0; r < d.G; ++r) dst[r] = (float)src[(size_t)d.P * r];
-            }
-        }
+    if (rs == 8) rsp_transpose_planes(amp, d.G, d.P, n_maps, reinterpret_cast<double*>(host.data()));
+    else rsp_transpose_planes(amp, d.G, d.P, n_maps, reinterpret_cast<float*>(host.data()));
     if ((rc = s3_reserve(p->s3_in, cells * rs))) return rc;
     HIPCHK(hipMemcpy(p->s3_in.p, host.data(), cells * rs, hipMemcpyHostToDevice));
     const S3Out o{nullptr, flags, threshold, hits, hits_cap, n_hits};
@@ -1225,22 +1106,18 @@ int32_t rsp_stage3_cfar(rsp_plan* p, const double* amp, int32_t n_maps, const rs
 int32_t rsp_process_stage2_cfar(rsp_plan* p, const void* iq, int32_t dtype, const rsp_stage3_cfar_params* prm,
                                 double* mtd_out, double* amp_out, uint8_t* flags, double* threshold, rsp_stage3_hit* hits,
                                 int64_t hits_cap, int64_t* n_hits) {
-    if (!p || !iq || !prm) return fail(RSP_ERR_INVALID, "null argument");
-    if (hits_cap < 0) return fail(RSP_ERR_INVALID, "negative hits_cap");
-    const S3Out o{amp_out, flags, threshold, hits, hits_cap, n_hits};
-    return s3_fused(p, iq, dtype, prm, mtd_out, o);
+    const int rc = s3_args(p, iq, prm, hits_cap);
+    return rc ? rc : s3_fused(p, iq, dtype, prm, mtd_out, S3Out{amp_out, flags, threshold, hits, hits_cap, n_hits});
 }
 
 int32_t rsp_process_stage2_gated_cfar(rsp_plan* p, const void* iq, int32_t dtype, int32_t n_gated, const int32_t* cols,
                                       const rsp_stage3_cfar_params* prm, double* mtd_out, double* amp_out, uint8_t* flags,
                                       double* threshold, rsp_stage3_hit* hits, int64_t hits_cap, int64_t* n_hits) {
-    if (!p || !iq || !prm) return fail(RSP_ERR_INVALID, "null argument");
-    if (hits_cap < 0) return fail(RSP_ERR_INVALID, "negative hits_cap");
     S3Desc d;
-    int rc = rsp_stage3_derive(p->g.P, p->gates, prm, &d);   // before the re-insertion's work too
-    if (rc) return rc;
+    int rc = s3_args(p, iq, prm, hits_cap);
+    if (rc || (rc = rsp_stage3_derive(p->g.P, p->gates, prm, &d))) return rc;   // before the re-insertion's work too
     std::vector<unsigned char> full;
-    if ((rc = stage2_regate(p, iq, dtype, n_gated, cols, full))) return rc;
+    if ((rc = rsp_stage2_regate(p->g.P, p->g.N, p->g.B, iq, dtype, n_gated, cols, full))) return rc;
     const S3Out o{amp_out, flags, threshold, hits, hits_cap, n_hits};
     return s3_fused(p, full.data(), dtype, prm, mtd_out, o);
 }
@@ -1249,7 +1126,7 @@ int32_t rsp_profile_stage3(rsp_plan* p, const rsp_stage3_cfar_params* prm, int32
     if (!p || !prm || iters < 1) return fail(RSP_ERR_INVALID, "bad argument");
     S3Desc d;
     int rc = rsp_stage3_derive(p->g.P, p->gates, prm, &d);
-    if (rc || (rc = s3_check_cells(d.P, d.G, p->g.B))) return rc;
+    if (rc || (rc = rsp_s3_check_cells(d.P, d.G, p->g.B))) return rc;
     if (!p->aux_valid) return fail(RSP_ERR_INVALID, "no stage-2 result on the device: call rsp_process_stage2 first");
     HIPCHK(hipSetDevice(p->device));
     if ((rc = drain_all(p))) return rc;
@@ -1272,16 +1149,8 @@ int32_t rsp_profile_stage3(rsp_plan* p, const rsp_stage3_cfar_params* prm, int32
         HIPCHK(hipStreamSynchronize(L.stream));
         std::vector<double> a(cells);
         HIPCHK(hipMemcpy(a.data(), amp, cells * 8, hipMemcpyDeviceToHost));
-        if (rs == 8) {
-            HIPCHK(hipMemcpy(p->s3_in.p, a.data(), cells * 8, hipMemcpyHostToDevice));
-        } else {
-            std::vector<float> f(a.begin(), a.end());
-            HIPCHK(hipMemcpy(p->s3_in.p, f.data(), cells * 4, hipMemcpyHostToDevice));
-        }
+        if ((rc = p->put_reals(p->s3_in.p, a.data(), cells))) return rc;
     }
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
     for (int s = 0; s < 3; ++s) {
         auto run = [&]() -> hipError_t {
             hipError_t e = hipMemsetAsync(cnt, 0, 4, L.stream);
@@ -1290,23 +1159,11 @@ int32_t rsp_profile_stage3(rsp_plan* p, const rsp_stage3_cfar_params* prm, int32
             if (s == 1) return launch_s3(d, p->g.prec, true, p->d_aux, B, amp, thr, fl, nullptr, cnt, 0, L.stream);
             return launch_s3(d, p->g.prec, true, p->d_aux, B, nullptr, nullptr, nullptr, hits, cnt, cap, L.stream);
         };
-        HIPCHK(run());
-        HIPCHK(hipEventRecord(e0, L.stream));
-        for (int i = 0; i < iters; ++i) HIPCHK(run());
-        HIPCHK(hipEventRecord(e1, L.stream));
-        HIPCHK(hipEventSynchronize(e1));
         float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        if (ms_out) ms_out[s] = ms / iters;
+        if ((rc = time_launches(L.stream, iters, [&]() -> int { HIPCHK(run()); return RSP_OK; }, &ms))) return rc;
+        if (ms_out) ms_out[s] = ms;
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (bytes_out) {   // every cell read once (the halo re-reads are cache hits), every output cell written once
-        const int64_t n = (int64_t)cells;
-        bytes_out[0] = n * ((int64_t)rs + 8 + 1);
-        bytes_out[1] = n * ((int64_t)p->esz + 8 + 8 + 1);
-        bytes_out[2] = n * (int64_t)p->esz;
-    }
+    if (bytes_out) rsp_stage3_bytes((int64_t)cells, (int)p->esz, bytes_out);
     return RSP_OK;
 }
 
@@ -1335,9 +1192,6 @@ int32_t rsp_profile_stages_rdm(rsp_plan* p, const void* const* d_cubes, int32_t 
         fps[j] = lane_ptrs(p, L, in, nf, d_rdms);   // as the queue: complex RDM stores only into d_rdms
     }
     const Geometry& g = p->g;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
     for (int s = 0; s < 3 && s < cap; ++s) {
         int it = 0;
         auto run = [&]() -> hipError_t {
@@ -1346,35 +1200,14 @@ int32_t rsp_profile_stages_rdm(rsp_plan* p, const void* const* d_cubes, int32_t 
             if (s == 1) return launch_k2(g, p->k, fj, nf, g.B * g.P, L.stream);
             // counts are zeroed by K1 in the pipeline; here by a tiny 2-D memset per launch
             hipError_t e = hipMemset2DAsync(L.dets, sizeof(DevDet) * (L.dcap + 1), 0, sizeof(int), nf, L.stream);
-            Geometry g3 = g;
-            g3.max_dets = L.dcap;
-            return e != hipSuccess ? e : launch_k3(g3, p->k, fj, nf, L.stream);
+            return e != hipSuccess ? e : launch_k3_lane(p, L, fj, nf);
         };
-        HIPCHK(run());
-        HIPCHK(hipEventRecord(e0, L.stream));
-        for (int i = 0; i < iters; ++i) HIPCHK(run());
-        HIPCHK(hipEventRecord(e1, L.stream));
-        HIPCHK(hipEventSynchronize(e1));
         float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        if (ms_out) ms_out[s] = ms / iters;
+        if ((rc = time_launches(L.stream, iters, [&]() -> int { HIPCHK(run()); return RSP_OK; }, &ms))) return rc;
+        if (ms_out) ms_out[s] = ms;
     }
     if (frames_out) *frames_out = nf;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (bytes_out) {   // algorithmic bytes per launch (nf frames); DESIGN.md "Measurement"
-        const int64_t es = (int64_t)p->esz, rs = (int64_t)p->rsz;   // complex / real element bytes
-        const int64_t cube = (int64_t)g.C * g.nU * g.P * es;       // used fast-time samples
-        const int64_t z = (int64_t)g.B * g.nU * g.P * es;          // Doppler-domain rows
-        const int64_t mag = (int64_t)g.B * g.P * g.G * rs;         // |RD| map (the RDM stays on chip)
-        if (cap > 0) bytes_out[0] = nf * (cube + z);
-        // the complex RD map, when written: into d_rdms, or (complex-ratio monopulse) into the
-        // lane's own map, which K3 then reads only at the detected cells (2 values per detection,
-        // not a map-sized stream, so K3's bytes stay the magnitude maps)
-        const int64_t rdm = (d_rdms || g.mono_c) ? (int64_t)g.B * g.P * g.G * es : 0;
-        if (cap > 1) bytes_out[1] = nf * (z + mag + rdm);
-        if (cap > 2) bytes_out[2] = nf * k3_map_bytes(g, (int)rs);   // the rows under test (rsp_internal.h)
-    }
+    if (bytes_out) rsp_stage_bytes(g, (int)p->esz, nf, d_rdms || g.mono_c, cap, bytes_out);
     return RSP_OK;
 }
 

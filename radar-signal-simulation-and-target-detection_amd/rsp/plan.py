@@ -16,6 +16,33 @@ def _dptr(a):
     return a.ctypes.data_as(ct.POINTER(ct.c_double))
 
 
+def _complex_arg(a):
+    """A complex array as the library takes it: (Fortran-ordered array, its void pointer, dtype
+    code).  complex64 stays; everything else becomes complex128."""
+    c64 = np.asarray(a).dtype == np.complex64
+    a = np.asfortranarray(a, None if c64 else np.complex128)
+    return a, a.ctypes.data_as(ct.c_void_p), _abi.RSP_C64 if c64 else _abi.RSP_C128
+
+
+def _gate_cols_arg(gate_cols):
+    """((first, last), ...) of the three segments as the six int32 the gated calls take."""
+    return (ct.c_int32 * 6)(*[int(x) for fl in gate_cols for x in fl])
+
+
+def _with_hits(call, first_cap, hits_cap, want_hits):
+    """The stage-3 calls' hit list: ``call(cap, hits_ptr, maps)`` runs the C function (``maps``
+    False: with None for every map pointer) and returns the total.  The first call takes ``hits_cap``
+    records (None: ``first_cap``); when the caller set no capacity and the total is larger, a second
+    one fetches the whole list, and nothing else.  Returns (total, the hits that came back)."""
+    cap = (int(hits_cap) if hits_cap is not None else first_cap) if want_hits else 0
+    hits = np.zeros(max(cap, 1), HIT_DTYPE)
+    total = call(cap, hits.ctypes.data_as(ct.POINTER(_abi.Stage3Hit)) if cap else None, True)
+    if want_hits and hits_cap is None and total > cap:
+        cap, hits = total, np.zeros(total, HIT_DTYPE)
+        total = call(cap, hits.ctypes.data_as(ct.POINTER(_abi.Stage3Hit)), False)
+    return total, hits[:min(total, cap)]
+
+
 def _det_dict(d):
     return {'v_idx': d.v_idx, 'r_idx': d.r_idx, 'pair_idx': d.pair_idx, 'amp': d.amp,
             'Range': d.Range, 'Velocity': d.Velocity, 'Angle': d.Angle}
@@ -252,13 +279,9 @@ class Plan:
         cube = np.asarray(cube)
         if cube.shape != (self.P, self.N, self.C):
             raise ValueError('cube shape %r != (P, N, C) = %r' % (cube.shape, (self.P, self.N, self.C)))
-        if cube.dtype == np.complex64:
-            a, dt = np.asfortranarray(cube), _abi.RSP_C64
-        else:
-            a, dt = np.asfortranarray(cube, np.complex128), _abi.RSP_C128
+        a, ap, dt = _complex_arg(cube)
         o, bufs, dets, tg = self._frame_out(want_rdm, want_cfar)
-        check(lib().rsp_process_cube(self.h, a.ctypes.data_as(ct.c_void_p), dt, _abi.RSP_LAYOUT_PNC,
-                                     int(frame_idx), ct.byref(o)))
+        check(lib().rsp_process_cube(self.h, ap, dt, _abi.RSP_LAYOUT_PNC, int(frame_idx), ct.byref(o)))
         return self._collect(o, bufs, dets, tg)
 
     def process_targets(self, targets, frame_idx=1, seed=20250101, p_noise=1.0, want_rdm=False, want_cfar=False):
@@ -281,30 +304,22 @@ class Plan:
         ``gate_cols``: ((first, last), ...) 1-based PRT columns of the segments of a gated
         input (rsp_process_stage2_gated); None: ``n`` is the full PRT."""
         iq = np.asarray(iq_beams)
-        if iq.dtype == np.complex64:
-            a, dt = np.asfortranarray(iq), _abi.RSP_C64
-        else:
-            a, dt = np.asfortranarray(iq, np.complex128), _abi.RSP_C128
+        a, ap, dt = _complex_arg(iq)
         mtd = np.empty((self.P, self.G, self.B), np.complex128, order='F')
         pc = np.empty((self.P, self.G, self.B), np.complex128, order='F')
         mo, po = mtd.ctypes.data_as(ct.POINTER(ct.c_double)), pc.ctypes.data_as(ct.POINTER(ct.c_double))
         if gate_cols is None:
             if iq.shape != (self.P, self.N, self.B):
                 raise ValueError('iq shape %r != (P, N, B) = %r' % (iq.shape, (self.P, self.N, self.B)))
-            check(lib().rsp_process_stage2(self.h, a.ctypes.data_as(ct.c_void_p), dt, mo, po))
+            check(lib().rsp_process_stage2(self.h, ap, dt, mo, po))
         else:
-            cols = (ct.c_int32 * 6)(*[int(x) for fl in gate_cols for x in fl])
+            cols = _gate_cols_arg(gate_cols)
             if iq.shape[0] != self.P or iq.shape[2] != self.B:
                 raise ValueError('iq shape %r: expected (P, n, B) with P=%d B=%d' % (iq.shape, self.P, self.B))
-            check(lib().rsp_process_stage2_gated(self.h, a.ctypes.data_as(ct.c_void_p), dt, iq.shape[1], cols, mo, po))
+            check(lib().rsp_process_stage2_gated(self.h, ap, dt, iq.shape[1], cols, mo, po))
         return mtd, pc
 
     # ---- stage-3 range CFAR of the stage-2 path ---------------------------------------------
-    @staticmethod
-    def _hits_buf(cap):
-        buf = np.zeros(max(int(cap), 1), HIT_DTYPE)
-        return buf, buf.ctypes.data_as(ct.POINTER(_abi.Stage3Hit))
-
     def stage3_cfar(self, amp, cfar, segments=None, hits_cap=None, want_hits=True):
         """local_execute_cfar (debug_simulated_data_processing_v2.m:419-511) on real amplitude maps
         ``amp`` [P, G] or [P, G, n] (rsp_stage3_cfar; include/rsp.h restates the semantics).
@@ -332,23 +347,18 @@ class Plan:
         fp_, tp = flags.ctypes.data_as(ct.POINTER(ct.c_uint8)), _dptr(thr)
         total = ct.c_int64()
 
-        def call(cap, hp, fp_, tp):
+        def call(cap, hp, maps):
+            tail = (_dptr(a), n, ct.byref(prm), fp_ if maps else None, tp if maps else None, hp, cap, ct.byref(total))
             if segments is None:
-                check(lib().rsp_stage3_cfar(self.h, _dptr(a), n, ct.byref(prm), fp_, tp, hp, cap, ct.byref(total)))
+                check(lib().rsp_stage3_cfar(self.h, *tail))
             else:
                 gates = (ct.c_int32 * 3)(*[int(x) for x in segments])
-                check(lib().rsp_stage3_cfar_shape(self.h, P, gates, _dptr(a), n, ct.byref(prm), fp_, tp, hp, cap,
-                                                  ct.byref(total)))
+                check(lib().rsp_stage3_cfar_shape(self.h, P, gates, *tail))
+            return total.value
 
-        cap = (int(hits_cap) if hits_cap is not None else max(4096, a.size // 8)) if want_hits else 0
-        hits, hp = self._hits_buf(cap)
-        call(cap, hp if cap else None, fp_, tp)
-        if want_hits and hits_cap is None and total.value > cap:   # the whole list: once more, for the list alone
-            cap = total.value
-            hits, hp = self._hits_buf(cap)
-            call(cap, hp, None, None)
+        n_hits, hits = _with_hits(call, max(4096, a.size // 8), hits_cap, want_hits)
         return dict(flags=flags.reshape(shape, order='F'), threshold=thr.reshape(shape, order='F'),
-                    n_hits=total.value, hits=hits[:min(total.value, cap)])
+                    n_hits=n_hits, hits=hits)
 
     def process_stage2_cfar(self, iq_beams, cfar, gate_cols=None, want=STAGE3_WANT, hits_cap=None):
         """process_stage2_mtd followed by the stage-3 range CFAR on |MTD_results| of every beam,
@@ -362,10 +372,7 @@ class Plan:
         if not want <= set(STAGE3_WANT):
             raise ValueError('want: unknown output(s) %r' % (sorted(want - set(STAGE3_WANT)),))
         iq = np.asarray(iq_beams)
-        if iq.dtype == np.complex64:
-            a, dt = np.asfortranarray(iq), _abi.RSP_C64
-        else:
-            a, dt = np.asfortranarray(iq, np.complex128), _abi.RSP_C128
+        a, iqp, dt = _complex_arg(iq)
         shp = (self.P, self.G, self.B)
         if gate_cols is None and iq.shape != (self.P, self.N, self.B):
             raise ValueError('iq shape %r != (P, N, B) = %r' % (iq.shape, (self.P, self.N, self.B)))
@@ -380,26 +387,19 @@ class Plan:
             else:
                 ptr[name] = None
         total = ct.c_int64()
-        iqp = a.ctypes.data_as(ct.c_void_p)
 
-        def call(cap, hp, ptr):
-            tail = (ct.byref(prm), ptr['mtd'], ptr['amp'], ptr['flags'], ptr['threshold'], hp, cap, ct.byref(total))
+        def call(cap, hp, maps):
+            m = ptr if maps else dict.fromkeys(ptr)
+            tail = (ct.byref(prm), m['mtd'], m['amp'], m['flags'], m['threshold'], hp, cap, ct.byref(total))
             if gate_cols is None:
                 check(lib().rsp_process_stage2_cfar(self.h, iqp, dt, *tail))
             else:
-                cols = (ct.c_int32 * 6)(*[int(x) for fl in gate_cols for x in fl])
-                check(lib().rsp_process_stage2_gated_cfar(self.h, iqp, dt, iq.shape[1], cols, *tail))
+                check(lib().rsp_process_stage2_gated_cfar(self.h, iqp, dt, iq.shape[1], _gate_cols_arg(gate_cols), *tail))
+            return total.value
 
-        cap = (int(hits_cap) if hits_cap is not None else max(4096, self.P * self.G * self.B // 8)) if 'hits' in want else 0
-        hits, hp = self._hits_buf(cap)
-        call(cap, hp if cap else None, ptr)
-        if 'hits' in want and hits_cap is None and total.value > cap:
-            cap = total.value
-            hits, hp = self._hits_buf(cap)
-            call(cap, hp, dict.fromkeys(ptr))
-        res['n_hits'] = total.value
+        res['n_hits'], hits = _with_hits(call, max(4096, self.P * self.G * self.B // 8), hits_cap, 'hits' in want)
         if 'hits' in want:
-            res['hits'] = hits[:min(total.value, cap)]
+            res['hits'] = hits
         return res
 
     def profile_stage3(self, cfar, iters=20):

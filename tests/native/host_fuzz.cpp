@@ -1,12 +1,15 @@
 // Host-only driver of librsp's plain-C++ parts (rsp_mat.cpp, rsp_host.cpp, rsp_geometry.cpp,
-// rsp_music_geometry.cpp) for the AddressSanitizer / UBSan build of tests/test_host_asan.py.  Status
-// codes are ignored: only memory errors (reported by the sanitizers, exit code != 0) fail the test.
+// rsp_music_geometry.cpp, rsp_frame_host.cpp) for the AddressSanitizer / UBSan build of
+// tests/test_host_asan.py.  Status codes are ignored, except by the frame mode, which checks what
+// it computes: elsewhere only memory errors (reported by the sanitizers, exit code != 0) fail the test.
 //   host_fuzz mat FILE...     every MAT entry point on every file
 //   host_fuzz cluster SEED    S10/S11 and inter-frame clustering on random lists
 //   host_fuzz geometry SEED   rsp_plan_describe on random plan arguments, most of them valid
 //   host_fuzz music SEED      the MUSIC host module on random line and planar plans, most of them valid
+//   host_fuzz frame SEED      the frame chain's host module: layouts, capped copies, rows, hit order, regating
 //   host_fuzz music-route line|planar c128|c64 N M S peaks|spectrum|eigs
 //                             prints the route of one call (planar: nx = N, ny = 1, an S x 3 grid)
+#include <algorithm>
 #include <cmath>
 #include <complex>
 #include <cstdio>
@@ -16,6 +19,7 @@
 #include <vector>
 
 #include "rsp.h"
+#include "rsp_frame_host.h"
 #include "rsp_music_geometry.h"
 
 static int mat(int argc, char** argv) {
@@ -307,6 +311,231 @@ static int music(unsigned seed) {
     return 0;
 }
 
+// ---- frame: the frame chain's host module (rsp_frame_host.h), results checked ----
+#define FRAME_CHECK(cond, ...)                      \
+    do {                                            \
+        if (!(cond)) {                              \
+            fprintf(stderr, "frame: " __VA_ARGS__); \
+            fprintf(stderr, " [%s]\n", #cond);      \
+            exit(1);                                \
+        }                                           \
+    } while (0)
+
+template <class T>
+static T frame_rnd(std::mt19937_64& g) {
+    if constexpr (std::is_same<T, uint8_t>::value) return (uint8_t)(g() & 0xFF);
+    else if constexpr (std::is_floating_point<T>::value) return (T)std::uniform_real_distribution<double>(-1.0, 1.0)(g);
+    else return T(frame_rnd<typename T::value_type>(g), frame_rnd<typename T::value_type>(g));
+}
+
+// device [n][P][G] of S -> MATLAB [P x G x n] of D, buffers exactly as long as the layout says
+template <class S, class D>
+static void frame_to_matlab(std::mt19937_64& g, int P, int G, int n) {
+    std::vector<S> in((size_t)n * P * G);
+    for (auto& v : in) v = frame_rnd<S>(g);
+    std::vector<D> out(in.size());
+    rsp_transpose_planes(in.data(), P, G, n, out.data());
+    for (int b = 0; b < n; ++b)
+        for (int v = 0; v < P; ++v)
+            for (int r = 0; r < G; ++r)
+                FRAME_CHECK(out[v + (size_t)P * (r + (size_t)G * b)] == static_cast<D>(in[((size_t)b * P + v) * G + r]),
+                            "to MATLAB, P %d G %d n %d at (%d, %d, %d)", P, G, n, v, r, b);
+}
+
+// MATLAB [P x G x n] doubles -> device [n][P][G] of D (narrowed: a (float) cast); in double, and back: the identity
+template <class D>
+static void frame_from_matlab(std::mt19937_64& g, int P, int G, int n) {
+    std::vector<double> in((size_t)n * P * G), back(in.size());
+    for (auto& v : in) v = frame_rnd<double>(g);
+    std::vector<D> out(in.size());
+    rsp_transpose_planes(in.data(), G, P, n, out.data());
+    for (int b = 0; b < n; ++b)
+        for (int v = 0; v < P; ++v)
+            for (int r = 0; r < G; ++r)
+                FRAME_CHECK(out[((size_t)b * P + v) * G + r] == (D)in[v + (size_t)P * (r + (size_t)G * b)],
+                            "from MATLAB, P %d G %d n %d at (%d, %d, %d)", P, G, n, v, r, b);
+    if (std::is_same<D, double>::value) {
+        rsp_transpose_planes(out.data(), P, G, n, back.data());
+        FRAME_CHECK(back == in, "there and back, P %d G %d n %d", P, G, n);
+    }
+}
+
+static void frame_layouts(std::mt19937_64& g, int P, int G, int n) {
+    typedef std::complex<float> cf;
+    typedef std::complex<double> cd;
+    frame_to_matlab<cf, cd>(g, P, G, n);
+    frame_to_matlab<cd, cd>(g, P, G, n);
+    frame_to_matlab<float, double>(g, P, G, n);
+    frame_to_matlab<double, double>(g, P, G, n);
+    frame_to_matlab<uint8_t, uint8_t>(g, P, G, n);
+    frame_from_matlab<float>(g, P, G, n);
+    frame_from_matlab<double>(g, P, G, n);
+    // the cube conversion: 2 scalars per element, widened and narrowed
+    std::vector<double> d((size_t)2 * P * G * n), wide(d.size());
+    std::vector<float> f(d.size());
+    for (auto& v : d) v = frame_rnd<double>(g);
+    rsp_convert_reals(d.data(), RSP_C128, d.size(), f.data());
+    rsp_convert_reals(f.data(), RSP_C64, f.size(), wide.data());
+    for (size_t i = 0; i < d.size(); ++i) FRAME_CHECK(f[i] == (float)d[i] && wide[i] == f[i], "precision conversion at %zu", i);
+}
+
+static bool frame_same_target(const rsp_target& a, const rsp_target& b) { return !memcmp(&a, &b, sizeof a); }
+
+// n records into caps of 0, n - 1, n and n + 1 with a guard record behind each, and a size query
+static void frame_capped_copy(std::mt19937_64& g, int n) {
+    std::vector<rsp_target> src(n);
+    for (auto& t : src) t = rsp_target{frame_rnd<double>(g), frame_rnd<double>(g), frame_rnd<double>(g), frame_rnd<double>(g)};
+    const rsp_target guard = {-1.0, -2.0, -3.0, -4.0};
+    for (int cap : {0, n - 1, n, n + 1}) {
+        if (cap < 0) continue;
+        std::vector<rsp_target> dst((size_t)cap + 1, guard);
+        int32_t got = -7;
+        const int rc = rsp_capped_copy(dst.data(), src.data(), n, cap, &got, "%d targets > cap %d", n, cap);
+        FRAME_CHECK(got == n, "capped copy: n_out %d of %d, cap %d", got, n, cap);
+        FRAME_CHECK(rc == (n > cap ? RSP_ERR_OVERFLOW : RSP_OK), "capped copy: status %d, n %d cap %d", rc, n, cap);
+        char want[64];
+        snprintf(want, sizeof want, "%d targets > cap %d", n, cap);
+        FRAME_CHECK(n <= cap || !strcmp(rsp_last_error(), want), "capped copy: message '%s'", rsp_last_error());
+        for (int i = 0; i < std::min(n, cap); ++i) FRAME_CHECK(frame_same_target(dst[i], src[i]), "capped copy: record %d", i);
+        for (int i = std::min(n, cap); i <= cap; ++i) FRAME_CHECK(frame_same_target(dst[i], guard), "capped copy: wrote record %d, n %d cap %d", i, n, cap);
+    }
+    int64_t got = -7;
+    FRAME_CHECK(rsp_capped_copy((rsp_target*)nullptr, src.data(), n, 0, &got, "cap too small") == RSP_OK && got == n, "size query");
+    FRAME_CHECK(rsp_capped_copy((rsp_target*)nullptr, src.data(), n, 0, (int32_t*)nullptr, "cap too small") == RSP_OK, "no count");
+}
+
+// queued frames with 0, 1 and several targets as rsp_results_rows packs them
+static void frame_rows(std::mt19937_64& g) {
+    auto ri = [&](int lo, int hi) { return std::uniform_int_distribution<int>(lo, hi)(g); };
+    const int nf = ri(3, 8);
+    std::vector<std::vector<rsp_target>> fr(nf);
+    std::vector<int> ids(nf);
+    std::vector<double> want;   // built from the description: 5 doubles per row
+    for (int f = 0; f < nf; ++f) {
+        ids[f] = ri(-3, 1000);
+        fr[f].resize(f == 0 ? 0 : f == 1 ? 1 : f == 2 ? 4 : ri(0, 5));
+        for (auto& t : fr[f]) t = rsp_target{frame_rnd<double>(g), frame_rnd<double>(g), frame_rnd<double>(g), frame_rnd<double>(g)};
+        for (const auto& t : fr[f]) want.insert(want.end(), {(double)ids[f], t.Range, t.Velocity, t.Angle, t.Power});
+        if (fr[f].empty()) want.insert(want.end(), {(double)ids[f], NAN, NAN, NAN, NAN});
+    }
+    const int64_t total = (int64_t)want.size() / 5;
+    auto pack = [&](double* rows, int64_t cap) {
+        int64_t n = 0;
+        for (int f = 0; f < nf; ++f) rsp_result_rows(ids[f], fr[f].data(), fr[f].size(), rows, cap, &n);
+        return n;
+    };
+    FRAME_CHECK(pack(nullptr, 0) == total, "rows: size query");
+    for (int64_t cap : {total, total - 1, (int64_t)0}) {
+        std::vector<double> rows((size_t)5 * (cap + 1), -5.0);   // one guard row behind cap
+        FRAME_CHECK(pack(rows.data(), cap) == total, "rows: count at cap %lld", (long long)cap);
+        for (int64_t i = 0; i < 5 * (cap + 1); ++i) {
+            const double w = i < 5 * cap ? want[i] : -5.0;
+            FRAME_CHECK(std::isnan(w) ? std::isnan(rows[i]) : rows[i] == w, "rows: value %lld at cap %lld", (long long)i, (long long)cap);
+        }
+    }
+}
+
+static void frame_hits(std::mt19937_64& g) {
+    auto ri = [&](int lo, int hi) { return std::uniform_int_distribution<int>(lo, hi)(g); };
+    const int B = ri(1, 4), G = ri(1, 12), P = ri(1, 9);
+    std::vector<rsp_stage3_hit> want;   // beam, then r, then v
+    for (int b = 1; b <= B; ++b)
+        for (int r = 1; r <= G; ++r)
+            for (int v = 1; v <= P; ++v)
+                if (ri(0, 2)) want.push_back(rsp_stage3_hit{v, r, b, 0, frame_rnd<double>(g), frame_rnd<double>(g)});
+    const int64_t n = (int64_t)want.size();
+    for (int64_t cap : {n, n - 1, n + 1, (int64_t)1}) {
+        if (cap < 1) continue;
+        std::vector<rsp_stage3_hit> h = want, out((size_t)cap + 1, rsp_stage3_hit{-1, -1, -1, -1, 0.0, 0.0});
+        std::shuffle(h.begin(), h.end(), g);
+        rsp_s3_sorted_hits(h.data(), n, out.data(), cap);
+        for (int64_t i = 0; i <= cap; ++i) {
+            const rsp_stage3_hit w = i < std::min(n, cap) ? want[i] : rsp_stage3_hit{-1, -1, -1, -1, 0.0, 0.0};
+            FRAME_CHECK(!memcmp(&out[i], &w, sizeof w), "hit order: record %lld of %lld, cap %lld", (long long)i, (long long)n, (long long)cap);
+        }
+    }
+}
+
+// One rsp_stage2_regate call on a gated input of exactly the size the columns say; status and
+// message against `msg` (null: accepted, and every byte of the result is checked)
+static void frame_regate_case(std::mt19937_64& g, int P, int N, int B, int dtype, int n_gated, const int32_t* cols, int want_rc,
+                              const char* msg) {
+    const size_t es = dtype == RSP_C64 ? 8 : 16, colb = (size_t)P * es;
+    std::vector<unsigned char> iq(std::max<size_t>((size_t)std::max(n_gated, 0) * B * colb, 1)), full;
+    for (auto& v : iq) v = (unsigned char)(1 + g() % 255);   // no zero byte: a gated column is told from the fill
+    const int rc = rsp_stage2_regate(P, N, B, iq.data(), dtype, n_gated, cols, full);
+    FRAME_CHECK(rc == want_rc, "regate: status %d, expected %d (%s)", rc, want_rc, msg ? msg : "accepted");
+    if (msg) {
+        FRAME_CHECK(!strcmp(rsp_last_error(), msg), "regate: message '%s', expected '%s'", rsp_last_error(), msg);
+        return;
+    }
+    static const int32_t ref[6] = {83, 310, 311, 1033, 1034, 3486};
+    const int32_t* c = cols ? cols : ref;
+    FRAME_CHECK(full.size() == (size_t)N * B * colb, "regate: %zu bytes", full.size());
+    for (int b = 0; b < B; ++b) {
+        std::vector<int> from(N, -1);   // PRT column -> gated column
+        int ng = 0;
+        for (int k = 0; k < 3; ++k)
+            for (int col = c[2 * k]; col <= c[2 * k + 1]; ++col) from[col - 1] = ng++;
+        for (int col = 0; col < N; ++col)
+            for (size_t i = 0; i < colb; ++i) {
+                const unsigned char w = from[col] < 0 ? 0 : iq[((size_t)b * n_gated + from[col]) * colb + i];
+                FRAME_CHECK(full[((size_t)b * N + col) * colb + i] == w, "regate: beam %d column %d byte %zu", b, col, i);
+            }
+    }
+}
+
+static void frame_regate(std::mt19937_64& g) {
+    auto ri = [&](int lo, int hi) { return std::uniform_int_distribution<int>(lo, hi)(g); };
+    frame_regate_case(g, 2, 3486, 2, RSP_C64, 3404, nullptr, RSP_OK, nullptr);   // the reference's columns
+    frame_regate_case(g, 1, 3486, 1, RSP_C128, 3404, nullptr, RSP_OK, nullptr);
+    const int32_t ok[6] = {2, 4, 6, 6, 9, 12};   // 3 + 1 + 4 columns
+    frame_regate_case(g, 3, 12, 2, 7, 8, ok, RSP_ERR_INVALID, "unknown dtype 7");
+    const int32_t low[6] = {0, 4, 6, 6, 9, 12};
+    frame_regate_case(g, 3, 12, 2, RSP_C64, 9, low, RSP_ERR_INVALID, "gate columns 0..4 of segment 0 outside the 12-sample PRT");
+    frame_regate_case(g, 3, 11, 2, RSP_C64, 8, ok, RSP_ERR_INVALID, "gate columns 9..12 of segment 2 outside the 11-sample PRT");
+    const int32_t over[6] = {2, 6, 6, 6, 9, 12};
+    frame_regate_case(g, 3, 12, 2, RSP_C128, 10, over, RSP_ERR_INVALID,
+                      "gate columns of segment 1 (6..6) overlap or precede segment 0 (..6)");
+    frame_regate_case(g, 3, 12, 2, RSP_C128, 9, ok, RSP_ERR_INVALID, "gated input has 9 columns, the gate columns cover 8");
+    for (int rep = 0; rep < 40; ++rep) {   // accepted: three ascending, disjoint segments inside a small PRT
+        const int P = ri(1, 5), B = ri(1, 3), N = ri(3, 30);
+        int cut[6];
+        for (int& v : cut) v = ri(1, N);
+        std::sort(cut, cut + 6);
+        if (cut[2] == cut[1] || cut[4] == cut[3]) continue;   // segments would share a column
+        const int32_t c[6] = {cut[0], cut[1], cut[2], cut[3], cut[4], cut[5]};
+        const int n_gated = (c[1] - c[0] + 1) + (c[3] - c[2] + 1) + (c[5] - c[4] + 1);
+        frame_regate_case(g, P, N, B, ri(0, 1) ? RSP_C64 : RSP_C128, n_gated, c, RSP_OK, nullptr);
+    }
+}
+
+static int frame(unsigned seed) {
+    std::mt19937_64 g(seed);
+    auto ri = [&](int lo, int hi) { return std::uniform_int_distribution<int>(lo, hi)(g); };
+    const int corners[][3] = {{1, 1, 1}, {1, 70, 5}, {40, 1, 1}, {40, 70, 5}, {1, 1, 5}, {7, 1, 2}, {1, 9, 1}};
+    for (const auto& c : corners) frame_layouts(g, c[0], c[1], c[2]);
+    for (int rep = 0; rep < 300; ++rep) frame_layouts(g, ri(1, 40), ri(1, 70), ri(1, 5));
+    for (int n = 0; n <= 6; ++n) frame_capped_copy(g, n);
+    for (int rep = 0; rep < 50; ++rep) {
+        frame_rows(g);
+        frame_hits(g);
+    }
+    frame_regate(g);
+    // the refusals of the stage-3 map count, and the synthesis constants and byte counts on exact-size arrays
+    FRAME_CHECK(rsp_s3_check_cells(12, 20, 0) == RSP_ERR_INVALID && rsp_s3_check_cells(12, 20, 65536) == RSP_ERR_INVALID &&
+                    rsp_s3_check_cells(32768, 32768, 2) == RSP_ERR_INVALID && rsp_s3_check_cells(12, 20, 13) == RSP_OK, "cell check");
+    std::vector<rsp_target_in> tin(RSP_MAX_SYNTH_TARGETS, rsp_target_in{3000.0, 12.5, -4.0, 10.0});
+    SynthTargets tg;
+    rsp_synth_targets(SynthConsts{3e8, 25e6, 0.1, 0.05, 2e-4, 1.0}, tin.data(), (int)tin.size(), 1.0, &tg);
+    FRAME_CHECK(tg.t[RSP_MAX_SYNTH_TARGETS - 1].delay == 500 && tg.t[0].fd_prt == 2.0 * 12.5 / 0.1 * 2e-4, "synthesis constants");
+    int64_t by[3];
+    rsp_stage3_bytes(100, 16, by);
+    FRAME_CHECK(by[0] == 100 * 17 && by[1] == 100 * 33 && by[2] == 1600, "stage-3 bytes");
+    printf("frame seed %u: ok\n", seed);
+    return 0;
+}
+
 static int music_route_of(char** a) {
     MusicCase c;
     c.planar = !strcmp(a[0], "planar");
@@ -336,7 +565,8 @@ int main(int argc, char** argv) {
     if (argc >= 3 && !strcmp(argv[1], "cluster")) return cluster((unsigned)atoi(argv[2]));
     if (argc >= 3 && !strcmp(argv[1], "geometry")) return geometry((unsigned)atoi(argv[2]));
     if (argc >= 3 && !strcmp(argv[1], "music")) return music((unsigned)atoi(argv[2]));
+    if (argc >= 3 && !strcmp(argv[1], "frame")) return frame((unsigned)atoi(argv[2]));
     if (argc >= 8 && !strcmp(argv[1], "music-route")) return music_route_of(argv + 2);
-    fprintf(stderr, "usage: host_fuzz mat FILE... | cluster SEED | geometry SEED | music SEED | music-route ...\n");
+    fprintf(stderr, "usage: host_fuzz mat FILE... | cluster SEED | geometry SEED | music SEED | frame SEED | music-route ...\n");
     return 2;
 }

@@ -4,8 +4,9 @@ csrc/rsp_mat.cpp (the MAT Level-5 reader/writer that parses untrusted frame file
 csrc/rsp_host.cpp (error sink, S10/S11 clustering of fun_process_single_frame.m:302-407,
 inter-frame association of main_simulate_echoes_with_array_v8_3.m:253-352) and
 csrc/rsp_geometry.cpp (plan geometry, K1 routing and host tables: rsp_plan_describe) and
-csrc/rsp_music_geometry.cpp (the MUSIC plans' checks, sizes, tables, routes and host conversions) are
-compiled with g++ -fsanitize=address,undefined together with tests/native/host_fuzz.cpp and driven over:
+csrc/rsp_music_geometry.cpp (the MUSIC plans' checks, sizes, tables, routes and host conversions) and
+csrc/rsp_frame_host.cpp (the frame chain's map layouts, precision conversions, regating, result lists
+and rows) are compiled with g++ -fsanitize=address,undefined together with tests/native/host_fuzz.cpp and driven over:
   * the reference's MATLAB-written files and scipy-written frames;
   * crafted malformed files: a small-form element claiming 8 inline bytes (the overflow the
     round-1 review found), truncations at every 7th byte, dims larger than the data, a corrupt
@@ -21,7 +22,14 @@ compiled with g++ -fsanitize=address,undefined together with tests/native/host_f
     1024 x 65 and 1025 x 3, null grids, precision 7, a complex-single planar plan): for each accepted
     one every table, the route of all three forms of call, both kinds of scene, the unpacking of
     random device-shaped results (batch 1..4, every combination of null outputs, both precisions)
-    and host snapshots widened and narrowed.
+    and host snapshots widened and narrowed;
+  * per seed, the frame chain's host module on 300 random map shapes (P <= 40, G <= 70, n <= 5, with
+    P = 1, G = 1 and n = 1): every instantiation of the plane transpose against the index formula,
+    there and back in double, capped copies into caps of 0, n - 1, n and n + 1 with a guard record,
+    result rows of frames with 0, 1 and several targets (size query, cap one short), shuffled hit
+    lists against beam / r / v order, and the regating: the default columns at N = 3486, each of the
+    five refusals with its message, and every byte of accepted small cases.  This mode checks its
+    results and exits non-zero on a mismatch.
 test_music_routes pins the routing decisions through the same program (host_fuzz music-route).
 Only sanitizer reports (non-zero exit) fail; the functions' status codes are not checked here
 (tests/test_matio.py does that).
@@ -51,7 +59,8 @@ def fuzz_bin(tmp_path_factory):
     cmd = ['g++', '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined',
            '-fno-omit-frame-pointer', '-I', os.path.join(ROOT, 'include'),
            os.path.join(CSRC, 'rsp_mat.cpp'), os.path.join(CSRC, 'rsp_host.cpp'),
-           os.path.join(CSRC, 'rsp_geometry.cpp'), os.path.join(CSRC, 'rsp_music_geometry.cpp'), '-I', CSRC,
+           os.path.join(CSRC, 'rsp_geometry.cpp'), os.path.join(CSRC, 'rsp_music_geometry.cpp'),
+           os.path.join(CSRC, 'rsp_frame_host.cpp'), '-I', CSRC,
            os.path.join(HERE, 'native', 'host_fuzz.cpp'), '-o', exe, '-lz', '-lpthread']
     subprocess.run(cmd, check=True)
     return exe
@@ -141,6 +150,11 @@ def test_plan_geometry_under_asan(fuzz_bin, seed):
 @pytest.mark.parametrize('seed', [1, 2])
 def test_music_host_under_asan(fuzz_bin, seed):
     _run(fuzz_bin, 'music', str(seed))
+
+
+@pytest.mark.parametrize('seed', [1, 2])
+def test_frame_host_under_asan(fuzz_bin, seed):
+    assert _run(fuzz_bin, 'frame', str(seed)) == 'frame seed %d: ok\n' % seed
 
 
 def _route(exe, kind, prec, N, M, S, want):
