@@ -418,6 +418,71 @@ int32_t rsp_process_stage2_gated_cfar(rsp_plan* plan, const void* iq_gated, int3
 int32_t rsp_profile_stage3(rsp_plan* plan, const rsp_stage3_cfar_params* params, int32_t iters, float* ms_out,
                            int64_t* bytes_out);
 
+/* ---- Doppler cell-averaging CFAR of the stage-2 path ----
+ * local_cfar_detector of main_simulate_echoes_with_array_v3.m:278-314, called at :249-250 on
+ * abs(mtd_results) of one beam: the only CFAR of the reference that slides along the velocity
+ * axis.  Per real amplitude map A [P x G] (P Doppler rows, 1-based row v, every range column on
+ * its own), r = refCells_V >= 1, g = guardCells_V >= 0 and even, h = g / 2:
+ *   gs = max(1, v - h);  lead  = rows max(1, gs - r) .. gs - 1          (empty when gs = 1)
+ *   ge = min(P, v + h);  trail = rows ge + 1 .. min(P, ge + r)          (empty when ge = P)
+ *   (:289-297; where the map ends the window is clipped, not replaced by the opposite one);
+ *   method 0 (CA, the reference, :299-306): noise = sum / n, sum = one running sum over the lead
+ *     rows in ascending order and then the trail rows in ascending order, starting from the first
+ *     cell that exists, n = the number of cells; n = 0: noise = 0;
+ *   method 1 (GOCA), 2 (SOCA): the two other values the script's `method` comment names (:35); the
+ *     reference's function ignores the field, so they are defined here: mL = sum(lead) / nL,
+ *     mT = sum(trail) / nT, each summed ascending with one division; noise = max(mL, mT) (GOCA) or
+ *     min (SOCA); one side empty: the other; both empty: noise = 0;
+ *   threshold = noise * T_CFAR; flag = A > threshold (strict, :309).  A cell with no reference
+ *     cells has threshold 0 and is flagged exactly when A > 0.
+ * No notch and no segments: the whole map is one piece.  Every operation is one correctly rounded
+ * IEEE operation in the plan's precision, in the order above (double for RSP_C128, float for
+ * RSP_C64; T_CFAR, the amplitudes and the count are rounded to it first), so the result is defined
+ * to the bit; thresholds and amplitudes leave the device widened to double.  There are no
+ * sliding-sum updates.  An odd guardCells_V makes the reference index with a non-integer and is
+ * refused. */
+typedef struct rsp_vcfar_params {
+    int32_t refCells_V, guardCells_V, method, reserved;
+    double T_CFAR;
+} rsp_vcfar_params;
+
+/* What the detector does with a map of P rows and G columns (rsp_vcfar_describe). */
+typedef struct rsp_vcfar_info {
+    int32_t P, G;
+    int32_t halo;             /* r + h: rows a window reaches above and below its cell            */
+    int32_t max_halo;         /* the largest r + h the kernel's tile holds                         */
+    int32_t rows, cols;       /* Doppler rows and range columns one workgroup of k_vcfar resolves  */
+    int32_t row_tiles, col_tiles;   /* workgroups per map along either axis                        */
+} rsp_vcfar_info;
+
+/* The checks of the calls below, with the same refusals and messages, and the tiling they use.
+ * RSP_ERR_INVALID: refCells_V < 1, guardCells_V < 0 or odd, method not 0, 1 or 2, T_CFAR not
+ * finite or <= 0, r + h beyond max_halo, P < 1 or G < 1.  `info` may be NULL.  No HIP call is made. */
+int32_t rsp_vcfar_describe(int32_t P, int32_t G, const rsp_vcfar_params* params, rsp_vcfar_info* info);
+
+/* local_cfar_detector on host maps of any shape: amp is real double [P x G x n_maps] column-major;
+ * flags (uint8) and threshold (double) have the same shape.  The plan gives only the device and
+ * the precision.  Any output may be NULL.  Hits are rsp_stage3_hit records ordered by map, then as
+ * find() on [P x G]; *n_hits = flagged cells of all maps, min(*n_hits, hits_cap) entries of `hits`
+ * are written, the first ones in order.  Synchronous; drains the queue first.  Refusals come
+ * before any device work. */
+int32_t rsp_vcfar(rsp_plan* plan, int32_t P, int32_t G, const double* amp, int32_t n_maps, const rsp_vcfar_params* params,
+                  uint8_t* flags, double* threshold, rsp_stage3_hit* hits, int64_t hits_cap, int64_t* n_hits);
+/* rsp_process_stage2, then the detector on |MTD_results| of all B beams without leaving the device
+ * (outputs as rsp_process_stage2_cfar's, every one optional). */
+int32_t rsp_process_stage2_vcfar(rsp_plan* plan, const void* iq_beams, int32_t dtype, const rsp_vcfar_params* params,
+                                 double* mtd_out, double* amp_out, uint8_t* flags, double* threshold,
+                                 rsp_stage3_hit* hits, int64_t hits_cap, int64_t* n_hits);
+/* The same on a gated input (iq_gated, n_gated, cols as rsp_process_stage2_gated). */
+int32_t rsp_process_stage2_gated_vcfar(rsp_plan* plan, const void* iq_gated, int32_t dtype, int32_t n_gated,
+                                       const int32_t* cols, const rsp_vcfar_params* params, double* mtd_out,
+                                       double* amp_out, uint8_t* flags, double* threshold, rsp_stage3_hit* hits,
+                                       int64_t hits_cap, int64_t* n_hits);
+/* Device time of k_vcfar over the plan's B beams of [P x G], in the three forms and with the
+ * algorithmic bytes of rsp_profile_stage3 (the same maps, the same bytes per form). */
+int32_t rsp_profile_vcfar(rsp_plan* plan, const rsp_vcfar_params* params, int32_t iters, float* ms_out,
+                          int64_t* bytes_out);
+
 /* ---- measurement ----
  * Time each device stage `iters` times on the plan's stream with HIP events.  Each launch
  * batches nf = min(n_cubes, frames_per_launch) frames taken from the device-resident

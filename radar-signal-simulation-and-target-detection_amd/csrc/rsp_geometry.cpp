@@ -808,3 +808,44 @@ extern "C" int32_t rsp_stage3_describe(const rsp_sig_config* cfg, const rsp_prec
     info->rows = RSP_S3_ROWS;
     return RSP_OK;
 }
+
+// ---- Doppler CA-CFAR (main_simulate_echoes_with_array_v3.m:278-314) ----
+int rsp_vcfar_derive(int P, int G, const rsp_vcfar_params* prm, VcDesc* out) {
+    if (!prm || !out) return fail(RSP_ERR_INVALID, "null argument");
+    if (P < 1 || G < 1) return fail(RSP_ERR_INVALID, "bad map shape P=%d G=%d", P, G);
+    const int r = prm->refCells_V, g = prm->guardCells_V;
+    if (r < 1) return fail(RSP_ERR_INVALID, "refCells_V must be >= 1, got %d", r);
+    if (g < 0 || (g & 1))
+        return fail(RSP_ERR_INVALID, "guardCells_V must be >= 0 and even (the reference indexes with guardCells_V / 2), got %d", g);
+    if (prm->method < 0 || prm->method > 2)
+        return fail(RSP_ERR_INVALID, "method must be 0 (CA), 1 (GOCA) or 2 (SOCA), got %d", prm->method);
+    if (!std::isfinite(prm->T_CFAR) || prm->T_CFAR <= 0) return fail(RSP_ERR_INVALID, "T_CFAR must be finite and > 0, got %g", prm->T_CFAR);
+    const int64_t halo = (int64_t)r + g / 2;
+    if (halo > RSP_VC_HMAX)
+        return fail(RSP_ERR_INVALID, "CFAR window refCells_V + guardCells_V / 2 = %lld exceeds the kernel's tile halo %d",
+                    (long long)halo, RSP_VC_HMAX);
+    VcDesc d{};
+    d.P = P;
+    d.G = G;
+    d.r = r; d.h = g / 2; d.halo = (int)halo;
+    d.method = prm->method;
+    d.T = prm->T_CFAR;
+    *out = d;
+    return RSP_OK;
+}
+
+extern "C" int32_t rsp_vcfar_describe(int32_t P, int32_t G, const rsp_vcfar_params* params, rsp_vcfar_info* info) {
+    VcDesc d;
+    if (!params) return fail(RSP_ERR_INVALID, "null argument");
+    int rc = rsp_vcfar_derive(P, G, params, &d);
+    if (rc || !info) return rc;
+    info->P = d.P;
+    info->G = d.G;
+    info->halo = d.halo;
+    info->max_halo = RSP_VC_HMAX;
+    info->rows = RSP_VC_ROWS;
+    info->cols = RSP_VC_COLS;
+    info->row_tiles = (d.P + RSP_VC_ROWS - 1) / RSP_VC_ROWS;
+    info->col_tiles = (d.G + RSP_VC_COLS - 1) / RSP_VC_COLS;
+    return RSP_OK;
+}

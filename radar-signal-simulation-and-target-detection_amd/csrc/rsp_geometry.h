@@ -224,6 +224,25 @@ struct S3Desc {          // kernel argument
 // gates[0..2] columns.  RSP_OK, or RSP_ERR_INVALID with the message set.
 int rsp_stage3_derive(int P, const int32_t* gates, const rsp_stage3_cfar_params* prm, S3Desc* out);
 
+// Doppler CA-CFAR (k_vcfar, rsp_vcfar.hip).  A workgroup resolves RSP_VC_ROWS Doppler rows of
+// RSP_VC_COLS range columns (4 waves, lanes across columns) from an LDS tile that holds those rows
+// and the window's halo = r + h rows above and below: halo <= RSP_VC_HMAX is the envelope.  The
+// tile is sized by the halo in use (vc_lds_bytes), not by RSP_VC_HMAX.
+#define RSP_VC_COLS 64
+#define RSP_VC_ROWS 32
+#define RSP_VC_HMAX 32
+struct VcDesc {          // kernel argument
+    int P, G;
+    int r, h, halo;      // refCells_V, guardCells_V / 2, r + h
+    int method;          // 0: CA, 1: GOCA, 2: SOCA
+    double T;            // T_CFAR
+};
+// Dynamic LDS bytes of k_vcfar's amplitude tile for reals of rs bytes
+RSP_HD constexpr size_t vc_lds_bytes(int halo, size_t rs) { return (size_t)(RSP_VC_ROWS + 2 * halo) * RSP_VC_COLS * rs; }
+// The checks of the Doppler CFAR calls and the descriptor for a map of P rows and G columns.
+// RSP_OK, or RSP_ERR_INVALID with the message set.
+int rsp_vcfar_derive(int P, int G, const rsp_vcfar_params* prm, VcDesc* out);
+
 // The checks of rsp_plan_create_ex that need no device and come before its device checks.
 int rsp_plan_check_args(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params* cluster,
                         const rsp_precomputed* pre, const rsp_plan_options* opt);

@@ -85,6 +85,9 @@ hipError_t launch_synth(const Geometry& g, const double* tx, const SynthTargets&
 // caller zeroes.
 hipError_t launch_s3(const S3Desc& d, int prec, bool cplx, const void* in, int n_maps, double* amp, double* thr,
                      uint8_t* flags, rsp_stage3_hit* hits, int* count, int hits_cap, hipStream_t s);
+// Doppler CA-CFAR (rsp_vcfar.hip) of n_maps maps [n_maps][P][G]: inputs and outputs as launch_s3's.
+hipError_t launch_vcfar(const VcDesc& d, int prec, bool cplx, const void* in, int n_maps, double* amp, double* thr,
+                        uint8_t* flags, rsp_stage3_hit* hits, int* count, int hits_cap, hipStream_t s);
 // Queue read-back: count record + the detections of nf frames (device stride dcap + 1 records) into
 // mapped pinned host memory (stride hcap + 1), only the records that exist.
 hipError_t launch_dets_to_host(const void* dets, int dcap, void* host, int hcap, int nf, hipStream_t s);

@@ -616,18 +616,20 @@ struct S3Out {   // host outputs of one CFAR call, each optional
     int64_t* n_hits;
 };
 
-// The argument checks every stage-3 entry starts with
-int s3_args(const rsp_plan* p, const void* in, const rsp_stage3_cfar_params* prm, int64_t hits_cap) {
+// The argument checks every CFAR entry starts with (prm: its parameter struct)
+int s3_args(const rsp_plan* p, const void* in, const void* prm, int64_t hits_cap) {
     if (!p || !in || !prm) return fail(RSP_ERR_INVALID, "null argument");
     if (hits_cap < 0) return fail(RSP_ERR_INVALID, "negative hits_cap");
     return RSP_OK;
 }
 
-// k_s3_cfar over n_maps device maps d_in (complex: the stage-2 result; else real amplitudes of the
-// plan's precision) on lane 0's stream, then the requested outputs to the host.
-int s3_run(rsp_plan* p, const S3Desc& d, bool cplx, const void* d_in, int n_maps, const S3Out& o) {
+// A CFAR kernel over n_maps device maps of P x G on lane 0's stream, then the requested outputs to
+// the host.  launch(amp, thr, flags, hits, count, cap, stream) starts the kernel with the device
+// outputs of this run (launch_s3's / launch_vcfar's trailing arguments).
+template <class Launch>
+int cfar_run(rsp_plan* p, int P, int G, int n_maps, const S3Out& o, Launch launch) {
     Lane& L = p->lanes[0];
-    const size_t cells = (size_t)n_maps * d.P * d.G;
+    const size_t cells = (size_t)n_maps * P * G;
     int rc;
     if (o.amp && (rc = s3_reserve(p->s3_amp, cells * 8))) return rc;
     if (o.thr && (rc = s3_reserve(p->s3_thr, cells * 8))) return rc;
@@ -639,19 +641,19 @@ int s3_run(rsp_plan* p, const S3Desc& d, bool cplx, const void* d_in, int n_maps
     for (int pass = 0;; ++pass) {
         const int cap = list ? (int)std::min<size_t>(p->s3_hits.cap / sizeof(rsp_stage3_hit), (size_t)INT32_MAX) : 0;
         HIPCHK(hipMemsetAsync(p->s3_count.p, 0, 4, L.stream));
-        HIPCHK(launch_s3(d, p->g.prec, cplx, d_in, n_maps, o.amp ? (double*)p->s3_amp.p : nullptr,
-                         o.thr ? (double*)p->s3_thr.p : nullptr, o.flags ? (uint8_t*)p->s3_flags.p : nullptr,
-                         list ? (rsp_stage3_hit*)p->s3_hits.p : nullptr, (int*)p->s3_count.p, cap, L.stream));
+        HIPCHK(launch(o.amp ? (double*)p->s3_amp.p : nullptr, o.thr ? (double*)p->s3_thr.p : nullptr,
+                      o.flags ? (uint8_t*)p->s3_flags.p : nullptr, list ? (rsp_stage3_hit*)p->s3_hits.p : nullptr,
+                      (int*)p->s3_count.p, cap, L.stream));
         HIPCHK(hipStreamSynchronize(L.stream));
         HIPCHK(hipMemcpy(&total, p->s3_count.p, 4, hipMemcpyDeviceToHost));
         if (!list || total <= cap) break;
-        if (pass > 0) return fail(RSP_ERR_DEVICE, "stage-3 hit count changed between two runs on the same map");
+        if (pass > 0) return fail(RSP_ERR_DEVICE, "CFAR hit count changed between two runs on the same map");
         if ((rc = s3_reserve(p->s3_hits, sizeof(rsp_stage3_hit) * (size_t)total))) return rc;   // every hit, then again
     }
     if (o.n_hits) *o.n_hits = total;
-    if (o.amp && (rc = maps_to_matlab<double>(p->s3_amp.p, d.P, d.G, n_maps, o.amp))) return rc;
-    if (o.thr && (rc = maps_to_matlab<double>(p->s3_thr.p, d.P, d.G, n_maps, o.thr))) return rc;
-    if (o.flags && (rc = maps_to_matlab<uint8_t>(p->s3_flags.p, d.P, d.G, n_maps, o.flags))) return rc;
+    if (o.amp && (rc = maps_to_matlab<double>(p->s3_amp.p, P, G, n_maps, o.amp))) return rc;
+    if (o.thr && (rc = maps_to_matlab<double>(p->s3_thr.p, P, G, n_maps, o.thr))) return rc;
+    if (o.flags && (rc = maps_to_matlab<uint8_t>(p->s3_flags.p, P, G, n_maps, o.flags))) return rc;
     if (list && total > 0) {
         std::vector<rsp_stage3_hit> h((size_t)total);   // the device list is in no order
         HIPCHK(hipMemcpy(h.data(), p->s3_hits.p, sizeof(rsp_stage3_hit) * (size_t)total, hipMemcpyDeviceToHost));
@@ -660,12 +662,36 @@ int s3_run(rsp_plan* p, const S3Desc& d, bool cplx, const void* d_in, int n_maps
     return RSP_OK;
 }
 
+// k_s3_cfar over n_maps device maps d_in (complex: the stage-2 result; else real amplitudes of the
+// plan's precision)
+int s3_run(rsp_plan* p, const S3Desc& d, bool cplx, const void* d_in, int n_maps, const S3Out& o) {
+    return cfar_run(p, d.P, d.G, n_maps, o,
+                    [&](double* amp, double* thr, uint8_t* flags, rsp_stage3_hit* hits, int* count, int cap, hipStream_t s) {
+                        return launch_s3(d, p->g.prec, cplx, d_in, n_maps, amp, thr, flags, hits, count, cap, s);
+                    });
+}
+// ... and k_vcfar
+int vc_run(rsp_plan* p, const VcDesc& d, bool cplx, const void* d_in, int n_maps, const S3Out& o) {
+    return cfar_run(p, d.P, d.G, n_maps, o,
+                    [&](double* amp, double* thr, uint8_t* flags, rsp_stage3_hit* hits, int* count, int cap, hipStream_t s) {
+                        return launch_vcfar(d, p->g.prec, cplx, d_in, n_maps, amp, thr, flags, hits, count, cap, s);
+                    });
+}
+
 int s3_fused(rsp_plan* p, const void* iq, int dtype, const rsp_stage3_cfar_params* prm, double* mtd_out, const S3Out& o) {
     S3Desc d;
     int rc = rsp_stage3_derive(p->g.P, p->gates, prm, &d);   // refusals before any device work
     if (rc || (rc = rsp_s3_check_cells(d.P, d.G, p->g.B)) || (rc = stage2_device(p, iq, dtype))) return rc;
     if (mtd_out && (rc = rdm_out(p, p->d_aux, mtd_out))) return rc;
     return s3_run(p, d, true, p->d_aux, p->g.B, o);
+}
+
+int vc_fused(rsp_plan* p, const void* iq, int dtype, const rsp_vcfar_params* prm, double* mtd_out, const S3Out& o) {
+    VcDesc d;
+    int rc = rsp_vcfar_derive(p->g.P, p->g.G, prm, &d);   // refusals before any device work
+    if (rc || (rc = rsp_s3_check_cells(d.P, d.G, p->g.B)) || (rc = stage2_device(p, iq, dtype))) return rc;
+    if (mtd_out && (rc = rdm_out(p, p->d_aux, mtd_out))) return rc;
+    return vc_run(p, d, true, p->d_aux, p->g.B, o);
 }
 
 // The profile entries' measurement: run() once to warm up, then iters times between two events on
@@ -1158,6 +1184,89 @@ int32_t rsp_profile_stage3(rsp_plan* p, const rsp_stage3_cfar_params* prm, int32
             if (s == 0) return launch_s3(d, p->g.prec, false, p->s3_in.p, B, nullptr, thr, fl, nullptr, cnt, 0, L.stream);
             if (s == 1) return launch_s3(d, p->g.prec, true, p->d_aux, B, amp, thr, fl, nullptr, cnt, 0, L.stream);
             return launch_s3(d, p->g.prec, true, p->d_aux, B, nullptr, nullptr, nullptr, hits, cnt, cap, L.stream);
+        };
+        float ms = 0;
+        if ((rc = time_launches(L.stream, iters, [&]() -> int { HIPCHK(run()); return RSP_OK; }, &ms))) return rc;
+        if (ms_out) ms_out[s] = ms;
+    }
+    if (bytes_out) rsp_stage3_bytes((int64_t)cells, (int)p->esz, bytes_out);
+    return RSP_OK;
+}
+
+int32_t rsp_vcfar(rsp_plan* p, int32_t P, int32_t G, const double* amp, int32_t n_maps, const rsp_vcfar_params* prm,
+                  uint8_t* flags, double* threshold, rsp_stage3_hit* hits, int64_t hits_cap, int64_t* n_hits) {
+    VcDesc d;
+    int rc = s3_args(p, amp, prm, hits_cap);
+    if (rc || (rc = rsp_vcfar_derive(P, G, prm, &d))) return rc;   // refusals before any device work
+    if ((rc = rsp_s3_check_cells(d.P, d.G, n_maps))) return rc;
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    // MATLAB column-major [P x G x n] -> [n][P][G] in the plan's precision
+    const size_t cells = (size_t)n_maps * d.P * d.G, rs = p->rsz;
+    std::vector<unsigned char> host(cells * rs);
+    if (rs == 8) rsp_transpose_planes(amp, d.G, d.P, n_maps, reinterpret_cast<double*>(host.data()));
+    else rsp_transpose_planes(amp, d.G, d.P, n_maps, reinterpret_cast<float*>(host.data()));
+    if ((rc = s3_reserve(p->s3_in, cells * rs))) return rc;
+    HIPCHK(hipMemcpy(p->s3_in.p, host.data(), cells * rs, hipMemcpyHostToDevice));
+    const S3Out o{nullptr, flags, threshold, hits, hits_cap, n_hits};
+    return vc_run(p, d, false, p->s3_in.p, n_maps, o);
+}
+
+int32_t rsp_process_stage2_vcfar(rsp_plan* p, const void* iq, int32_t dtype, const rsp_vcfar_params* prm, double* mtd_out,
+                                 double* amp_out, uint8_t* flags, double* threshold, rsp_stage3_hit* hits, int64_t hits_cap,
+                                 int64_t* n_hits) {
+    const int rc = s3_args(p, iq, prm, hits_cap);
+    return rc ? rc : vc_fused(p, iq, dtype, prm, mtd_out, S3Out{amp_out, flags, threshold, hits, hits_cap, n_hits});
+}
+
+int32_t rsp_process_stage2_gated_vcfar(rsp_plan* p, const void* iq, int32_t dtype, int32_t n_gated, const int32_t* cols,
+                                       const rsp_vcfar_params* prm, double* mtd_out, double* amp_out, uint8_t* flags,
+                                       double* threshold, rsp_stage3_hit* hits, int64_t hits_cap, int64_t* n_hits) {
+    VcDesc d;
+    int rc = s3_args(p, iq, prm, hits_cap);
+    if (rc || (rc = rsp_vcfar_derive(p->g.P, p->g.G, prm, &d))) return rc;   // before the re-insertion's work too
+    std::vector<unsigned char> full;
+    if ((rc = rsp_stage2_regate(p->g.P, p->g.N, p->g.B, iq, dtype, n_gated, cols, full))) return rc;
+    const S3Out o{amp_out, flags, threshold, hits, hits_cap, n_hits};
+    return vc_fused(p, full.data(), dtype, prm, mtd_out, o);
+}
+
+int32_t rsp_profile_vcfar(rsp_plan* p, const rsp_vcfar_params* prm, int32_t iters, float* ms_out, int64_t* bytes_out) {
+    if (!p || !prm || iters < 1) return fail(RSP_ERR_INVALID, "bad argument");
+    VcDesc d;
+    int rc = rsp_vcfar_derive(p->g.P, p->g.G, prm, &d);
+    if (rc || (rc = rsp_s3_check_cells(d.P, d.G, p->g.B))) return rc;
+    if (!p->aux_valid) return fail(RSP_ERR_INVALID, "no stage-2 result on the device: call rsp_process_stage2 first");
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    Lane& L = p->lanes[0];
+    const int B = p->g.B;
+    const size_t cells = (size_t)B * d.P * d.G, rs = p->rsz;
+    if ((rc = s3_reserve(p->s3_amp, cells * 8)) || (rc = s3_reserve(p->s3_thr, cells * 8)) ||
+        (rc = s3_reserve(p->s3_flags, cells)) || (rc = s3_reserve(p->s3_count, 16)) || (rc = s3_reserve(p->s3_in, cells * rs)) ||
+        (rc = s3_reserve(p->s3_hits, sizeof(rsp_stage3_hit) * std::min<size_t>(cells, 65536))))
+        return rc;
+    double* amp = (double*)p->s3_amp.p;
+    double* thr = (double*)p->s3_thr.p;
+    uint8_t* fl = (uint8_t*)p->s3_flags.p;
+    rsp_stage3_hit* hits = (rsp_stage3_hit*)p->s3_hits.p;
+    int* cnt = (int*)p->s3_count.p;
+    const int cap = (int)std::min<size_t>(p->s3_hits.cap / sizeof(rsp_stage3_hit), (size_t)INT32_MAX);
+    {   // the real form's input: the magnitudes the complex form writes, in the plan's precision
+        HIPCHK(hipMemsetAsync(cnt, 0, 4, L.stream));
+        HIPCHK(launch_vcfar(d, p->g.prec, true, p->d_aux, B, amp, nullptr, nullptr, nullptr, cnt, 0, L.stream));
+        HIPCHK(hipStreamSynchronize(L.stream));
+        std::vector<double> a(cells);
+        HIPCHK(hipMemcpy(a.data(), amp, cells * 8, hipMemcpyDeviceToHost));
+        if ((rc = p->put_reals(p->s3_in.p, a.data(), cells))) return rc;
+    }
+    for (int s = 0; s < 3; ++s) {
+        auto run = [&]() -> hipError_t {
+            hipError_t e = hipMemsetAsync(cnt, 0, 4, L.stream);
+            if (e != hipSuccess) return e;
+            if (s == 0) return launch_vcfar(d, p->g.prec, false, p->s3_in.p, B, nullptr, thr, fl, nullptr, cnt, 0, L.stream);
+            if (s == 1) return launch_vcfar(d, p->g.prec, true, p->d_aux, B, amp, thr, fl, nullptr, cnt, 0, L.stream);
+            return launch_vcfar(d, p->g.prec, true, p->d_aux, B, nullptr, nullptr, nullptr, hits, cnt, cap, L.stream);
         };
         float ms = 0;
         if ((rc = time_launches(L.stream, iters, [&]() -> int { HIPCHK(run()); return RSP_OK; }, &ms))) return rc;

@@ -20,9 +20,9 @@ import numpy as np
 
 from .config import (named_config, make_config, default_cfar_params, default_cluster_params,
                      v8_2_targets, evolve_targets, V8_FIR, stage2_config, debug_v3_config,
-                     debug_v2_cfar_config)
+                     debug_v2_cfar_config, v3_cfar_params)
 from .precompute import precompute
-from .plan import Plan, process_targets_multi
+from .plan import Plan, process_targets_multi, describe_vcfar
 from ._abi import RspError
 from .matio import load_frame, save_frame
 from .music import MusicPlan, MUSIC_1D, MusicPlan2D, MUSIC_2D
@@ -143,3 +143,22 @@ def local_execute_cfar(mtd_amplitude_map, cfar_params, config, device=0, precisi
     p = _plan_for(config, default_cfar_params(), default_cluster_params(), _stage2_precompute(config), device, precision)
     r = p.stage3_cfar(mtd_amplitude_map, cfar_params, segments=segs, want_hits=False)
     return r['flags'].astype(np.float64), r['threshold']
+
+
+def local_cfar_detector(rdm_abs, params, device=0, precision='c128'):
+    """main_simulate_echoes_with_array_v3.m:278 -- ``[detection_map, threshold_map] =
+    local_cfar_detector(rdm_abs, params)``: the cell-averaging CFAR the reference slides along the
+    velocity axis of ``abs(mtd_results)`` of one beam (:249-250), every range column on its own, with
+    the guard and reference windows clipped where the map ends and the strict ``>`` test
+    (include/rsp.h restates it).
+
+    ``rdm_abs`` is real [P, G] (or [P, G, n]) of any shape; ``params`` has the reference's fields
+    refCells_V, guardCells_V and T_CFAR (config.v3_cfar_params builds the script's).
+    ``params['method']`` is ignored, as the reference's function ignores it: the noise level is always
+    the cell average (``Plan.doppler_cfar`` has the greatest-of and smallest-of variants).  Returns
+    (detection_map bool, threshold_map float64) of the input's shape.  'c128' computes in double like
+    MATLAB, 'c64' in single (thresholds widened to double)."""
+    cfg, cfar, cluster, W, ang, k = named_config('plumbing')   # the plan gives the device and the precision only
+    p = _plan_for(cfg, cfar, cluster, precompute(cfg, W, ang, k, V8_FIR), device, precision)
+    r = p.doppler_cfar(rdm_abs, params, method='ca', want_hits=False)
+    return r['flags'].astype(bool), r['threshold']

@@ -102,6 +102,16 @@ class Stage3Info(ct.Structure):
                 ('max_halo', ct.c_int32), ('chunk', ct.c_int32), ('rows', ct.c_int32)]
 
 
+class VcfarParams(ct.Structure):
+    _fields_ = [('refCells_V', ct.c_int32), ('guardCells_V', ct.c_int32), ('method', ct.c_int32),
+                ('reserved', ct.c_int32), ('T_CFAR', ct.c_double)]
+
+
+class VcfarInfo(ct.Structure):
+    _fields_ = [('P', ct.c_int32), ('G', ct.c_int32), ('halo', ct.c_int32), ('max_halo', ct.c_int32),
+                ('rows', ct.c_int32), ('cols', ct.c_int32), ('row_tiles', ct.c_int32), ('col_tiles', ct.c_int32)]
+
+
 RSP_PLAN_K1_TILED = 1
 RSP_PLAN_MONOPULSE_COMPLEX = 2
 
@@ -235,6 +245,16 @@ PROTOTYPES = {
                                                    ct.POINTER(Stage3Hit), ct.c_int64, ct.POINTER(ct.c_int64)]),
     'rsp_profile_stage3': (ct.c_int32, [_P, ct.POINTER(Stage3CfarParams), ct.c_int32, ct.POINTER(ct.c_float),
                                         ct.POINTER(ct.c_int64)]),
+    'rsp_vcfar_describe': (ct.c_int32, [ct.c_int32, ct.c_int32, ct.POINTER(VcfarParams), ct.POINTER(VcfarInfo)]),
+    'rsp_vcfar': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, _dp, ct.c_int32, ct.POINTER(VcfarParams), _U8, _dp,
+                               ct.POINTER(Stage3Hit), ct.c_int64, ct.POINTER(ct.c_int64)]),
+    'rsp_process_stage2_vcfar': (ct.c_int32, [_P, _P, ct.c_int32, ct.POINTER(VcfarParams), _dp, _dp, _U8, _dp,
+                                              ct.POINTER(Stage3Hit), ct.c_int64, ct.POINTER(ct.c_int64)]),
+    'rsp_process_stage2_gated_vcfar': (ct.c_int32, [_P, _P, ct.c_int32, ct.c_int32, ct.POINTER(ct.c_int32),
+                                                    ct.POINTER(VcfarParams), _dp, _dp, _U8, _dp,
+                                                    ct.POINTER(Stage3Hit), ct.c_int64, ct.POINTER(ct.c_int64)]),
+    'rsp_profile_vcfar': (ct.c_int32, [_P, ct.POINTER(VcfarParams), ct.c_int32, ct.POINTER(ct.c_float),
+                                       ct.POINTER(ct.c_int64)]),
     'rsp_profile_stages': (ct.c_int32, [_P, ct.POINTER(_P), ct.c_int32, ct.c_int32, ct.POINTER(ct.c_float),
                                         ct.POINTER(ct.c_int64), ct.c_int32, ct.POINTER(ct.c_int32)]),
     'rsp_profile_stages_rdm': (ct.c_int32, [_P, ct.POINTER(_P), ct.c_int32, ct.POINTER(_P), ct.c_int32,

@@ -119,6 +119,12 @@ def default_cfar_params():
     return dict(refCells_V=5, guardCells_V=10, refCells_R=5, guardCells_R=10, T_CFAR=8.0, method='GOCA')
 
 
+def v3_cfar_params():
+    """main_simulate_echoes_with_array_v3.m:30-35, the ``cfar_params`` its local_cfar_detector
+    (:278-314) is handed.  The function reads refCells_V, guardCells_V and T_CFAR and ignores the rest."""
+    return dict(refCells_V=4, guardCells_V=6, refCells_R=4, guardCells_R=6, T_CFAR=6.0, method='GOCA')
+
+
 def default_cluster_params():
     """v8:49-51."""
     return dict(max_range_sep=30.0, max_vel_sep=0.4, max_angle_sep=5.0)

@@ -171,6 +171,31 @@ def describe_stage3(P, segments, cfar):
                 chunk=info.chunk, rows=info.rows)
 
 
+VCFAR_METHODS = {'ca': 0, 'goca': 1, 'soca': 2}
+
+
+def _vcfar_params(cfar, method='ca'):
+    """rsp_vcfar_params from the reference's cfar_params field names
+    (main_simulate_echoes_with_array_v3.m:30-35) and ``method``: 'ca' (what the reference computes),
+    'goca' or 'soca', any letter case, or the C value 0, 1, 2.  ``cfar['method']`` is not read."""
+    if isinstance(method, str):
+        if method.lower() not in VCFAR_METHODS:
+            raise ValueError("method must be 'ca', 'goca' or 'soca', got %r" % (method,))
+        method = VCFAR_METHODS[method.lower()]
+    return _abi.VcfarParams(refCells_V=int(cfar['refCells_V']), guardCells_V=int(cfar['guardCells_V']),
+                            method=int(method), T_CFAR=float(cfar['T_CFAR']))
+
+
+def describe_vcfar(P, G, cfar, method='ca'):
+    """What the Doppler CA-CFAR does with a map of ``P`` Doppler rows and ``G`` range columns, without
+    a device (rsp_vcfar_describe): the window's ``halo`` = refCells_V + guardCells_V / 2, the kernel's
+    ``max_halo``, the ``rows`` and ``cols`` of a workgroup's tile and ``row_tiles``, ``col_tiles``.
+    Refusals raise RspError with the code and message the CFAR calls give."""
+    prm, info = _vcfar_params(cfar, method), _abi.VcfarInfo()
+    check(lib().rsp_vcfar_describe(int(P), int(G), ct.byref(prm), ct.byref(info)))
+    return {k: getattr(info, k) for k, _ in _abi.VcfarInfo._fields_}
+
+
 class Plan:
     """One device plan = the reference's per-frame kernel bound to fixed config/precompute.
 
@@ -410,6 +435,84 @@ class Plan:
         prm = _stage3_params(cfar)
         ms, by = (ct.c_float * 3)(), (ct.c_int64 * 3)()
         check(lib().rsp_profile_stage3(self.h, ct.byref(prm), int(iters), ms, by))
+        return {k: (ms[i], by[i]) for i, k in enumerate(('real', 'fused_all', 'fused_hits'))}
+
+    # ---- Doppler CA-CFAR of the stage-2 path --------------------------------------------------
+    def doppler_cfar(self, amp, cfar, method='ca', hits_cap=None, want_hits=True):
+        """local_cfar_detector (main_simulate_echoes_with_array_v3.m:278-314) on real amplitude maps
+        ``amp`` [P, G] or [P, G, n] of any shape (rsp_vcfar; include/rsp.h restates the semantics):
+        the plan gives the device and the precision.  ``cfar``: refCells_V, guardCells_V, T_CFAR;
+        ``method``: 'ca' (the reference), 'goca' or 'soca'.  Returns ``flags`` (uint8) and
+        ``threshold`` (float64) shaped like ``amp``, ``n_hits`` and ``hits``: a HIT_DTYPE array in
+        map-then-find() order, all of them, or the first ``hits_cap``."""
+        a = np.asarray(amp, np.float64)
+        shape = a.shape
+        if a.ndim == 2:
+            a = a[:, :, None]
+        if a.ndim != 3:
+            raise ValueError('amp must be [P, G] or [P, G, n], got shape %r' % (shape,))
+        P, G, n = a.shape
+        a = np.asfortranarray(a)
+        prm = _vcfar_params(cfar, method)
+        flags = np.empty((P, G, n), np.uint8, order='F')
+        thr = np.empty((P, G, n), np.float64, order='F')
+        fp_, tp = flags.ctypes.data_as(ct.POINTER(ct.c_uint8)), _dptr(thr)
+        total = ct.c_int64()
+
+        def call(cap, hp, maps):
+            check(lib().rsp_vcfar(self.h, P, G, _dptr(a), n, ct.byref(prm), fp_ if maps else None, tp if maps else None,
+                                  hp, cap, ct.byref(total)))
+            return total.value
+
+        n_hits, hits = _with_hits(call, max(4096, a.size // 8), hits_cap, want_hits)
+        return dict(flags=flags.reshape(shape, order='F'), threshold=thr.reshape(shape, order='F'),
+                    n_hits=n_hits, hits=hits)
+
+    def process_stage2_vcfar(self, iq_beams, cfar, method='ca', gate_cols=None, want=STAGE3_WANT, hits_cap=None):
+        """process_stage2_mtd followed by the Doppler CA-CFAR on |MTD_results| of every beam, without
+        leaving the device (rsp_process_stage2_vcfar / _gated_vcfar).  ``iq_beams``, ``gate_cols``,
+        ``want`` and ``hits_cap`` as ``process_stage2_cfar``; ``cfar`` and ``method`` as
+        ``doppler_cfar``."""
+        want = set(want)
+        if not want <= set(STAGE3_WANT):
+            raise ValueError('want: unknown output(s) %r' % (sorted(want - set(STAGE3_WANT)),))
+        iq = np.asarray(iq_beams)
+        a, iqp, dt = _complex_arg(iq)
+        shp = (self.P, self.G, self.B)
+        if gate_cols is None and iq.shape != (self.P, self.N, self.B):
+            raise ValueError('iq shape %r != (P, N, B) = %r' % (iq.shape, (self.P, self.N, self.B)))
+        if gate_cols is not None and (iq.ndim != 3 or iq.shape[0] != self.P or iq.shape[2] != self.B):
+            raise ValueError('iq shape %r: expected (P, n, B) with P=%d B=%d' % (iq.shape, self.P, self.B))
+        prm = _vcfar_params(cfar, method)
+        res, ptr = {}, {}
+        for name, dtype in (('mtd', np.complex128), ('amp', np.float64), ('flags', np.uint8), ('threshold', np.float64)):
+            if name in want:
+                res[name] = np.empty(shp, dtype, order='F')
+                ptr[name] = res[name].ctypes.data_as(ct.POINTER(ct.c_uint8 if name == 'flags' else ct.c_double))
+            else:
+                ptr[name] = None
+        total = ct.c_int64()
+
+        def call(cap, hp, maps):
+            m = ptr if maps else dict.fromkeys(ptr)
+            tail = (ct.byref(prm), m['mtd'], m['amp'], m['flags'], m['threshold'], hp, cap, ct.byref(total))
+            if gate_cols is None:
+                check(lib().rsp_process_stage2_vcfar(self.h, iqp, dt, *tail))
+            else:
+                check(lib().rsp_process_stage2_gated_vcfar(self.h, iqp, dt, iq.shape[1], _gate_cols_arg(gate_cols), *tail))
+            return total.value
+
+        res['n_hits'], hits = _with_hits(call, max(4096, self.P * self.G * self.B // 8), hits_cap, 'hits' in want)
+        if 'hits' in want:
+            res['hits'] = hits
+        return res
+
+    def profile_vcfar(self, cfar, method='ca', iters=20):
+        """HIP-event time of k_vcfar over the B beams of the plan's last stage-2 result
+        (rsp_profile_vcfar), in the three forms of ``profile_stage3``."""
+        prm = _vcfar_params(cfar, method)
+        ms, by = (ct.c_float * 3)(), (ct.c_int64 * 3)()
+        check(lib().rsp_profile_vcfar(self.h, ct.byref(prm), int(iters), ms, by))
         return {k: (ms[i], by[i]) for i, k in enumerate(('real', 'fused_all', 'fused_hits'))}
 
     # ---- device-resident queue -------------------------------------------------------------
