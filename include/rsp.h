@@ -228,6 +228,34 @@ typedef struct rsp_k3_tiling {
 } rsp_k3_tiling;
 int32_t rsp_query_k3_tiling(const rsp_plan* plan, rsp_k3_tiling* out);
 
+/* How the plan lays out the pulse-compression kernel k2_pc (read-only; the fields the launcher
+ * and the kernel read).  One slot per segment of the stitched row: 0 narrow (direct FIR), 1 medium,
+ * 2 long (overlap-save).  Tests assert it, so that a case runs the instantiation, the block size
+ * and the block count it is there to cover. */
+typedef struct rsp_k2_segment {
+    int32_t present;          /* 0: the segment has no gate; every other field is then 0        */
+    int32_t type;             /* 0: direct FIR, 1: FFT overlap-save                             */
+    int32_t ga, gb;           /* stitched gates [ga, gb), 0-based                               */
+    int32_t seg_lo;           /* 0-based first fast-time sample of the segment                  */
+    int32_t lo, hi;           /* 0-based sample window that reaches a kept gate, inclusive      */
+    int32_t Ls, ntaps, delay; /* FIR: segment length (the circshift's modulus), taps, shift     */
+    int32_t Lh, M, V;         /* overlap-save: filter length, block points, M - Lh + 1 gates
+                                 per block                                                      */
+    int32_t nblocks;          /* overlap-save blocks per row; block b holds the gates
+                                 [ga + b V, min(gb, ga + (b + 1) V))                            */
+    int32_t rows_per_wg;      /* rows of the [prtNum x beam_num] row set per workgroup          */
+} rsp_k2_segment;
+typedef struct rsp_k2_layout {
+    int32_t k2_pts;           /* complex LDS points per workgroup: 4096 or 2560                 */
+    int32_t wg_per_cu;        /* workgroups per CU the launched instantiation is sized for:
+                                 4 (k2_pc<T, 4>, k2_pts = 2560) or 2 (k2_pc<T, 2>)              */
+    int32_t NZ;               /* samples per slab of the K1 -> K2 buffer (K1's NT)              */
+    int32_t nseg, njobs;      /* present segments; (segment, block) jobs                        */
+    int32_t nwg;              /* workgroups per frame                                           */
+    rsp_k2_segment seg[3];
+} rsp_k2_layout;
+int32_t rsp_query_k2_layout(const rsp_plan* plan, rsp_k2_layout* out);
+
 /* What rsp_plan_create_ex would build for these arguments on a device of `ncu` compute units,
  * without a device: the same checks (opt->device aside), refusals and messages, and the values
  * rsp_query_sizes and rsp_query_k1_route report for the created plan.  `sizes` / `route` may be
@@ -239,6 +267,10 @@ int32_t rsp_plan_describe(const rsp_sig_config* cfg, const rsp_cfar_params* cfar
 int32_t rsp_plan_describe_k3(const rsp_sig_config* cfg, const rsp_cfar_params* cfar,
                              const rsp_cluster_params* cluster, const rsp_precomputed* pre,
                              const rsp_plan_options* opt, int32_t ncu, rsp_k3_tiling* tiling);
+/* The same for rsp_query_k2_layout's values. */
+int32_t rsp_plan_describe_k2(const rsp_sig_config* cfg, const rsp_cfar_params* cfar,
+                             const rsp_cluster_params* cluster, const rsp_precomputed* pre,
+                             const rsp_plan_options* opt, int32_t ncu, rsp_k2_layout* layout);
 
 /* Cube-in path: S5..S11 of fun_process_single_frame on one host cube
  * (layout RSP_LAYOUT_PNC, dtype RSP_C64 or RSP_C128; converted to the plan's precision

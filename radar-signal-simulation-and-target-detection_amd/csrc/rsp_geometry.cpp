@@ -723,6 +723,28 @@ void rsp_fill_k3_tiling(const Geometry& g, rsp_k3_tiling* out) {
     out->rows = g.cfar_rows;
 }
 
+void rsp_fill_k2_layout(const Geometry& g, const int32_t gates[RSP_MAX_SEG], rsp_k2_layout* out) {
+    *out = rsp_k2_layout{};
+    out->k2_pts = g.k2_pts;
+    out->wg_per_cu = k2_wg_per_cu(g);   // launch_k2_p's choice of instantiation
+    out->NZ = g.NZ;
+    out->nseg = g.nseg;
+    out->njobs = g.njobs;
+    out->nwg = g.nwg_k2;
+    for (int slot = 0, q = 0; slot < RSP_MAX_SEG && q < g.nseg; ++slot) {
+        if (gates[slot] <= 0) continue;   // derive_segments skips it
+        const SegDesc& s = g.segs[q++];
+        rsp_k2_segment& o = out->seg[slot];
+        o.present = 1;
+        o.type = s.type;
+        o.ga = s.ga; o.gb = s.gb;
+        o.seg_lo = s.seg_lo; o.lo = s.lo; o.hi = s.hi;
+        o.Ls = s.Ls; o.ntaps = s.ntaps; o.delay = s.delay;
+        o.Lh = s.Lh; o.M = s.M; o.V = s.V; o.nblocks = s.nblocks;
+        o.rows_per_wg = s.rows_per_wg;
+    }
+}
+
 extern "C" int32_t rsp_plan_describe(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params* cluster,
                                      const rsp_precomputed* pre, const rsp_plan_options* opt, int32_t ncu, rsp_sizes* sizes,
                                      rsp_k1_route* route) {
@@ -743,6 +765,18 @@ extern "C" int32_t rsp_plan_describe_k3(const rsp_sig_config* cfg, const rsp_cfa
     PlanHost h;
     if ((rc = rsp_plan_derive(cfg, cfar, cluster, pre, opt, ncu, &h))) return rc;
     if (tiling) rsp_fill_k3_tiling(h.g, tiling);
+    return RSP_OK;
+}
+
+extern "C" int32_t rsp_plan_describe_k2(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params* cluster,
+                                        const rsp_precomputed* pre, const rsp_plan_options* opt, int32_t ncu,
+                                        rsp_k2_layout* layout) {
+    int rc = rsp_plan_check_args(cfg, cfar, cluster, pre, opt);
+    if (rc) return rc;
+    PlanHost h;
+    if ((rc = rsp_plan_derive(cfg, cfar, cluster, pre, opt, ncu, &h))) return rc;
+    const int32_t gates[RSP_MAX_SEG] = {pre->N_gate_narrow, pre->N_gate_medium, pre->N_gate_long};
+    if (layout) rsp_fill_k2_layout(h.g, gates, layout);
     return RSP_OK;
 }
 

@@ -121,6 +121,10 @@ RSP_HD inline long long k3_map_bytes(const Geometry& g, int real_bytes) {
     return (long long)g.B * g.P * g.G * real_bytes;
 }
 
+// Workgroups per CU that K2's instantiation is sized for: k2_pc<T, 4> for the 2560-point
+// workgroups, k2_pc<T, 2> for RSP_K2_POINTS (launch_k2_p, rsp_fill_k2_layout).
+RSP_HD inline int k2_wg_per_cu(const Geometry& g) { return g.k2_pts != RSP_K2_POINTS ? 4 : 2; }
+
 struct SynthTarget {          // per-target constants of S4 (fsf:51-73), host-computed
     int delay;                // delay_samples
     double amp;
@@ -251,8 +255,11 @@ int rsp_plan_check_args(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, 
 int rsp_plan_derive(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params* cluster,
                     const rsp_precomputed* pre, const rsp_plan_options* opt, int ncu, PlanHost* out);
 
-// The one filling routine of rsp_query_sizes / rsp_query_k1_route / rsp_query_k3_tiling and
-// rsp_plan_describe / rsp_plan_describe_k3.
+// The one filling routine of rsp_query_sizes / rsp_query_k1_route / rsp_query_k3_tiling /
+// rsp_query_k2_layout and rsp_plan_describe / rsp_plan_describe_k3 / rsp_plan_describe_k2.
+// gates = N_gate_narrow, N_gate_medium, N_gate_long: Geometry::segs holds the present segments
+// only, in that order.
 void rsp_fill_sizes(const Geometry& g, int det_bound, rsp_sizes* s);
 void rsp_fill_k1_route(const Geometry& g, rsp_k1_route* out);
 void rsp_fill_k3_tiling(const Geometry& g, rsp_k3_tiling* out);
+void rsp_fill_k2_layout(const Geometry& g, const int32_t gates[RSP_MAX_SEG], rsp_k2_layout* out);

@@ -2722,7 +2722,7 @@ template <class T>
 static hipError_t launch_k2_p(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, int rows,
                               hipStream_t s) {
     // workgroups sized for the 2560-point block (complex double): 4 per CU, the row's LDS alone
-    const bool w4 = g.k2_pts != RSP_K2_POINTS;
+    const bool w4 = k2_wg_per_cu(g) == 4;
     const size_t lds = w4 ? (size_t)g.k2_pts * sizeof(cx<T>)
                           : (size_t)(k2_lds_data(g.k2_pts, k2_sh<T>()) + k2_tw_lds_max()) * sizeof(cx<T>);
     const auto kernel = w4 ? k2_pc<T, 4> : k2_pc<T, 2>;

@@ -842,6 +842,12 @@ int32_t rsp_query_k3_tiling(const rsp_plan* p, rsp_k3_tiling* out) {
     return RSP_OK;
 }
 
+int32_t rsp_query_k2_layout(const rsp_plan* p, rsp_k2_layout* out) {
+    if (!p || !out) return fail(RSP_ERR_INVALID, "null argument");
+    rsp_fill_k2_layout(p->g, p->gates, out);
+    return RSP_OK;
+}
+
 int32_t rsp_process_cube(rsp_plan* p, const void* cube, int32_t dtype, int32_t layout, int32_t frame_idx,
                          rsp_frame_out* out) {
     if (!p || !cube) return fail(RSP_ERR_INVALID, "null argument");

@@ -86,6 +86,16 @@ class K3Tiling(ct.Structure):
                 ('n_tiles', ct.c_int32), ('n_bands', ct.c_int32), ('VB', ct.c_int32), ('rows', ct.c_int32)]
 
 
+class K2Segment(ct.Structure):
+    _fields_ = [(n, ct.c_int32) for n in ('present', 'type', 'ga', 'gb', 'seg_lo', 'lo', 'hi', 'Ls', 'ntaps', 'delay',
+                                          'Lh', 'M', 'V', 'nblocks', 'rows_per_wg')]
+
+
+class K2Layout(ct.Structure):
+    _fields_ = [('k2_pts', ct.c_int32), ('wg_per_cu', ct.c_int32), ('NZ', ct.c_int32), ('nseg', ct.c_int32),
+                ('njobs', ct.c_int32), ('nwg', ct.c_int32), ('seg', K2Segment * 3)]
+
+
 class Stage3CfarParams(ct.Structure):
     _fields_ = [('refCells_R', ct.c_int32), ('saveCells_R', ct.c_int32), ('CFARmethod_R', ct.c_int32),
                 ('MTD_0v_num', ct.c_int32), ('T_CFAR', ct.c_double)]
@@ -204,6 +214,10 @@ PROTOTYPES = {
     'rsp_plan_describe_k3': (ct.c_int32, [ct.POINTER(SigConfig), ct.POINTER(CfarParams), ct.POINTER(ClusterParams),
                                           ct.POINTER(Precomputed), ct.POINTER(PlanOptions), ct.c_int32,
                                           ct.POINTER(K3Tiling)]),
+    'rsp_query_k2_layout': (ct.c_int32, [_P, ct.POINTER(K2Layout)]),
+    'rsp_plan_describe_k2': (ct.c_int32, [ct.POINTER(SigConfig), ct.POINTER(CfarParams), ct.POINTER(ClusterParams),
+                                          ct.POINTER(Precomputed), ct.POINTER(PlanOptions), ct.c_int32,
+                                          ct.POINTER(K2Layout)]),
     'rsp_process_cube': (ct.c_int32, [_P, _P, ct.c_int32, ct.c_int32, ct.c_int32, ct.POINTER(FrameOut)]),
     'rsp_process_targets': (ct.c_int32, [_P, ct.POINTER(TargetIn), ct.c_int32, ct.c_int32, ct.c_uint64,
                                          ct.c_double, ct.POINTER(FrameOut)]),

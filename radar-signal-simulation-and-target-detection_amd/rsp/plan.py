@@ -141,6 +141,27 @@ def describe_k3(config, cfar_params, cluster_params, precomputed_data, precision
     return _tiling_dict(t)
 
 
+K2_SEGMENTS = ('narrow', 'medium', 'long')   # rsp_k2_layout.seg's slots
+
+
+def _k2_dict(L):
+    segs = [{k: getattr(s, k) for k, _ in _abi.K2Segment._fields_ if k != 'present'} if s.present else None
+            for s in L.seg]
+    return dict(k2_pts=L.k2_pts, wg_per_cu=L.wg_per_cu, NZ=L.NZ, nseg=L.nseg, njobs=L.njobs, nwg=L.nwg, segments=segs)
+
+
+def describe_k2(config, cfar_params, cluster_params, precomputed_data, precision='c128', k1_tiled=False, ncu=256):
+    """``Plan.k2_layout()`` of the plan these arguments would give, without a device
+    (rsp_plan_describe_k2); refusals as ``describe``."""
+    keep = []
+    cfg, cfar, cluster, pre = _marshal(config, cfar_params, cluster_params, precomputed_data, keep)
+    opt = _options(0, 1, precision, k1_tiled, 'amplitude')
+    L = _abi.K2Layout()
+    check(lib().rsp_plan_describe_k2(ct.byref(cfg), ct.byref(cfar), ct.byref(cluster), ct.byref(pre), ct.byref(opt),
+                                     int(ncu), ct.byref(L)))
+    return _k2_dict(L)
+
+
 HIT_DTYPE = np.dtype([('v_idx', np.int32), ('r_idx', np.int32), ('beam_idx', np.int32), ('reserved', np.int32),
                       ('amp', np.float64), ('threshold', np.float64)])   # rsp_stage3_hit
 STAGE3_WANT = ('mtd', 'amp', 'flags', 'threshold', 'hits')
@@ -258,6 +279,16 @@ class Plan:
         t = _abi.K3Tiling()
         check(lib().rsp_query_k3_tiling(self.h, ct.byref(t)))
         return _tiling_dict(t)
+
+    def k2_layout(self):
+        """How this plan lays out the pulse-compression kernel (rsp_query_k2_layout): ``k2_pts`` LDS
+        points per workgroup, ``wg_per_cu`` (4: k2_pc<T, 4>, 2: k2_pc<T, 2>), ``NZ``, ``nseg``,
+        ``njobs``, ``nwg`` and ``segments``: for narrow, medium, long (K2_SEGMENTS) a dict of
+        ``type, ga, gb, seg_lo, lo, hi, Ls, ntaps, delay, Lh, M, V, nblocks, rows_per_wg``, or None
+        for a segment without gates."""
+        L = _abi.K2Layout()
+        check(lib().rsp_query_k2_layout(self.h, ct.byref(L)))
+        return _k2_dict(L)
 
     # ---- synchronous frame paths ---------------------------------------------------------
     def _frame_out(self, want_rdm, want_cfar):

@@ -196,15 +196,191 @@ def k3_band_edges(P, win, tiling):
     return out
 
 
+# ---- K2 (pulse compression) block counts, filter lengths and FIR edges -------------------------
+# One case per path of k2_pc that the named configurations, the route / K3 cases and
+# test_k2_blocks.py do not reach.  Every case has 8 channels and, unless it says otherwise, 16
+# pulses x 3 beams: 48 rows, so that workgroups of 32 or 64 rows have a partly filled last one, and
+# K1 picks NT = 8.  args = rsp.config.make_config's arguments; pre = entries set in both precompute
+# dicts (the narrow FIR's taps and shift).  layout = what Plan.k2_layout() / rsp.plan.describe_k2
+# must report, per precision where the two differ: wg_per_cu (4: k2_pc<T, 4>, 2: k2_pc<T, 2>),
+# k2_pts, NZ and, per segment, (M, Lh, V, nblocks, rows_per_wg), for the narrow FIR (ntaps, delay,
+# Ls, rows_per_wg), None for a segment without gates.  The tests assert it, so a change of
+# build_fft_segment's cost model cannot silently move a case off the path it is there for.
+# test_k2_cases.py holds the oracle's preconditions and the coverage the table must reach.
+_PW = dict(gap_duration=(2.84e-6, 4e-6, 6e-6))
+_PLUMB = dict(point_PRT=1024, tao=(0.16e-6, 2e-6, 6e-6), gap_duration=(2.84e-6, 8e-6, 12e-6))
+_POW2 = dict(point_PRT=2048, tao=(0.16e-6, 1e-6, 2e-6), **_PW)
+_V8FIR = (35, 17)   # C.V8_FIR's taps and fir_delay
+
+
+def _fft(M, Lh, nblocks, rows):
+    return dict(M=M, Lh=Lh, V=M - Lh + 1, nblocks=nblocks, rows_per_wg=rows)
+
+
+def _fir(Ls, rows, ntaps=_V8FIR[0], delay=_V8FIR[1]):
+    return dict(ntaps=ntaps, delay=delay, Ls=Ls, rows_per_wg=rows)
+
+
+def _k2(args, both, c128=None, c64=None, pre=None, P=16, B=3, why=()):
+    return dict(P=P, B=B, C=8, args=args, pre=pre or {}, why=frozenset(why),
+                layout={'c128': dict(both, **(c128 or {})), 'c64': dict(both, **(c64 or {}))})
+
+
+_US = 1e-6
+_X2_LONG = _fft(2560, 700, 1, 1)
+_W4 = dict(wg_per_cu=4, k2_pts=2560)    # complex double beside a 2560-point block: k2_pc<double, 4>
+_W2 = dict(wg_per_cu=2, k2_pts=4096)    # k2_pc<T, 2>
+_NZ8 = dict(_W2, NZ=8)
+_POW2_SEGS = dict(_POW2, point_prt_segments=(62, 301, 1203))
+_POW2_FFT = (_fft(128, 25, 3, 32), _fft(256, 50, 6, 16))
+_TAPS8 = [3.0, -1.0, 4.0, 1.5, -5.0, 9.0, 2.0, -6.0]
+
+
+def _w4(narrow, medium, long_):
+    """k2_pc<double, 4> in complex double (2048 / M rows per workgroup), k2_pc<float, 2> in complex
+    single (4096 / M rows); the 2560-point block takes one row in either."""
+    wide = [sg if sg['M'] == 2560 else dict(sg, rows_per_wg=2 * sg['rows_per_wg']) for sg in (medium, long_)]
+    return dict(both=dict(NZ=8), c128=dict(_W4, seg=(narrow, medium, long_)), c64=dict(_W2, seg=(narrow, *wide)))
+
+
+K2_CASES = {
+    # k2_pc<double, 4> with more than one block per segment: 128 x 3 (16 rows per workgroup, last
+    # block 93 gates) beside 2560 x 1
+    'w4-mb128': _k2(dict(point_PRT=4096, tao=(0.16 * _US, 1 * _US, 28 * _US), point_prt_segments=(228, 301, 1860)),
+                    **_w4(_fir(4092, 8), _fft(128, 25, 3, 16), _X2_LONG),
+                    why=('w4-multiblock', 'multiblock-multirow')),
+    # the same with a 10-tap medium filter: 64 x 3 in k2_pc<double, 4> (32 rows per workgroup)
+    'w4-m64': _k2(dict(point_PRT=4096, tao=(0.16 * _US, 0.4 * _US, 28 * _US), point_prt_segments=(228, 120, 1860)),
+                  **_w4(_fir(4092, 8), _fft(64, 10, 3, 32), _X2_LONG),
+                  why=('w4-multiblock', 'zaddr-multiblock')),
+    # 512 x 4 (last block 61 gates) and the 2560-point block twice (last block 1839 gates)
+    'w4-mb-all': _k2(dict(point_PRT=8192, point_prt_segments=(228, 1000, 3700)),
+                     **_w4(_fir(8188, 8), _fft(512, 200, 4, 4), _fft(2560, 700, 2, 1)),
+                     why=('w4-multiblock', 'w4-2560-multiblock', 'multiblock-multirow')),
+    # 2560 x 3; G = 5949 is no multiple of 4 and the narrow segment's last 4-gate group has 2 gates
+    'w4-3blk': _k2(dict(point_PRT=8192, point_prt_segments=(226, 723, 5000)),
+                   **_w4(_fir(8188, 8), _fft(1024, 200, 1, 2), _fft(2560, 700, 3, 1)),
+                   why=('w4-2560-multiblock', 'g-odd', 'fir-tail')),
+    # 2-per-CU workgroups of 32 and 16 rows with 3 and 6 blocks; g1 = 62 ends in a partial 4-gate group
+    'mb-pow2': _k2(_POW2_SEGS, dict(_NZ8, seg=(_fir(2044, 8), *_POW2_FFT)), why=('multiblock-multirow', 'fir-tail')),
+    # the same blocks behind the persistent K1 (P = 128, B = 8): NT = 4 in complex double
+    'mb-pow2-nt4': _k2(_POW2_SEGS, dict(_W2, seg=(_fir(2044, 8), *_POW2_FFT)), c128=dict(NZ=4), c64=dict(NZ=8),
+                       P=128, B=8, why=('multiblock-multirow', 'nz4')),
+    # every last block exactly full: 3 x 104 and 6 x 207 gates
+    'exact-v': _k2(dict(_POW2, point_prt_segments=(62, 312, 1242)), dict(_NZ8, seg=(_fir(2044, 8), *_POW2_FFT)),
+                   why=('exact-full',)),
+    # 64 x 3 (Lh = 10, last block 10 gates, 64 rows per workgroup: 48 of them in use) and 128 x 5
+    'm64-mb': _k2(dict(point_PRT=1024, tao=(0.16 * _US, 0.4 * _US, 1 * _US), point_prt_segments=(30, 120, 500), **_PW),
+                  dict(_NZ8, seg=(_fir(1020, 8), _fft(64, 10, 3, 64), _fft(128, 25, 5, 32))),
+                  why=('zaddr-multiblock', 'multiblock-multirow', 'fir-tail')),
+    # a one-tap medium filter: Lh1 = 0, V = M
+    'lh1': _k2(dict(point_PRT=1024, tao=(0.16 * _US, 0.04 * _US, 1 * _US), point_prt_segments=(30, 50, 600), **_PW),
+               dict(_NZ8, seg=(_fir(1020, 8), _fft(64, 1, 1, 64), _fft(128, 25, 6, 32))), why=('lh-1',)),
+    # the 700-tap long filter in a 1024-point block: V = 325, Lh - 1 > M / 2
+    'lh-heavy': _k2(dict(point_PRT=4096, point_prt_segments=(228, 723, 100)),
+                    dict(_NZ8, seg=(_fir(4092, 8), _fft(1024, 200, 1, 4), _fft(1024, 700, 1, 4))), why=('lh-gt-half',)),
+    # a segment without gates: nseg = 2, the job list and k2order without it
+    'no-narrow': _k2(dict(_PLUMB, point_prt_segments=(0, 192, 256)),
+                     dict(_NZ8, seg=(None, _fft(256, 50, 1, 16), _fft(512, 150, 1, 8))), why=('no-narrow',)),
+    'no-medium': _k2(dict(_PLUMB, point_prt_segments=(64, 0, 256)),
+                     dict(_NZ8, seg=(_fir(1020, 8), None, _fft(512, 150, 1, 8))), why=('no-medium',)),
+    'no-long': _k2(dict(_PLUMB, point_prt_segments=(64, 192, 0)),
+                   dict(_NZ8, seg=(_fir(1020, 8), _fft(256, 50, 1, 16), None)), why=('no-long',)),
+    # narrow only, whole-row window: g1 + fir_delay > Ls = 1020, so gates 1003 .. 1014 wrap to the
+    # segment's start and the 4-gate group 1000 .. 1003 straddles the wrap; 1015 is no multiple of 4
+    'fir-wrap': _k2(dict(_PLUMB, point_prt_segments=(1015, 0, 0)), dict(_NZ8, seg=(_fir(1020, 3), None, None)),
+                    why=('fir-wrap-group', 'fir-tail', 'g-odd', 'no-medium', 'no-long')),
+    # 8 distinct, non-symmetric taps (an even count below the 4-deep unroll's multiple) and a negative
+    # shift: gates 0 .. 2 wrap to the segment's end
+    'fir-8tap': _k2(_POW2_SEGS, dict(_NZ8, seg=(_fir(2044, 2, 8, -3), *_POW2_FFT)),
+                    pre=dict(MF_narrow=_TAPS8, fir_delay=-3), why=('fir-wrap-group', 'fir-neg-delay', 'fir-even-taps')),
+    # one tap, no shift: PADL = 0, the tap loop's zero-trip case
+    'fir-1tap': _k2(_POW2_SEGS, dict(_NZ8, seg=(_fir(2044, 8, 1, 0), *_POW2_FFT)),
+                    pre=dict(MF_narrow=[2.0], fir_delay=0), why=('fir-1tap',)),
+}
+# every condition the cases are there for (test_k2_cases.py derives them from describe_k2)
+K2_CONDITIONS = frozenset().union(*(kc['why'] for kc in K2_CASES.values()))
+
+
+def k2_scenario(name):
+    kc = K2_CASES[name]
+    cfg = C.make_config(prtNum=kc['P'], channel_num=kc['C'], beam_num=kc['B'], **kc['args'])
+    W, ang, k = plumbing_weights(cfg)
+    return cfg, _route_cfar(kc['P'], 'small'), C.default_cluster_params(), W, ang, k
+
+
+def k2_summary(L):
+    """Plan.k2_layout() / describe_k2 reduced to the fields a K2_CASES layout records."""
+    def seg(sg):
+        if sg is None:
+            return None
+        return {k: sg[k] for k in (('ntaps', 'delay', 'Ls', 'rows_per_wg') if sg['type'] == 0 else
+                                   ('M', 'Lh', 'V', 'nblocks', 'rows_per_wg'))}
+    return dict(wg_per_cu=L['wg_per_cu'], k2_pts=L['k2_pts'], NZ=L['NZ'], seg=tuple(seg(sg) for sg in L['segments']))
+
+
+def k2_blocks(L):
+    """(segment slot, block, g0, gend) of every K2 job of a layout: the narrow segment as one
+    block, an overlap-save segment's blocks as k2_fft_job's g0 = ga + blk V, gend = min(gb, g0 + V)."""
+    out = []
+    for slot, sg in enumerate(L['segments']):
+        if sg is None:
+            continue
+        if sg['type'] == 0:
+            out.append((slot, 0, sg['ga'], sg['gb']))
+            continue
+        for b in range(sg['nblocks']):
+            g0 = sg['ga'] + b * sg['V']
+            out.append((slot, b, g0, min(sg['gb'], g0 + sg['V'])))
+    return out
+
+
+def k2_target_gates(L):
+    """The gates a K2 case's targets sit on: the middle of every present segment, and one within Lh
+    gates of a block boundary (just past the first boundary inside a segment of several blocks;
+    else just past the start of the first overlap-save segment)."""
+    segs = [sg for sg in L['segments'] if sg is not None]
+    gates = [(sg['ga'] + sg['gb']) // 2 for sg in segs]
+    fft = [sg for sg in segs if sg['type'] == 1]
+    multi = [sg for sg in fft if sg['nblocks'] > 1]
+    if multi:
+        gates.append(multi[-1]['ga'] + multi[-1]['V'] + min(2, multi[-1]['Lh'] - 1))
+    elif fft:
+        gates.append(fft[0]['ga'] + min(fft[0]['Lh'], fft[0]['gb'] - fft[0]['ga']) // 2)
+    return gates
+
+
+def k2_targets(s, L):
+    """Three or four targets of a K2 case, placed from the case's own axes on k2_target_gates."""
+    pre, sc = s['pre_o'], s['cfg']['Sig_Config']
+    ang, B = pre['beam_angles_deg'], sc['beam_num']
+    vmax = sc['wavelength'] / (2 * sc['prt'])
+    vel, snr = (0.11, -0.2, 0.3, -0.36), (8.0, 5.0, 10.0, 6.0)
+    return [dict(Range=float(pre['range_axis'][max(g, 1)]), Velocity=vel[i % 4] * vmax,
+                 ElevationAngle=float(ang[i % B]) + 0.5, SNR_dB=snr[i % 4])
+            for i, g in enumerate(k2_target_gates(L))]
+
+
+def k2_cube(s, L, prec, frame_idx=1):
+    """The cube of a K2 case: its targets plus Philox noise, complex128, or rounded to complex64
+    for the c64 plans."""
+    raw = chain.synthesize_echo(k2_targets(s, L), s['cfg'], s['pre_o']) + chain.philox_noise(s['cfg'], frame_idx, SEED)
+    return raw if prec == 'c128' else raw.astype(np.complex64)
+
+
 def scenario(name):
     if name in ROUTE_CASES:
         cfg, cfar, clus, W, ang, k = _route_scenario(name)
     elif name in K3_CASES:
         cfg, cfar, clus, W, ang, k = k3_scenario(name)
+    elif name in K2_CASES:
+        cfg, cfar, clus, W, ang, k = k2_scenario(name)
     else:
         cfg, cfar, clus, W, ang, k = C.named_config(name)
     pre_o = oracle_precompute.precompute(cfg, W, ang, k, C.V8_FIR)
     pre_p = product_precompute(cfg, W, ang, k, C.V8_FIR)
+    for key, val in K2_CASES.get(name, {}).get('pre', {}).items():   # a K2 case's own narrow FIR
+        pre_o[key] = pre_p[key] = val
     return dict(name=name, cfg=cfg, cfar=cfar, clus=clus, pre_o=pre_o, pre_p=pre_p)
 
 

@@ -1,10 +1,10 @@
 // Host-only driver of librsp's plain-C++ parts (rsp_mat.cpp, rsp_host.cpp, rsp_geometry.cpp,
 // rsp_music_geometry.cpp, rsp_frame_host.cpp) for the AddressSanitizer / UBSan build of
-// tests/test_host_asan.py.  Status codes are ignored, except by the frame mode, which checks what
-// it computes: elsewhere only memory errors (reported by the sanitizers, exit code != 0) fail the test.
+// tests/test_host_asan.py.  Status codes are ignored, except by the frame mode and the geometry
+// mode's K2 layout, which check what they compute: elsewhere only memory errors (reported by the sanitizers, exit code != 0) fail the test.
 //   host_fuzz mat FILE...     every MAT entry point on every file
 //   host_fuzz cluster SEED    S10/S11 and inter-frame clustering on random lists
-//   host_fuzz geometry SEED   rsp_plan_describe on random plan arguments, most of them valid
+//   host_fuzz geometry SEED   rsp_plan_describe and rsp_plan_describe_k2 on random plan arguments, most of them valid
 //   host_fuzz music SEED      the MUSIC host module on random line and planar plans, most of them valid
 //   host_fuzz frame SEED      the frame chain's host module: layouts, capped copies, rows, hit order, regating
 //   host_fuzz music-route line|planar c128|c64 N M S peaks|spectrum|eigs
@@ -162,10 +162,39 @@ static int geometry(unsigned seed) {
         rsp_plan_options opt = {0, 1, ri(0, 1) ? RSP_C128 : RSP_C64, ri(0, 3)};
         rsp_sizes sz;
         rsp_k1_route rt;
-        n_ok += rsp_plan_describe(&cfg, &cf, &cl, &pre, &opt, ri(0, 1) ? 256 : 0, &sz, &rt) == RSP_OK;
+        const int ncu = ri(0, 1) ? 256 : 0;
+        const int rc = rsp_plan_describe(&cfg, &cf, &cl, &pre, &opt, ncu, &sz, &rt);
+        n_ok += rc == RSP_OK;
+        // the K2 layout of the same arguments: the same verdict, and segments that tile the gates
+        rsp_k2_layout k2;
+        const int rc2 = rsp_plan_describe_k2(&cfg, &cf, &cl, &pre, &opt, ncu, &k2);
+        if (rc2 != rc || rsp_plan_describe_k2(&cfg, &cf, &cl, &pre, &opt, ncu, nullptr) != rc) {
+            fprintf(stderr, "geometry seed %u set %d: rsp_plan_describe %d, rsp_plan_describe_k2 %d\n", seed, rep, rc, rc2);
+            return 1;
+        }
+        if (rc2 == RSP_OK) {
+            const int gates[3] = {g1, g2, g3};
+            int nseg = 0, njobs = 0, at = 0;
+            bool ok = (k2.wg_per_cu == 4) == (k2.k2_pts == 2560) && (k2.wg_per_cu == 2) == (k2.k2_pts == 4096);
+            for (int q = 0; q < 3; ++q) {
+                const rsp_k2_segment& sg = k2.seg[q];
+                ok = ok && (sg.present != 0) == (gates[q] > 0);
+                if (!sg.present) continue;
+                ++nseg;
+                njobs += sg.type ? sg.nblocks : 1;
+                ok = ok && sg.type == (q > 0) && sg.ga == at && sg.gb == at + gates[q] && sg.rows_per_wg >= 1;
+                if (sg.type) ok = ok && sg.V == sg.M - sg.Lh + 1 && sg.V >= 1 && (sg.nblocks - 1) * sg.V < gates[q] && sg.nblocks * sg.V >= gates[q];
+                at = sg.gb;
+            }
+            if (!ok || nseg != k2.nseg || njobs != k2.njobs || at != G) {
+                fprintf(stderr, "geometry seed %u set %d: inconsistent K2 layout\n", seed, rep);
+                return 1;
+            }
+        }
     }
     printf("geometry seed %u: %d of %d parameter sets accepted\n", seed, n_ok, n_sets);
     rsp_plan_describe(nullptr, nullptr, nullptr, nullptr, nullptr, 256, nullptr, nullptr);
+    rsp_plan_describe_k2(nullptr, nullptr, nullptr, nullptr, nullptr, 256, nullptr);
     return 0;
 }
 

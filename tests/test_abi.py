@@ -47,7 +47,7 @@ STRUCTS = {'rsp_sig_config': _abi.SigConfig, 'rsp_cfar_params': _abi.CfarParams,
            'rsp_music_scene': _abi.MusicScene, 'rsp_music_out': _abi.MusicOut, 'rsp_track_point': _abi.TrackPoint,
            'rsp_inter_frame_params': _abi.InterFrameParams, 'rsp_track': _abi.Track,
            'rsp_plan_options': _abi.PlanOptions, 'rsp_k1_route': _abi.K1Route,
-           'rsp_k3_tiling': _abi.K3Tiling}
+           'rsp_k3_tiling': _abi.K3Tiling, 'rsp_k2_segment': _abi.K2Segment, 'rsp_k2_layout': _abi.K2Layout}
 
 
 def test_struct_layouts_match_header():
@@ -89,6 +89,8 @@ def test_null_arguments_are_rejected():
     assert lib.rsp_query_k1_route(None, None) == _abi.RSP_ERR_INVALID
     assert lib.rsp_query_k3_tiling(None, None) == _abi.RSP_ERR_INVALID
     assert lib.rsp_plan_describe_k3(None, None, None, None, None, 256, None) == _abi.RSP_ERR_INVALID
+    assert lib.rsp_query_k2_layout(None, None) == _abi.RSP_ERR_INVALID
+    assert lib.rsp_plan_describe_k2(None, None, None, None, None, 256, None) == _abi.RSP_ERR_INVALID
     assert lib.rsp_drain(None) == _abi.RSP_ERR_INVALID
     assert lib.rsp_process_cube(None, None, 1, 0, 0, None) == _abi.RSP_ERR_INVALID
     assert lib.rsp_stage_name(99) == b'?'

@@ -17,7 +17,7 @@ import pytest
 
 from oracle import chain
 from rsp import config as C
-from rsp.plan import Plan
+from rsp.plan import Plan, describe_k2
 
 from _scen import oracle_precompute, product_precompute, SEED
 
@@ -85,6 +85,12 @@ def test_configs_reach_the_intended_blocks(name):
     get = (lambda n: pre[n]) if isinstance(pre, dict) else (lambda n: getattr(pre, n))
     assert _block(get('MF_medium_fft'), g1, g1 + g2) == CFGS[name][3]
     assert _block(get('MF_long_fft'), g1 + g2, g1 + g2 + g3) == 2560
+    # this file's copy of the cost model agrees with the plan's own (the device-free rsp_plan_describe_k2)
+    for prec in ('c128', 'c64'):
+        segs = describe_k2(s['cfg'], s['cfar'], s['clus'], pre, precision=prec)['segments']
+        assert segs[1]['M'] == _block(get('MF_medium_fft'), g1, g1 + g2)
+        assert segs[2]['M'] == _block(get('MF_long_fft'), g1 + g2, g1 + g2 + g3)
+        assert (segs[1]['nblocks'], segs[2]['nblocks']) == (1, 1)
     # every stitched long gate inside the long convolution's support (no all-zero columns)
     N = s['cfg']['Sig_Config']['point_PRT']
     assert g1 + g2 + g3 <= (N - get('seg_start_long') + 1) + 700 - 1
