@@ -98,19 +98,6 @@ cd root_of_unity(long long e, long long n) {
     return cd((double)std::cos(a), (double)std::sin(a));
 }
 
-// Radix sequence for a 2^m-point Stockham FFT: radix 16 passes, remainder as 8/4
-// (never a lone radix-2 pass unless m == 1).  pal: a 3-pass plan with the remainder in the
-// middle (the overlap-save blocks, rad_bits_pal in rsp_kernels.hip).
-void radix_plan(int m, int* nrad, int* rad, bool pal = false) {
-    *nrad = 0;
-    while (m > 0) {
-        const int p = (m == 5) ? 3 : (m >= 4 ? 4 : m);
-        rad[(*nrad)++] = 1 << p;
-        m -= p;
-    }
-    if (pal && *nrad == 3) std::swap(rad[1], rad[2]);
-}
-
 void push_pass_twiddles(std::vector<cd>& out, int Ns, int R, bool cmp) {
     if (cmp) {
         for (int r = 1; r < R; r *= 2)
@@ -121,34 +108,13 @@ void push_pass_twiddles(std::vector<cd>& out, int Ns, int R, bool cmp) {
     }
 }
 
-// Per-pass Stockham twiddle tables of a 2^m-point FFT (radix order reversed if rev),
-// concatenated: pass q >= 1 owns Ns_q x (R_q - 1) entries T[k][r-1] = exp(-2 pi i k r / (Ns_q R_q))
-// (must match tw_pass_off() in rsp_kernels.hip).  Compact tables (cmp): r = 1, 2, 4, 8 only,
-// stored column-major, [i][k] = T[k][2^i] (load_tw in rsp_kernels.hip).
-// The angle's numerator is reduced modulo the period first, so every entry is the correctly
-// rounded double of the exact root of unity's angle.
-void build_pass_twiddles(int m, std::vector<cd>& out, bool rev = false, bool cmp = false, bool pal = false) {
-    int nrad, rad[8];
-    radix_plan(m, &nrad, rad, pal);
-    if (rev) std::reverse(rad, rad + nrad);
-    int Ns = 1;
-    for (int q = 0; q < nrad; ++q) {
-        const int R = rad[q];
-        if (q > 0) push_pass_twiddles(out, Ns, R, cmp);
-        Ns *= R;
-    }
-}
-
-// Mixed-radix overlap-save block M = 16 x R1 x 16 (k2_fft_job_mix): a palindrome, so the
-// inverse table (reversed radices) is the forward one and only the forward table is stored.
-void build_mix_twiddles(int R0, int R1, std::vector<cd>& out, bool cmp) {
-    const int rad[3] = {R0, R1, R0};
-    int Ns = 1;
-    for (int q = 0; q < 3; ++q) {
-        const int R = rad[q];
-        if (q > 0) push_pass_twiddles(out, Ns, R, cmp);
-        Ns *= R;
-    }
+// Per-pass Stockham twiddle tables of a radix plan, concatenated as plan_tw_off() lays them out:
+// pass q >= 1 owns Ns_q x (R_q - 1) entries T[k][r-1] = exp(-2 pi i k r / (Ns_q R_q)).  Compact
+// tables (cmp): r = 1, 2, 4, 8 only, stored column-major, [i][k] = T[k][2^i] (load_tw in
+// rsp_kernels.hip).  The angle's numerator is reduced modulo the period first, so every entry is
+// the correctly rounded double of the exact root of unity's angle.
+void build_plan_twiddles(const RadixPlan& p, std::vector<cd>& out, bool cmp) {
+    for (int q = 1; q < p.np; ++q) push_pass_twiddles(out, plan_ns(p, q), p.rad[q], cmp);
 }
 
 struct Interval { int lo, hi; };
@@ -240,12 +206,11 @@ int build_fft_segment(SegDesc& s, const double* mf_fft, int Nfft, int N, int ga,
     if (ti < 0) {
         tw.sizes.push_back(M);
         tw.offs.push_back((int)twM.size());
-        if (mix) {
-            build_mix_twiddles(16, M / 256, twM, true);
-        } else {
-            build_pass_twiddles(s.logM, twM, false, true, true);   // forward FFT (compact rows, palindromic plan)
-            build_pass_twiddles(s.logM, twM, true, true, true);    // inverse FFT (reversed radices)
-        }
+        // compact tables of the forward FFT; a power-of-two block's inverse FFT (reversed radices)
+        // has its own behind them, the 2560-point palindrome reads the forward ones
+        const RadixPlan pl = mix ? plan_os_2560() : plan_os_pow2(s.logM);
+        build_plan_twiddles(pl, twM, true);
+        if (!mix) build_plan_twiddles(plan_rev(pl), twM, true);
         ti = (int)tw.sizes.size() - 1;
     }
     s.tw_off = tw.offs[ti];
@@ -526,7 +491,7 @@ void build_tables(const rsp_precomputed* pre, PlanHost& h) {
                 h.atab[((mb * nj + j) * 2 + 1) * 64 + lane] = im ? wr : -wi;   // coefficient of Im(x_c)
             }
     h.twP.resize(P);
-    if (g.pow2P) build_pass_twiddles(g.logP, h.twPp);
+    if (g.pow2P) build_plan_twiddles(plan_pow2(g.logP), h.twPp, false);
     g.twPp_elems = (int)h.twPp.size();
     if (g.pow2P && P >= 64 && P <= 256)   // k1_fft_dif (k1_dif: P = 64 .. 256): compact pass-A twiddles, column-major [i][n2]
         for (int i = 0; i < 4; ++i)

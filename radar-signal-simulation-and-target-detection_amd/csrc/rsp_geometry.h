@@ -149,6 +149,78 @@ inline int rq_table_elems(int twq_elems, int P) { return twq_elems + (P > 2 * RQ
 constexpr int RSP_K2_SH = 5;
 RSP_HD constexpr int k2_lds_data(int pts, int sh) { return pts + (pts >> sh); }
 
+// ---- radix plans of the Stockham FFTs (K1's slow-time FFT, K2's overlap-save blocks) ----------
+// The one description of a transform's passes: the kernels instantiate their passes from it and the
+// host builds the twiddle tables from it.  A plan reaches a template as a type with a static
+// constexpr member `p` (C++17 has no class-type template parameters).
+struct RadixPlan {
+    int np;       // passes
+    int rad[4];   // radix of pass q < np
+};
+RSP_HD constexpr int clog2(int x) { return x <= 1 ? 0 : 1 + clog2(x >> 1); }
+// 2^m points: radix-16 passes, the remainder as 8 / 4 (m = 5 -> 8 x 4; never a lone radix-2 pass
+// unless m = 1)
+RSP_HD constexpr RadixPlan plan_pow2(int m) {
+    RadixPlan p{0, {1, 1, 1, 1}};
+    while (m > 0) {
+        const int b = (m == 5) ? 3 : (m >= 4 ? 4 : m);
+        p.rad[p.np++] = 1 << b;
+        m -= b;
+    }
+    return p;
+}
+// The overlap-save block of 2^m points: a 3-pass plan takes its last two radices in the other order
+// (2048 = 16 x 8 x 16, 1024 = 16 x 4 x 16): a palindrome, so the inverse FFT runs the same radices,
+// and both Ns = 1 passes -- the forward first pass and the inverse first pass fused into the
+// forward last one -- are radix 16, whose stride-16 stores are at most 2-way conflicted
+// (tools/ab/lds_conflicts64.py).
+RSP_HD constexpr RadixPlan plan_os_pow2(int m) {
+    RadixPlan p = plan_pow2(m);
+    if (p.np == 3) {
+        const int t = p.rad[1];
+        p.rad[1] = p.rad[2];
+        p.rad[2] = t;
+    }
+    return p;
+}
+// The mixed-radix overlap-save block 2560 = 16 x 10 x 16: one block covers x2's long segment
+// (Lh = 700, 1860 gates), which takes two 2048-point blocks in powers of two -- 37.5% fewer points.
+RSP_HD constexpr RadixPlan plan_os_2560() { return RadixPlan{3, {16, 10, 16, 1}}; }
+// The same radices in reverse order: the inverse FFT of an overlap-save block, so that its first
+// pass consumes exactly the elements the forward FFT's last pass leaves in each thread's registers.
+RSP_HD constexpr RadixPlan plan_rev(RadixPlan p) {
+    RadixPlan r{p.np, {1, 1, 1, 1}};
+    for (int q = 0; q < p.np; ++q) r.rad[q] = p.rad[p.np - 1 - q];
+    return r;
+}
+// Ns before pass q: the product of the earlier radices (q = np: the transform's length)
+RSP_HD constexpr int plan_ns(RadixPlan p, int q) {
+    int ns = 1;
+    for (int i = 0; i < q; ++i) ns *= p.rad[i];
+    return ns;
+}
+RSP_HD constexpr int plan_len(RadixPlan p) { return plan_ns(p, p.np); }
+// Twiddle entries per butterfly index k of a radix-R pass: full rows W^(k r), r = 1 .. R - 1, or
+// (cmp) compact tables W^(k 2^i), 2^i < R (load_tw in rsp_kernels.hip)
+RSP_HD constexpr int tw_row(int R, bool cmp) { return cmp ? clog2(R - 1) + 1 : R - 1; }
+// Offset of pass q's table inside the plan's concatenated per-pass tables: pass i >= 1 owns Ns_i rows
+// of tw_row(R_i) entries (pass 0: Ns = 1, no twiddles); q = np: the tables' total
+RSP_HD constexpr int plan_tw_off(RadixPlan p, int q, bool cmp) {
+    int off = 0;
+    for (int i = 1; i < q; ++i) off += plan_ns(p, i) * tw_row(p.rad[i], cmp);
+    return off;
+}
+RSP_HD constexpr int plan_tw_total(RadixPlan p, bool cmp) { return plan_tw_off(p, p.np, cmp); }
+// The reversed plan's tables equal the forward ones (the conjugation happens in load_tw)
+RSP_HD constexpr bool plan_is_palindrome(RadixPlan p) {
+    for (int q = 0; q < p.np; ++q)
+        if (p.rad[q] != p.rad[p.np - 1 - q]) return false;
+    return true;
+}
+template <int LG> struct PlanPow2 { static constexpr RadixPlan p = plan_pow2(LG); };
+template <int M> struct PlanOs { static constexpr RadixPlan p = M == 2560 ? plan_os_2560() : plan_os_pow2(clog2(M)); };
+template <class P> struct PlanRev { static constexpr RadixPlan p = plan_rev(P::p); };
+
 // K1's launch configuration for C channels and B beams: the template arguments CP (channels padded
 // to the MFMA's groups of 4) and BMAX of the K1 kernels, NJ channel groups, MB MFMA row blocks of
 // 8 beams and TPW sub-tiles per wave of a load round (16 16-B registers per lane).  The Atab

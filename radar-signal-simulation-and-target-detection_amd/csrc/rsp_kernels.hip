@@ -295,8 +295,6 @@ template <bool INV, class V> struct Dft<12, INV, V> {
     static __device__ __forceinline__ void run(V* a) { dft_pfa<4, 3, INV>(a); }
 };
 
-constexpr int clog2(int x) { return x <= 1 ? 0 : 1 + clog2(x >> 1); }
-
 // LDS index inside a row: SH > 0 inserts one complex every 2^SH to break power-of-two
 // strides (tools/ab/lds_conflicts.py models the gfx950 bank rules for each pass).
 template <int SH>
@@ -344,187 +342,43 @@ __device__ __forceinline__ void load_tw(const TW& twk, V (&w)[R]) {
         }
     }
 }
-constexpr int tw_row(int R, bool cmp) { return cmp ? clog2(R - 1) + 1 : R - 1; }
 
-// Radix plan of a 2^m-point FFT: radix-16 passes, remainder as 8/4 (m = 5 -> 8 x 4);
-// must match radix_plan() in rsp_plan.cpp.  REV = the same radices in reverse order (the
-// inverse FFT of the overlap-save block, so that its first pass consumes exactly the
-// elements the forward FFT's last pass leaves in each thread's registers).
-constexpr int rad_bits(int m, int q) {
-    for (int i = 0; i < q; ++i) m -= (m == 5) ? 3 : (m >= 4 ? 4 : m);
-    return (m == 5) ? 3 : (m >= 4 ? 4 : m);
-}
-constexpr int n_passes(int m) {
-    int n = 0;
-    while (m > 0) {
-        m -= (m == 5) ? 3 : (m >= 4 ? 4 : m);
-        ++n;
-    }
-    return n;
-}
-// PAL: the overlap-save blocks' plan puts the smallest radix in the middle of a 3-pass plan
-// (2048 = 16 x 8 x 16, 1024 = 16 x 4 x 16): a palindrome, so the inverse FFT runs the same
-// radices, and both Ns = 1 passes -- the forward first pass and the inverse first pass fused
-// into the forward last one -- are radix 16, whose stride-16 stores are at most 2-way
-// conflicted (tools/ab/lds_conflicts64.py).  Must match radix_plan() in rsp_plan.cpp.
-constexpr int rad_bits_pal(int m, int q) {
-    return n_passes(m) == 3 && q >= 1 ? rad_bits(m, 3 - q) : rad_bits(m, q);
-}
-constexpr int rad_bits_p(int m, int q, bool rev, bool pal = false) {
-    return pal ? (rev ? rad_bits_pal(m, n_passes(m) - 1 - q) : rad_bits_pal(m, q))
-               : (rev ? rad_bits(m, n_passes(m) - 1 - q) : rad_bits(m, q));
-}
-
-// Offset of pass q's twiddle table inside the concatenated per-pass tables of a 2^LG FFT:
-// pass i >= 1 owns Ns_i rows of tw_row(R_i) entries (pass 0: Ns = 1, no twiddles).  Must
-// match build_pass_twiddles() in rsp_plan.cpp.
-constexpr int tw_pass_off(int LG, int q, bool rev = false, bool cmp = false, bool pal = false) {
-    int off = 0, lgns = 0;
-    for (int i = 0; i < q; ++i) {
-        const int rb = rad_bits_p(LG, i, rev, pal);
-        if (i > 0) off += (1 << lgns) * tw_row(1 << rb, cmp);
-        lgns += rb;
-    }
-    return off;
-}
-constexpr int tw_total(int LG, bool rev = false, bool cmp = false, bool pal = false) {
-    return tw_pass_off(LG, n_passes(LG), rev, cmp, pal);
-}
-
-// One Stockham radix-R pass (Govindaraju et al. formulation) over `nrows` rows of
-// length L = 2^LGL held in LDS (row stride rs).  Ns = 2^LGNS = product of the earlier
-// radices.  Reads stride L/R, twiddle W_{Ns R}^{(j mod Ns) r} (from this pass's table),
-// radix-R DFT, writes positions expand(j, Ns, R) + r Ns.  In place: all reads, barrier,
-// all writes, barrier.  Every size is a compile-time constant, so a pass is straight-line
-// code and no address math is carried across passes.
-// With power-of-two nb, Ns and pads every 2^SH, lidx(j + r nb) = lidx(j) + r nb + ((r nb) >> SH)
-// and lidx(idxD + r Ns) = lidx(idxD) + r Ns + ((r Ns) >> SH): every LDS address of a butterfly
-// is a per-thread base plus a compile-time offset (ds_read/ds_write immediate offsets).
-template <int R, bool INV, int NB, int SH, int NTHR, int LGL, int LGNS, bool CMP = false, int XL = 0, class V, class TW>
-__device__ __forceinline__ void sh_load(const V* buf, int rs, int nrows, const TW& tw, V (&v)[NB][R]) {
-    constexpr int lgR = clog2(R);
-    constexpr int lgnb = LGL - lgR;
-    constexpr int nb = 1 << lgnb;
-    constexpr int Ns = 1 << LGNS;
-    static_assert(!XL || nb % 128 == 0, "XOR-swizzled input needs r nb to keep the swizzle bits");
-    const int total = nb * nrows;
-#pragma unroll
-    for (int t = 0; t < NB; ++t) {
-        const int beta = threadIdx.x + t * NTHR;
-        if (beta < total) {
-            const int row = beta >> lgnb, j = beta & (nb - 1);
-            const int k = j & (Ns - 1);
-            const V* src = XL ? buf + (row << LGL) + (j ^ ((j >> 4) & 7)) : buf + row * rs + lidx<SH>(j);
-            V w[R];
-            if (LGNS > 0) load_tw<R, INV, CMP, Ns>(tw + (CMP ? k : k * tw_row(R, CMP)), w);
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                V x = src[r * nb + (SH && !XL ? (r * nb) >> SH : 0)];
-                if (r > 0 && LGNS > 0) x = vmul(x, w[r]);
-                v[t][r] = x;
-            }
-        }
-    }
-}
-
-// Radix-R DFT of the loaded butterflies and the Stockham store (through policy st).
-// XL = 1: the output is stored XOR-swizzled, element i at (i ^ ((i >> 4) & 7)) of a row of 2^LGL
-// (Ns = 1 radix-16 passes only).  Their stores write 16 j + r for lane j, which the pad layout
-// puts 2-way on the banks of every group of 8 lanes; swizzled, the 8 lanes hit 8 distinct
-// 16-B banks, and the next pass's reads (j + r nb, nb a multiple of 128) stay conflict-free.
-template <int R, bool INV, int NB, int SH, int NTHR, int LGL, int LGNS, int XL = 0, class V, class St>
-__device__ __forceinline__ void sh_store(V (&v)[NB][R], int rs, int nrows, const St& st) {
-    constexpr int lgR = clog2(R);
-    constexpr int lgnb = LGL - lgR;
-    constexpr int nb = 1 << lgnb;
-    constexpr int Ns = 1 << LGNS;
-    static_assert(!XL || (LGNS == 0 && R == 16), "XOR-swizzled output: Ns = 1 radix-16 passes");
-    const int total = nb * nrows;
-#pragma unroll
-    for (int t = 0; t < NB; ++t) {
-        const int beta = threadIdx.x + t * NTHR;
-        if (beta < total) {
-            const int row = beta >> lgnb, j = beta & (nb - 1);
-            const int k = j & (Ns - 1);
-            Dft<R, INV, V>::run(v[t]);
-            const int idxD = ((j >> LGNS) << (LGNS + lgR)) + k;
-            if constexpr (XL) {
-                const int wbase = (row << LGL) + idxD, c = j & 7;
-#pragma unroll
-                for (int r = 0; r < R; ++r) st.put(t * R + r, row, idxD + r, wbase + (r & 8) + ((r & 7) ^ c), v[t][r]);
-            } else {
-                const int wbase = row * rs + lidx<SH>(idxD);
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-                    st.put(t * R + r, row, idxD + r * Ns, wbase + r * Ns + (SH ? (r * Ns) >> SH : 0), v[t][r]);
-            }
-        }
-    }
-}
-
-// TAIL = false: no barrier after the pass (the caller's next LDS writes go to other rows).
-template <int R, bool INV, int NB, int SH, int NTHR, int LGL, int LGNS, bool CMP, int XL = 0, bool TAIL = true, class V,
-          class TW, class St>
-__device__ __forceinline__ void sh_pass(V* buf, int rs, int nrows, const TW& tw, const St& st) {
-    V v[NB][R];
-    sh_load<R, INV, NB, SH, NTHR, LGL, LGNS, CMP, XL>(buf, rs, nrows, tw, v);
-    if constexpr (StoresLds<St>::value) __syncthreads();   // every read of the pass before any write
-    sh_store<R, INV, NB, SH, NTHR, LGL, LGNS>(v, rs, nrows, st);
-    if constexpr (TAIL) __syncthreads();
-}
-
-// Passes Q..QEND-1 of a 2^LG-point FFT (radix order reversed if REV) over `nrows` rows;
-// pass n_passes - 1 stores through `last`, the others through `mid`.  tw = this plan's
-// concatenated tables.  PTS = complex points per thread (nrows * L / NTHR).
-template <int LG, int Q, int QEND, int LGNS, int PTS, bool INV, bool REV, int SH, int NTHR, bool CMP, bool PAL = false,
-          int XIN = 0, bool TAIL = true, class V, class TW, class StMid, class StLast>
-__device__ __forceinline__ void fft_range(V* buf, int rs, int nrows, const TW& tw, const StMid& mid, const StLast& last) {
-    constexpr int NP = n_passes(LG);
-    if constexpr (Q < QEND) {
-        constexpr int RB = rad_bits_p(LG, Q, REV, PAL);
-        constexpr int R = 1 << RB;
-        constexpr int NB = (PTS + R - 1) / R;
-        const auto twq = tw + tw_pass_off(LG, Q, REV, CMP, PAL);
-        if constexpr (Q == NP - 1)
-            sh_pass<R, INV, NB, SH, NTHR, LG, LGNS, CMP, XIN, TAIL>(buf, rs, nrows, twq, last);
-        else
-            sh_pass<R, INV, NB, SH, NTHR, LG, LGNS, CMP, XIN>(buf, rs, nrows, twq, mid);
-        fft_range<LG, Q + 1, QEND, LGNS + RB, PTS, INV, REV, SH, NTHR, CMP, PAL, 0, TAIL>(buf, rs, nrows, tw, mid, last);
-    }
-}
-
-// All passes of a 2^LG-point FFT over `nrows` rows; the last pass stores through `last`
-// (TAIL: followed by a barrier).
-template <int LG, int PTS, int SH, int NTHR, bool TAIL = true, class V, class StMid, class StLast>
-__device__ __forceinline__ void fft_passes(V* buf, int rs, int nrows, const V* tw, const StMid& mid,
-                                           const StLast& last) {
-    fft_range<LG, 0, n_passes(LG), 0, PTS, false, false, SH, NTHR, false, false, 0, TAIL>(buf, rs, nrows, tw, mid, last);
-}
-
-// ---- Stockham passes of any length L and radix R (mixed-radix overlap-save blocks) ----------
-// Same formulation as sh_load / sh_store with L, R, Ns compile-time constants that need not be
-// powers of two: divisions by them become multiply-shifts, and every LDS index is padded per
-// element (lidx of the full position).
-// Padded LDS offset of element j + r D of a row when it splits into a per-thread base lidx(j) plus
-// a compile-time offset: always when D is a multiple of the pad period 2^SH ((j + r D) >> SH =
-// (j >> SH) + r D / 2^SH); with DIVP also when D divides 2^SH and the thread's j mod 2^SH < D
-// (shg_store: idxD = (j / NS) NS R + j mod NS with NS R a multiple of 2^SH), where the carry of
-// j mod 2^SH + r D past 2^SH is that of r D alone.
-template <int SH, int D, bool DIVP = false>
+// When the padded LDS offset of element i + r D, r < R, of a row splits into the thread's base
+// lidx(i) plus the compile-time lidx_off(r) (a ds_read/ds_write immediate offset), for a base with
+// i mod (D R) < D.  sh_load's i = j < nb = D and sh_store's i = idxD = (j / Ns) Ns R + j mod Ns with
+// D = Ns are such bases.  With p = 2^SH the pad period, lidx(i + r D) - lidx(i) = r D + ((i + r D) >> SH)
+// - (i >> SH), and ((i + r D) >> SH) = (i >> SH) + ((r D) >> SH):
+//  - SH = 0: no pads;
+//  - p | D: r D is whole pad periods;
+//  - D | p and p | D R: i mod p = (i mod D R) mod p < D, and r D mod p is a multiple of D, so at most
+//    p - D: the sum does not carry past p;
+//  - D | p and D R | p: i and i + r D lie in one aligned group of D R elements (i mod D R + r D < D R),
+//    which no multiple of p splits, and r D < p.
+// Powers of two D, R always meet one of them; of the 2560-point block's passes, all but the
+// unpadded rows' (SH = 30), whose addresses go through lidx element by element.
+template <int SH, int D, int R>
 constexpr bool lidx_sep() {
-    return SH == 0 || D % (1 << SH) == 0 || (DIVP && (1 << SH) % D == 0);
+    constexpr int p = 1 << SH;
+    return SH == 0 || D % p == 0 || (p % D == 0 && ((D * R) % p == 0 || p % (D * R) == 0));
 }
 template <int SH, int D>
 constexpr int lidx_off(int r) {
     return r * D + (SH ? (r * D) >> SH : 0);
 }
 
-template <int R, bool INV, int NB, int SH, int NTHR, int L, int NS, bool CMP, int XL = 0, class V, class TW>
-__device__ __forceinline__ void shg_load(const V* buf, int rs, int nrows, const TW& tw, V (&v)[NB][R],
-                                         int tix = threadIdx.x) {
+// One Stockham radix-R pass (Govindaraju et al. formulation) over `nrows` rows of length L held
+// in LDS (row stride rs).  Ns = product of the earlier radices.  Reads stride nb = L / R, twiddle
+// W_{Ns R}^{(j mod Ns) r} (from this pass's table), radix-R DFT, writes positions
+// expand(j, Ns, R) + r Ns.  In place: all reads, barrier, all writes, barrier.  L, R and Ns are
+// compile-time constants that need not be powers of two (divisions by them become shifts or
+// multiply-shifts), so a pass is straight-line code and no address math is carried across passes.
+// tix = the thread's index in the workgroup.
+template <int R, bool INV, int NB, int SH, int NTHR, int L, int NS, bool CMP = false, int XL = 0, class V, class TW>
+__device__ __forceinline__ void sh_load(const V* buf, int rs, int nrows, const TW& tw, V (&v)[NB][R],
+                                        int tix = threadIdx.x) {
     constexpr int nb = L / R;
     static_assert(!XL || nb % 128 == 0, "XOR-swizzled input needs r nb to keep the swizzle bits");
-    constexpr bool SEP = lidx_sep<SH, nb>();
+    constexpr bool SEP = lidx_sep<SH, nb, R>();
     const int total = nb * nrows;
 #pragma unroll
     for (int t = 0; t < NB; ++t) {
@@ -543,8 +397,14 @@ __device__ __forceinline__ void shg_load(const V* buf, int rs, int nrows, const 
         }
     }
 }
+
+// Radix-R DFT of the loaded butterflies and the Stockham store (through policy st).
+// XL = 1: the output is stored XOR-swizzled, element i at (i ^ ((i >> 4) & 7)) of a row of L
+// (Ns = 1 radix-16 passes only).  Their stores write 16 j + r for lane j, which the pad layout
+// puts 2-way on the banks of every group of 8 lanes; swizzled, the 8 lanes hit 8 distinct
+// 16-B banks, and the next pass's reads (j + r nb, nb a multiple of 128) stay conflict-free.
 template <int R, bool INV, int NB, int SH, int NTHR, int L, int NS, int XL = 0, class V, class St>
-__device__ __forceinline__ void shg_store(V (&v)[NB][R], int rs, int nrows, const St& st, int tix = threadIdx.x) {
+__device__ __forceinline__ void sh_store(V (&v)[NB][R], int rs, int nrows, const St& st, int tix = threadIdx.x) {
     constexpr int nb = L / R;
     static_assert(!XL || (NS == 1 && R == 16), "XOR-swizzled output: Ns = 1 radix-16 passes");
     const int total = nb * nrows;
@@ -559,7 +419,7 @@ __device__ __forceinline__ void shg_store(V (&v)[NB][R], int rs, int nrows, cons
                 const int wbase = row * L + idxD, c = j & 7;
 #pragma unroll
                 for (int r = 0; r < R; ++r) st.put(t * R + r, row, idxD + r, wbase + (r & 8) + ((r & 7) ^ c), v[t][r]);
-            } else if constexpr (lidx_sep<SH, NS, (NS * R) % (1 << SH) == 0>()) {
+            } else if constexpr (lidx_sep<SH, NS, R>()) {
                 const int wbase = row * rs + lidx<SH>(idxD);
 #pragma unroll
                 for (int r = 0; r < R; ++r) st.put(t * R + r, row, idxD + r * NS, wbase + lidx_off<SH, NS>(r), v[t][r]);
@@ -571,13 +431,43 @@ __device__ __forceinline__ void shg_store(V (&v)[NB][R], int rs, int nrows, cons
         }
     }
 }
-template <int R, bool INV, int NB, int SH, int NTHR, int L, int NS, bool CMP, int XL = 0, class V, class TW, class St>
-__device__ __forceinline__ void shg_pass(V* buf, int rs, int nrows, const TW& tw, const St& st) {
+
+// The read/write barrier only when the store policy writes the LDS rows the pass reads.
+// TAIL = false: no barrier after the pass (the caller's next LDS writes go to other rows).
+template <int R, bool INV, int NB, int SH, int NTHR, int L, int NS, bool CMP, int XL = 0, bool TAIL = true, class V,
+          class TW, class St>
+__device__ __forceinline__ void sh_pass(V* buf, int rs, int nrows, const TW& tw, const St& st) {
     V v[NB][R];
-    shg_load<R, INV, NB, SH, NTHR, L, NS, CMP, XL>(buf, rs, nrows, tw, v);
-    __syncthreads();   // every read of the pass before any write
-    shg_store<R, INV, NB, SH, NTHR, L, NS>(v, rs, nrows, st);
-    __syncthreads();
+    sh_load<R, INV, NB, SH, NTHR, L, NS, CMP, XL>(buf, rs, nrows, tw, v);
+    if constexpr (StoresLds<St>::value) __syncthreads();   // every read of the pass before any write
+    sh_store<R, INV, NB, SH, NTHR, L, NS>(v, rs, nrows, st);
+    if constexpr (TAIL) __syncthreads();
+}
+
+// Passes Q..QEND-1 of radix plan Plan (rsp_geometry.h) over `nrows` rows; the plan's last pass
+// stores through `last` (TAIL: followed by a barrier), the others through `mid`.  tw = the plan's
+// concatenated tables.  PTS = complex points per thread (nrows * L / NTHR).  XIN: the first of
+// these passes reads XOR-swizzled rows.
+template <class Plan, int Q, int QEND, int PTS, bool INV, int SH, int NTHR, bool CMP, int XIN = 0, bool TAIL = true,
+          class V, class TW, class StMid, class StLast>
+__device__ __forceinline__ void fft_range(V* buf, int rs, int nrows, const TW& tw, const StMid& mid, const StLast& last) {
+    if constexpr (Q < QEND) {
+        constexpr int R = Plan::p.rad[Q], L = plan_len(Plan::p), NS = plan_ns(Plan::p, Q);
+        constexpr int NB = (PTS + R - 1) / R, TWQ = plan_tw_off(Plan::p, Q, CMP);
+        const auto twq = tw + TWQ;
+        if constexpr (Q == Plan::p.np - 1)
+            sh_pass<R, INV, NB, SH, NTHR, L, NS, CMP, XIN, TAIL>(buf, rs, nrows, twq, last);
+        else
+            sh_pass<R, INV, NB, SH, NTHR, L, NS, CMP, XIN>(buf, rs, nrows, twq, mid);
+        fft_range<Plan, Q + 1, QEND, PTS, INV, SH, NTHR, CMP, 0, TAIL>(buf, rs, nrows, tw, mid, last);
+    }
+}
+
+// All passes of a 2^LG-point FFT over `nrows` rows.
+template <int LG, int PTS, int SH, int NTHR, bool TAIL = true, class V, class StMid, class StLast>
+__device__ __forceinline__ void fft_passes(V* buf, int rs, int nrows, const V* tw, const StMid& mid,
+                                           const StLast& last) {
+    fft_range<PlanPow2<LG>, 0, PlanPow2<LG>::p.np, PTS, false, SH, NTHR, false, 0, TAIL>(buf, rs, nrows, tw, mid, last);
 }
 
 __device__ __forceinline__ int ilog2(int x) { return 31 - __clz(x); }
@@ -1513,19 +1403,12 @@ template <class T, bool NOPAD> constexpr int k2_sh_np() { return NOPAD ? K2_NOPA
 // with its LDS data reads instead of after an L2 round trip (-6% for k2_pc in complex double).
 // When the radix plan is a palindrome the inverse plan's table equals the forward one (the
 // conjugation happens in load_tw), so one copy serves both.
-constexpr bool k2_tw_sym(int LGM) {
-    for (int q = 0; q < n_passes(LGM); ++q)
-        if (rad_bits_p(LGM, q, false, true) != rad_bits_p(LGM, n_passes(LGM) - 1 - q, false, true))
-            return false;
-    return true;
+constexpr int k2_tw_lds(RadixPlan p) {
+    return plan_tw_total(p, true) + (plan_is_palindrome(p) ? 0 : plan_tw_total(plan_rev(p), true));
 }
-constexpr int k2_tw_lds(int LGM) {
-    return tw_total(LGM, false, true, true) +
-           (k2_tw_sym(LGM) ? 0 : tw_total(LGM, true, true, true));
-}
-constexpr int k2_tw_lds_max() {
-    int m = 16 * tw_row(10, true) + 160 * tw_row(16, true);   // k2_fft_job_mix<2560>
-    for (int lg = 6; lg <= 11; ++lg) m = k2_tw_lds(lg) > m ? k2_tw_lds(lg) : m;
+constexpr int k2_tw_lds_max() {   // over the blocks whose tables are staged: 64 .. 2048 and 2560
+    int m = k2_tw_lds(plan_os_2560());
+    for (int lg = 6; lg <= 11; ++lg) m = k2_tw_lds(plan_os_pow2(lg)) > m ? k2_tw_lds(plan_os_pow2(lg)) : m;
     return m;
 }
 
@@ -1599,11 +1482,14 @@ __device__ __forceinline__ void k2_fft_job(const Geometry& g, const DevConsts& k
     constexpr int M = 1 << LGM;
     constexpr int rows = PTS / M > 0 ? PTS / M : 1;
     constexpr int rs = M + (M >> SH);
-    constexpr int NP = n_passes(LGM);
+    typedef PlanOs<M> Plan;
+    typedef PlanRev<Plan> PlanI;   // the inverse FFT's
+    constexpr int NP = Plan::p.np;
     static_assert(NP >= 2, "overlap-save block needs >= 2 FFT passes");
-    constexpr bool PAL = true, CMP = true;
-    constexpr int RB0 = rad_bits_p(LGM, 0, false, PAL), R0 = 1 << RB0, NB0 = 16 / R0, nb0 = M / R0;
-    constexpr int RBL = rad_bits_p(LGM, NP - 1, false, PAL), RL = 1 << RBL, NBL = 16 / RL;   // last forward pass
+    constexpr bool CMP = true;
+    constexpr int R0 = Plan::p.rad[0], NB0 = 16 / R0, nb0 = M / R0;
+    constexpr int RL = Plan::p.rad[NP - 1], NBL = 16 / RL;   // last forward pass
+    constexpr int TWL = plan_tw_off(Plan::p, NP - 1, CMP), TWIL = plan_tw_off(PlanI::p, NP - 1, CMP);
     const int P = g.P, G = g.G;
     const int lo = sd.lo, hi = sd.hi, off = sd.off;
     const int tid = threadIdx.x;
@@ -1666,28 +1552,27 @@ __device__ __forceinline__ void k2_fft_job(const Geometry& g, const DevConsts& k
             for (int r = 0; r < RL; ++r) hreg[t * RL + r] = buf_ld<V>(hr, (unsigned)(j + r * (M / RL)) * (unsigned)sizeof(V));
         }
     }
-    constexpr int NTWF = tw_total(LGM, false, CMP, PAL);
+    constexpr int NTWF = plan_tw_total(Plan::p, CMP), NTWL = k2_tw_lds(Plan::p);
     // twiddles staged in LDS next to the rows; a 4096-point block's (1 088 entries) do not fit the
     // 2-per-CU workgroup's LDS and are read from L1/L2 instead
     constexpr bool TW_LDS = LGM <= 11 && !NOPAD;
     V* twL = L + k2_lds_data(g.k2_pts, SH);
-    if constexpr (TW_LDS) stage_lds<K2_THREADS>(twL, twl, k2_tw_lds(LGM));   // visible after the pass-0 barrier
+    if constexpr (TW_LDS) stage_lds<K2_THREADS>(twL, twl, NTWL);   // visible after the pass-0 barrier
     const auto twF = k2_tw_src<TW_LDS, V>(twL, twl);
-    const auto twI = k2_tw_sym(LGM) ? twF : twF + NTWF;
+    constexpr int TWI = plan_is_palindrome(Plan::p) ? 0 : NTWF;   // a palindrome: the forward tables
+    const auto twI = twF + TWI;
     // forward pass 0 (Ns = 1, no twiddles) straight from the loaded samples
     // the Ns = 1 passes' outputs XOR-swizzled (sh_store) when a middle pass reads them (3 passes)
     constexpr int XZ = (NP == 3 && R0 == 16 && RL == 16) ? 1 : 0;
-    sh_store<R0, false, NB0, SH, K2_THREADS, LGM, 0, XZ>(v0, rs, rows, StoreLds<V>{L});
+    sh_store<R0, false, NB0, SH, K2_THREADS, M, 1, XZ>(v0, rs, rows, StoreLds<V>{L});
     __syncthreads();
     K2_STAMP(1);
     // forward passes 1 .. NP-2
-    fft_range<LGM, 1, NP - 1, RB0, 16, false, false, SH, K2_THREADS, CMP, PAL, XZ>(L, rs, rows, twF, StoreLds<V>{L},
-                                                                               StoreLds<V>{L});
+    fft_range<Plan, 1, NP - 1, 16, false, SH, K2_THREADS, CMP, XZ>(L, rs, rows, twF, StoreLds<V>{L}, StoreLds<V>{L});
     // fused: forward last pass, x H (1/M folded in), inverse pass 0 of the reversed plan
     {
         V v[NBL][RL];
-        sh_load<RL, false, NBL, SH, K2_THREADS, LGM, LGM - RBL, CMP>(L, rs, rows,
-                                                                      twF + tw_pass_off(LGM, NP - 1, false, CMP, PAL), v);
+        sh_load<RL, false, NBL, SH, K2_THREADS, M, M / RL, CMP>(L, rs, rows, twF + TWL, v);
         __syncthreads();   // every read of the pass before any write
 #pragma unroll
         for (int t = 0; t < NBL; ++t) {
@@ -1700,7 +1585,7 @@ __device__ __forceinline__ void k2_fft_job(const Geometry& g, const DevConsts& k
                 for (int r = 0; r < RL; ++r) v[t][r] = vmul(v[t][r], hreg[(t % NHT) * RL + r]);
             }
         }
-        sh_store<RL, true, NBL, SH, K2_THREADS, LGM, 0, XZ>(v, rs, rows, StoreLds<V>{L});
+        sh_store<RL, true, NBL, SH, K2_THREADS, M, 1, XZ>(v, rs, rows, StoreLds<V>{L});
         __syncthreads();
     }
     K2_STAMP(3);
@@ -1708,27 +1593,24 @@ __device__ __forceinline__ void k2_fft_job(const Geometry& g, const DevConsts& k
     if constexpr (EPI) {
         // inverse passes 1 .. NP-1 (reversed radices) into LDS; then the valid overlap-save outputs
         // = stitched gates go to the maps
-        fft_range<LGM, 1, NP, RBL, 16, true, true, SH, K2_THREADS, CMP, PAL, XZ>(L, rs, rows, twI, StoreLds<V>{L},
-                                                                               StoreLds<V>{L});
+        fft_range<PlanI, 1, NP, 16, true, SH, K2_THREADS, CMP, XZ>(L, rs, rows, twI, StoreLds<V>{L}, StoreLds<V>{L});
         k2_epilogue<T, SH>(L, rs, rows, row0, rows_total, Lh1, g0, gend, rdm, mag, G, g.Gp);
     } else if constexpr (WROW) {
         // inverse passes 1 .. NP-2 into LDS, then the last one (Ns = nb0, input not swizzled:
         // XZ applies to the pass after an Ns = 1 pass only) stores the kept gates straight into
         // this wave's row of the maps
-        fft_range<LGM, 1, NP - 1, RBL, 16, true, true, SH, K2_THREADS, CMP, PAL, XZ>(L, rs, rows, twI, StoreLds<V>{L},
-                                                                                   StoreLds<V>{L});
-        constexpr int LGNSL = LGM - RB0;
+        fft_range<PlanI, 1, NP - 1, 16, true, SH, K2_THREADS, CMP, XZ>(L, rs, rows, twI, StoreLds<V>{L}, StoreLds<V>{L});
         static_assert(NP >= 3 || XZ == 0, "last pass input is never swizzled");
-        const auto twl_last = twI + tw_pass_off(LGM, NP - 1, true, CMP, PAL);
+        const auto twl_last = twI + TWIL;
         const int rho = row0 + __builtin_amdgcn_readfirstlane(tid / nb0);
         if (rdm)
-            sh_pass<R0, true, NB0, SH, K2_THREADS, LGM, LGNSL, CMP, 0, false>(
+            sh_pass<R0, true, NB0, SH, K2_THREADS, M, nb0, CMP, 0, false>(
                 L, rs, rows, twl_last, StoreRowK<V, true, nb0, R0>(rdm, mag, G, g.Gp, rho, rows_total, Lh1, g0, gend));
         else
-            sh_pass<R0, true, NB0, SH, K2_THREADS, LGM, LGNSL, CMP, 0, false>(
+            sh_pass<R0, true, NB0, SH, K2_THREADS, M, nb0, CMP, 0, false>(
                 L, rs, rows, twl_last, StoreRowK<V, false, nb0, R0>(rdm, mag, G, g.Gp, rho, rows_total, Lh1, g0, gend));
     } else {
-        fft_range<LGM, 1, NP, RBL, 16, true, true, SH, K2_THREADS, CMP, PAL, XZ, false>(
+        fft_range<PlanI, 1, NP, 16, true, SH, K2_THREADS, CMP, XZ, false>(
             L, rs, rows, twI, StoreLds<V>{L},
             StoreRdm<V>{buf_rsrc(rdm, (unsigned)(rows_total * G * sizeof(V))),
                         buf_rsrc(mag, (unsigned)(rows_total * g.Gp * sizeof(T))), G, g.Gp, row0, rows_total, Lh1, g0,
@@ -1796,14 +1678,14 @@ __device__ __forceinline__ void k2_fft_job_mix(const Geometry& g, const DevConst
     const auto twF = k2_tw_src<!NOPAD, V>(twL, twl);
     const auto twI = twF;   // palindrome: the reversed plan's table is the forward one
     constexpr int XZ = R0 == 16 ? 1 : 0;   // Ns = 1 outputs XOR-swizzled (see sh_store)
-    shg_store<R0, false, NB0, SH, K2_THREADS, M, 1, XZ>(v0, rs, rows, StoreLds<V>{L}, tid);
+    sh_store<R0, false, NB0, SH, K2_THREADS, M, 1, XZ>(v0, rs, rows, StoreLds<V>{L}, tid);
     __syncthreads();
     K2_STAMP(1);
-    shg_pass<R1, false, NB1, SH, K2_THREADS, M, NS1, CMP, XZ>(L, rs, rows, twF, StoreLds<V>{L});
+    sh_pass<R1, false, NB1, SH, K2_THREADS, M, NS1, CMP, XZ>(L, rs, rows, twF, StoreLds<V>{L});
     K2_STAMP(2);
     {
         V v[NB0][R0];
-        shg_load<R0, false, NB0, SH, K2_THREADS, M, NS2, CMP>(L, rs, rows, twF + TW2, v, tid);
+        sh_load<R0, false, NB0, SH, K2_THREADS, M, NS2, CMP>(L, rs, rows, twF + TW2, v, tid);
         __syncthreads();   // every read of the pass before any write
         const __amdgpu_buffer_rsrc_t hr = buf_rsrc(H + sd.H_off, (unsigned)(M * sizeof(V)));
 #pragma unroll
@@ -1816,25 +1698,25 @@ __device__ __forceinline__ void k2_fft_job_mix(const Geometry& g, const DevConst
                 for (int r = 0; r < R0; ++r) v[t][r] = vmul(v[t][r], hreg[t][r]);
             }
         }
-        shg_store<R0, true, NB0, SH, K2_THREADS, M, 1, XZ>(v, rs, rows, StoreLds<V>{L}, tid);
+        sh_store<R0, true, NB0, SH, K2_THREADS, M, 1, XZ>(v, rs, rows, StoreLds<V>{L}, tid);
         __syncthreads();
     }
     K2_STAMP(3);
-    shg_pass<R1, true, NB1, SH, K2_THREADS, M, NS1, CMP, XZ>(L, rs, rows, twI, StoreLds<V>{L});
+    sh_pass<R1, true, NB1, SH, K2_THREADS, M, NS1, CMP, XZ>(L, rs, rows, twI, StoreLds<V>{L});
     K2_STAMP(4);
     const int gend = min(sd.gb, g0 + sd.V);
     if constexpr (EPI) {
-        shg_pass<R0, true, NB0, SH, K2_THREADS, M, NS2, CMP>(L, rs, rows, twI + TW2, StoreLds<V>{L});
+        sh_pass<R0, true, NB0, SH, K2_THREADS, M, NS2, CMP>(L, rs, rows, twI + TW2, StoreLds<V>{L});
         k2_epilogue<T, SH>(L, rs, rows, row0, rows_total, Lh1, g0, gend, rdm, mag, G, g.Gp);
     } else {
         static_assert(EPI || (rows == 1 && NS2 == nb0), "last pass: thread j's outputs are j + r NS2 of one row");
         V v[NB0][R0];
-        shg_load<R0, true, NB0, SH, K2_THREADS, M, NS2, CMP>(L, rs, rows, twI + TW2, v, tid);
+        sh_load<R0, true, NB0, SH, K2_THREADS, M, NS2, CMP>(L, rs, rows, twI + TW2, v, tid);
         if (rdm)
-            shg_store<R0, true, NB0, SH, K2_THREADS, M, NS2>(
+            sh_store<R0, true, NB0, SH, K2_THREADS, M, NS2>(
                 v, rs, rows, StoreRowK<V, true, NS2, R0>(rdm, mag, G, g.Gp, row0, rows_total, Lh1, g0, gend), tid);
         else
-            shg_store<R0, true, NB0, SH, K2_THREADS, M, NS2>(
+            sh_store<R0, true, NB0, SH, K2_THREADS, M, NS2>(
                 v, rs, rows, StoreRowK<V, false, NS2, R0>(rdm, mag, G, g.Gp, row0, rows_total, Lh1, g0, gend), tid);
     }
 }
@@ -2477,7 +2359,8 @@ __global__ __launch_bounds__(RSP_THREADS, 2) void k_mtd_cols(Geometry g, DevCons
     constexpr int GT = 16;
     V* twl = Y + GT * g.Ppad;
     const T* __restrict__ win = static_cast<const T*>(k.win);
-    if constexpr (LGP > 0) stage_lds<RSP_THREADS>(twl, static_cast<const V*>(k.twPp), tw_total(LGP));
+    constexpr int NTW = plan_tw_total(PlanPow2<LGP>::p, false);
+    if constexpr (LGP > 0) stage_lds<RSP_THREADS>(twl, static_cast<const V*>(k.twPp), NTW);
     const int b = blockIdx.y, gt0 = blockIdx.x * GT;
     const int P = g.P, G = g.G, Ppad = g.Ppad;
     for (int e = threadIdx.x; e < P * GT; e += RSP_THREADS) {

@@ -76,7 +76,7 @@ def conditions(L):
                 c.add('w4-2560-multiblock')
         if mb and sg['rows_per_wg'] > 1:
             c.add('multiblock-multirow')
-        if mb and sg['M'] != 2560 and (sg['M'] // 16) % L['NZ']:   # pass 0 is radix 16 (rad_bits_p)
+        if mb and sg['M'] != 2560 and (sg['M'] // 16) % L['NZ']:   # pass 0 is radix 16 (plan_os_pow2)
             c.add('zaddr-multiblock')
         if mb and L['NZ'] == 4:
             c.add('nz4')
