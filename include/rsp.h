@@ -256,6 +256,18 @@ typedef struct rsp_k2_layout {
 } rsp_k2_layout;
 int32_t rsp_query_k2_layout(const rsp_plan* plan, rsp_k2_layout* out);
 
+/* The pulse-compression workgroups in dispatch order, one record each: what workgroup blockIdx.x of a
+ * k2_pc launch reads to find its work.  rsp_k2_layout.nwg records; the first min(cap, nwg) go to
+ * `out` (NULL allowed when cap is 0) and nwg to *n (NULL allowed). */
+typedef struct rsp_k2_record {
+    int32_t seg;              /* index among the present segments (narrow, medium, long order)   */
+    int32_t blk;              /* overlap-save block of the segment (0 for the direct FIR)        */
+    int32_t row0;             /* first row of the [beam_num x prtNum] row set; rows_per_wg rows  */
+    int32_t wg;               /* the workgroup's index in job order: segment by segment, block by
+                                 block, ceil(rows / rows_per_wg) workgroups per (segment, block)  */
+} rsp_k2_record;
+int32_t rsp_query_k2_records(const rsp_plan* plan, rsp_k2_record* out, int32_t cap, int32_t* n);
+
 /* What rsp_plan_create_ex would build for these arguments on a device of `ncu` compute units,
  * without a device: the same checks (opt->device aside), refusals and messages, and the values
  * rsp_query_sizes and rsp_query_k1_route report for the created plan.  `sizes` / `route` may be
@@ -271,6 +283,11 @@ int32_t rsp_plan_describe_k3(const rsp_sig_config* cfg, const rsp_cfar_params* c
 int32_t rsp_plan_describe_k2(const rsp_sig_config* cfg, const rsp_cfar_params* cfar,
                              const rsp_cluster_params* cluster, const rsp_precomputed* pre,
                              const rsp_plan_options* opt, int32_t ncu, rsp_k2_layout* layout);
+/* The same for rsp_query_k2_records' values. */
+int32_t rsp_plan_describe_k2_records(const rsp_sig_config* cfg, const rsp_cfar_params* cfar,
+                                     const rsp_cluster_params* cluster, const rsp_precomputed* pre,
+                                     const rsp_plan_options* opt, int32_t ncu, rsp_k2_record* out, int32_t cap,
+                                     int32_t* n);
 
 /* Cube-in path: S5..S11 of fun_process_single_frame on one host cube
  * (layout RSP_LAYOUT_PNC, dtype RSP_C64 or RSP_C128; converted to the plan's precision

@@ -430,6 +430,14 @@ int derive_k2_order(PlanHost& h) {
     for (int w : single) order.push_back(w);
     if ((int)order.size() != g.nwg_k2)
         return fail(RSP_ERR_INVALID, "K2 dispatch order covers %d of %d workgroups", (int)order.size(), g.nwg_k2);
+    // The same order as records: what k2_pc would find for workgroup `wg` by searching the job list
+    h.k2rec.reserve(order.size());
+    for (int wg : order) {
+        size_t ji = 0;
+        while (ji + 1 < h.jobs.size() && wg >= h.jobs[ji + 1].wg_begin) ++ji;
+        const K2Job& jb = h.jobs[ji];
+        h.k2rec.push_back(K2Rec{jb.seg, jb.blk, (wg - jb.wg_begin) * h.segs[jb.seg].rows_per_wg, wg});
+    }
     return RSP_OK;
 }
 
@@ -743,6 +751,25 @@ extern "C" int32_t rsp_plan_describe_k2(const rsp_sig_config* cfg, const rsp_cfa
     const int32_t gates[RSP_MAX_SEG] = {pre->N_gate_narrow, pre->N_gate_medium, pre->N_gate_long};
     if (layout) rsp_fill_k2_layout(h.g, gates, layout);
     return RSP_OK;
+}
+
+int rsp_fill_k2_records(const std::vector<K2Rec>& rec, rsp_k2_record* out, int32_t cap, int32_t* n) {
+    if (cap < 0 || (cap > 0 && !out)) return fail(RSP_ERR_INVALID, "bad record buffer (capacity %d)", cap);
+    const size_t m = std::min((size_t)cap, rec.size());
+    for (size_t i = 0; i < m; ++i) out[i] = rsp_k2_record{rec[i].seg, rec[i].blk, rec[i].row0, rec[i].wg};
+    if (n) *n = (int32_t)rec.size();
+    return RSP_OK;
+}
+
+extern "C" int32_t rsp_plan_describe_k2_records(const rsp_sig_config* cfg, const rsp_cfar_params* cfar,
+                                                const rsp_cluster_params* cluster, const rsp_precomputed* pre,
+                                                const rsp_plan_options* opt, int32_t ncu, rsp_k2_record* out, int32_t cap,
+                                                int32_t* n) {
+    int rc = rsp_plan_check_args(cfg, cfar, cluster, pre, opt);
+    if (rc) return rc;
+    PlanHost h;
+    if ((rc = rsp_plan_derive(cfg, cfar, cluster, pre, opt, ncu, &h))) return rc;
+    return rsp_fill_k2_records(h.k2rec, out, cap, n);
 }
 
 // ---- stage-3 range CFAR (debug_simulated_data_processing_v2.m:419-511) ----

@@ -53,6 +53,14 @@ struct K2Job {
     int seg, blk, wg_begin, wg_count;
 };
 
+// One pulse-compression workgroup, in dispatch order: record blockIdx.x of the table a plan uploads
+// (DevConsts::k2rec) is everything k2_pc needs to find its work -- one 16-byte scalar load instead of
+// the dispatch-order lookup followed by a search of the job list.  wg = the workgroup's index in
+// job order (jobs[].wg_begin + its position in the job); row0 = its first row of the B x P row set.
+struct K2Rec {
+    int seg, blk, row0, wg;
+};
+
 #define RSP_MAX_SEG 3
 #define RSP_MAX_JOBS 16
 #define RSP_MAX_IVL 4
@@ -93,6 +101,7 @@ struct Geometry {
 };
 // Geometry is a kernel argument: the host and the device compiler must lay it out alike.
 static_assert(sizeof(SegDesc) == 76 && sizeof(K2Job) == 16 && sizeof(Geometry) == 680, "kernel-argument layout");
+static_assert(sizeof(K2Rec) == 16, "one 16-byte scalar load per workgroup");
 
 // K3's compile-time path: the reference's cfar_params (v8:45-46) and a 32/64-cell tile
 RSP_HD inline bool k3_fast_params(const Geometry& g) {
@@ -279,6 +288,7 @@ struct PlanHost {
     std::vector<cd> H, twM;
     std::vector<double> range_axis, velocity_axis, beam_angles, klut;
     std::vector<int> k2order;        // pulse-compression workgroup dispatch order
+    std::vector<K2Rec> k2rec;        // the same as per-workgroup records: what the plan uploads
 };
 
 // Stage-3 range CFAR (k_s3_cfar, rsp_stage3.hip).  A workgroup resolves RSP_S3_ROWS Doppler rows
@@ -335,3 +345,6 @@ void rsp_fill_sizes(const Geometry& g, int det_bound, rsp_sizes* s);
 void rsp_fill_k1_route(const Geometry& g, rsp_k1_route* out);
 void rsp_fill_k3_tiling(const Geometry& g, rsp_k3_tiling* out);
 void rsp_fill_k2_layout(const Geometry& g, const int32_t gates[RSP_MAX_SEG], rsp_k2_layout* out);
+// rsp_query_k2_records / rsp_plan_describe_k2_records: the first min(cap, rec.size()) records into out
+// (may be NULL when cap is 0), rec.size() into *n.
+int rsp_fill_k2_records(const std::vector<K2Rec>& rec, rsp_k2_record* out, int32_t cap, int32_t* n);

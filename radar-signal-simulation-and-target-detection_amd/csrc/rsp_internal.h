@@ -61,7 +61,7 @@ struct DevConsts {
     const void* taps;        // narrow FIR taps, real
     const void* H;           // overlap-save spectra, 1/M scaled, complex
     const void* twM;         // per-pass Stockham twiddles of each overlap-save block size, complex
-    const int* k2order;      // pulse-compression workgroup dispatch order: job kinds interleaved
+    const K2Rec* k2rec;      // pulse-compression workgroups in dispatch order (job kinds interleaved), a record each
     const double* range_axis;
     const double* velocity_axis;
     const double* beam_angles;

@@ -319,6 +319,23 @@ template <class V> struct StoresLds<StoreLds<V>> { static constexpr bool value =
 // powers formed as products of at most lgR - 1 of them.  Column-major so that the lanes of a
 // pass (consecutive k) read consecutive 16-B entries: conflict-free, where [k][i] rows of 4
 // entries put every 4th lane on the same banks (tools/ab/lds_conflicts_k2v2.py).
+// The compact form in two steps, so that a pass's table entries can be fetched ahead of the pass
+// (k2_fft_job_mix): tw_fetch loads the bases W^(k 2^i), 2^i < R, as the table holds them; tw_expand
+// conjugates them for the inverse and forms the other powers.
+template <int R, int NS, class V, class TW>
+__device__ __forceinline__ void tw_fetch(const TW& twk, V (&b)[tw_row(R, true)]) {
+#pragma unroll
+    for (int i = 0; i < tw_row(R, true); ++i) b[i] = twk[i * NS];
+}
+template <int R, bool INV, class V>
+__device__ __forceinline__ void tw_expand(const V (&b)[tw_row(R, true)], V (&w)[R]) {
+#pragma unroll
+    for (int r = 1; r < R; ++r) {
+        const int hb = 1 << clog2(r);
+        const V t = b[clog2(r)];
+        w[r] = (hb == r) ? V{t.x, INV ? -t.y : t.y} : vmul(w[hb], w[r - hb]);
+    }
+}
 template <int R, bool INV, bool CMP, int NS, class V, class TW>
 __device__ __forceinline__ void load_tw(const TW& twk, V (&w)[R]) {
     if constexpr (!CMP) {
@@ -328,18 +345,9 @@ __device__ __forceinline__ void load_tw(const TW& twk, V (&w)[R]) {
             w[r] = V{t.x, INV ? -t.y : t.y};
         }
     } else {
-        constexpr int lgR = clog2(R - 1) + 1;   // bases W^(k 2^i), 2^i < R (= log2 R for powers of two)
-        V b[lgR];
-#pragma unroll
-        for (int i = 0; i < lgR; ++i) {
-            const V t = twk[i * NS];
-            b[i] = V{t.x, INV ? -t.y : t.y};
-        }
-#pragma unroll
-        for (int r = 1; r < R; ++r) {
-            const int hb = 1 << clog2(r);
-            w[r] = (hb == r) ? b[clog2(r)] : vmul(w[hb], w[r - hb]);
-        }
+        V b[tw_row(R, true)];   // lgR bases (= log2 R for powers of two)
+        tw_fetch<R, NS>(twk, b);
+        tw_expand<R, INV>(b, w);
     }
 }
 
@@ -392,6 +400,46 @@ __device__ __forceinline__ void sh_load(const V* buf, int rs, int nrows, const T
             for (int r = 0; r < R; ++r) {
                 V x = XL ? src[r * nb] : (SEP ? src[lidx_off<SH, nb>(r)] : src[lidx<SH>(j + r * nb)]);
                 if (r > 0 && NS > 1) x = vmul(x, w[r]);
+                v[t][r] = x;
+            }
+        }
+    }
+}
+
+// The same pass in two steps (compact tables): sh_tw_fetch loads the table entries of this thread's
+// butterflies, sh_load_pf reads the rows and applies them.  The entries depend on the thread's index
+// alone, so the fetch can go out a pass ahead and its L2 round trip is over when the pass's LDS
+// reads return; NB x lgR complex registers stay live in between.
+template <int R, int NB, int NTHR, int L, int NS, class V, class TW>
+__device__ __forceinline__ void sh_tw_fetch(int nrows, const TW& tw, V (&b)[NB][tw_row(R, true)], int tix = threadIdx.x) {
+    constexpr int nb = L / R;
+    static_assert(NS > 1, "a pass with twiddles");
+    const int total = nb * nrows;
+#pragma unroll
+    for (int t = 0; t < NB; ++t) {
+        const int beta = tix + t * NTHR;
+        if (beta < total) tw_fetch<R, NS>(tw + (beta % nb) % NS, b[t]);
+    }
+}
+template <int R, bool INV, int NB, int SH, int NTHR, int L, int NS, int XL = 0, class V>
+__device__ __forceinline__ void sh_load_pf(const V* buf, int rs, int nrows, const V (&b)[NB][tw_row(R, true)],
+                                           V (&v)[NB][R], int tix = threadIdx.x) {
+    constexpr int nb = L / R;
+    static_assert(!XL || nb % 128 == 0, "XOR-swizzled input needs r nb to keep the swizzle bits");
+    constexpr bool SEP = lidx_sep<SH, nb, R>();
+    const int total = nb * nrows;
+#pragma unroll
+    for (int t = 0; t < NB; ++t) {
+        const int beta = tix + t * NTHR;
+        if (beta < total) {
+            const int row = beta / nb, j = beta - row * nb;
+            const V* src = XL ? buf + row * L + (j ^ ((j >> 4) & 7)) : buf + row * rs + (SEP ? lidx<SH>(j) : 0);
+            V w[R];
+            tw_expand<R, INV>(b[t], w);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                V x = XL ? src[r * nb] : (SEP ? src[lidx_off<SH, nb>(r)] : src[lidx<SH>(j + r * nb)]);
+                if (r > 0) x = vmul(x, w[r]);
                 v[t][r] = x;
             }
         }
@@ -1418,6 +1466,48 @@ constexpr int k2_tw_lds_max() {   // over the blocks whose tables are staged: 64
 // it.  Consecutive lanes take consecutive gates (coalesced, conflict-free LDS reads), and the
 // square roots run a few at a time instead of 16 per thread at once at the end of the last pass:
 // that pass was k2_pc's register peak (188 VGPRs; with this epilogue 3 workgroups fit per CU).
+//
+// A trip takes U gates per lane, K2_THREADS apart: its U LDS reads go out together, the U
+// independent magnitude chains (v_rsq_f64 and its refinement, rsp_cmag.h) interleave, then the
+// stores.  One gate per trip left every read and every chain of a lane waiting for the one before
+// it: eight serial trips for the 2560-point block's 1 860 gates, now two.  Branch-free: a lane past
+// the kept gates reads the last one (inside the row) and its stores fall outside the buffer
+// resources' range.
+template <class T, int SH, int U, bool RDM>
+__device__ __forceinline__ void k2_epi_trip(const cx<T>* src, int pad0, int e0, int nkeep, __amdgpu_buffer_rsrc_t rr,
+                                            __amdgpu_buffer_rsrc_t mr) {
+    typedef cx<T> V;
+    V x[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const int i = min(e0 + u * K2_THREADS, nkeep - 1);
+        x[u] = src[i + (SH ? ((pad0 + i) >> SH) : 0)];
+    }
+    T m[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) m[u] = cmag(x[u]);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const unsigned e = (unsigned)(e0 + u * K2_THREADS);
+        if (RDM) buf_st<RSP_RDM_AUX>(rr, e * (unsigned)sizeof(V), x[u]);
+        buf_st1(mr, e * (unsigned)sizeof(T), m[u]);
+    }
+}
+template <class T, int SH, bool RDM>
+__device__ __forceinline__ void k2_epi_row(const cx<T>* src, int pad0, int nkeep, __amdgpu_buffer_rsrc_t rr,
+                                           __amdgpu_buffer_rsrc_t mr) {
+    constexpr int U = 4;
+    int e0 = threadIdx.x, left = nkeep;   // left: uniform
+    for (; left > (U - 1) * K2_THREADS; left -= U * K2_THREADS, e0 += U * K2_THREADS)
+        k2_epi_trip<T, SH, U, RDM>(src, pad0, e0, nkeep, rr, mr);
+    // the remainder in one trip of the fewest gates per lane that cover it
+    if (left > 2 * K2_THREADS)
+        k2_epi_trip<T, SH, 3, RDM>(src, pad0, e0, nkeep, rr, mr);
+    else if (left > K2_THREADS)
+        k2_epi_trip<T, SH, 2, RDM>(src, pad0, e0, nkeep, rr, mr);
+    else if (left > 0)
+        k2_epi_trip<T, SH, 1, RDM>(src, pad0, e0, nkeep, rr, mr);
+}
 template <class T, int SH>
 __device__ __forceinline__ void k2_epilogue(const cx<T>* L, int rs, int rows, int row0, int rows_total, int Lh1, int g0,
                                             int gend, cx<T>* __restrict__ rdm, T* __restrict__ mag, int G, int Gp) {
@@ -1431,14 +1521,9 @@ __device__ __forceinline__ void k2_epilogue(const cx<T>* L, int rs, int rows, in
         const __amdgpu_buffer_rsrc_t mr = buf_rsrc(mag + (size_t)rho * Gp + g0, (unsigned)nkeep * (unsigned)sizeof(T));
         if (rdm) {
             const __amdgpu_buffer_rsrc_t rr = buf_rsrc(rdm + (size_t)rho * G + g0, (unsigned)nkeep * (unsigned)sizeof(V));
-            for (int e = threadIdx.x; e < nkeep; e += K2_THREADS) {
-                const V x = src[e + (SH ? ((pad0 + e) >> SH) : 0)];
-                buf_st<RSP_RDM_AUX>(rr, (unsigned)e * (unsigned)sizeof(V), x);
-                buf_st1(mr, (unsigned)e * (unsigned)sizeof(T), cmag(x));
-            }
+            k2_epi_row<T, SH, true>(src, pad0, nkeep, rr, mr);
         } else {
-            for (int e = threadIdx.x; e < nkeep; e += K2_THREADS)
-                buf_st1(mr, (unsigned)e * (unsigned)sizeof(T), cmag(src[e + (SH ? ((pad0 + e) >> SH) : 0)]));
+            k2_epi_row<T, SH, false>(src, pad0, nkeep, mr, mr);
         }
     }
 }
@@ -1678,10 +1763,27 @@ __device__ __forceinline__ void k2_fft_job_mix(const Geometry& g, const DevConst
     const auto twF = k2_tw_src<!NOPAD, V>(twL, twl);
     const auto twI = twF;   // palindrome: the reversed plan's table is the forward one
     constexpr int XZ = R0 == 16 ? 1 : 0;   // Ns = 1 outputs XOR-swizzled (see sh_store)
+    // NOPAD (twiddles from L1/L2): a twiddled pass opened with the L2 round trip of its table entries
+    // between its barrier and its first butterfly.  Where registers allow, the entries are fetched a
+    // pass ahead (sh_tw_fetch): pass 1's go out with the z loads (pass 0 has no twiddles), the inverse
+    // last pass's after the inverse radix-R1 pass's twiddle products (R1 < R0: register slack; an
+    // empty asm keeps the fetch below that pass's own loads).  The other two -- the fused pass's
+    // fetched in forward pass 1, the inverse pass 1's after the H product -- spill (+16 B and +152 B
+    // of scratch per lane) and measured slower; they load their entries as they start.
+    V b1[NOPAD ? NB1 : 1][tw_row(R1, true)], b2[NOPAD ? NB0 : 1][tw_row(R0, true)];
+    if constexpr (NOPAD) sh_tw_fetch<R1, NB1, K2_THREADS, M, NS1>(rows, twF, b1, tid);
     sh_store<R0, false, NB0, SH, K2_THREADS, M, 1, XZ>(v0, rs, rows, StoreLds<V>{L}, tid);
     __syncthreads();
     K2_STAMP(1);
-    sh_pass<R1, false, NB1, SH, K2_THREADS, M, NS1, CMP, XZ>(L, rs, rows, twF, StoreLds<V>{L});
+    if constexpr (NOPAD) {
+        V v[NB1][R1];
+        sh_load_pf<R1, false, NB1, SH, K2_THREADS, M, NS1, XZ>(L, rs, rows, b1, v, tid);
+        __syncthreads();   // every read of the pass before any write
+        sh_store<R1, false, NB1, SH, K2_THREADS, M, NS1>(v, rs, rows, StoreLds<V>{L}, tid);
+        __syncthreads();
+    } else {
+        sh_pass<R1, false, NB1, SH, K2_THREADS, M, NS1, CMP, XZ>(L, rs, rows, twF, StoreLds<V>{L});
+    }
     K2_STAMP(2);
     {
         V v[NB0][R0];
@@ -1702,10 +1804,27 @@ __device__ __forceinline__ void k2_fft_job_mix(const Geometry& g, const DevConst
         __syncthreads();
     }
     K2_STAMP(3);
-    sh_pass<R1, true, NB1, SH, K2_THREADS, M, NS1, CMP, XZ>(L, rs, rows, twI, StoreLds<V>{L});
+    if constexpr (NOPAD) {
+        V v[NB1][R1];
+        sh_load<R1, true, NB1, SH, K2_THREADS, M, NS1, CMP, XZ>(L, rs, rows, twI, v, tid);
+        asm volatile("" ::: "memory");
+        sh_tw_fetch<R0, NB0, K2_THREADS, M, NS2>(rows, twI + TW2, b2, tid);
+        __syncthreads();   // every read of the pass before any write
+        sh_store<R1, true, NB1, SH, K2_THREADS, M, NS1>(v, rs, rows, StoreLds<V>{L}, tid);
+        __syncthreads();
+    } else {
+        sh_pass<R1, true, NB1, SH, K2_THREADS, M, NS1, CMP, XZ>(L, rs, rows, twI, StoreLds<V>{L});
+    }
     K2_STAMP(4);
     const int gend = min(sd.gb, g0 + sd.V);
-    if constexpr (EPI) {
+    if constexpr (EPI && NOPAD) {
+        V v[NB0][R0];
+        sh_load_pf<R0, true, NB0, SH, K2_THREADS, M, NS2>(L, rs, rows, b2, v, tid);
+        __syncthreads();   // every read of the pass before any write
+        sh_store<R0, true, NB0, SH, K2_THREADS, M, NS2>(v, rs, rows, StoreLds<V>{L}, tid);
+        __syncthreads();
+        k2_epilogue<T, SH>(L, rs, rows, row0, rows_total, Lh1, g0, gend, rdm, mag, G, g.Gp);
+    } else if constexpr (EPI) {
         sh_pass<R0, true, NB0, SH, K2_THREADS, M, NS2, CMP>(L, rs, rows, twI + TW2, StoreLds<V>{L});
         k2_epilogue<T, SH>(L, rs, rows, row0, rows_total, Lh1, g0, gend, rdm, mag, G, g.Gp);
     } else {
@@ -1736,13 +1855,13 @@ __global__ __launch_bounds__(K2_THREADS, WGS) void k2_pc(Geometry g, DevConsts k
     typedef cx<T> V;
     V* L = reinterpret_cast<V*>(rsp_lds);   // overlap-save rows | narrow: staged rows + taps
     const int f = blockIdx.y;
-    const int wg = k.k2order[blockIdx.x];   // the plan's dispatch order (job kinds interleaved)
-    int ji = 0;
-    while (ji + 1 < g.njobs && wg >= g.jobs[ji + 1].wg_begin) ++ji;
-    const K2Job job = g.jobs[ji];
-    const SegDesc& sd = g.segs[job.seg];
+    // the plan's dispatch order (job kinds interleaved) as one record per workgroup: a single scalar
+    // load, where a dispatch-order entry and a search of g.jobs were 3 to 5 dependent ones
+    const K2Rec rec = k.k2rec[blockIdx.x];
+    const K2Job job{rec.seg, rec.blk, 0, 0};   // the block jobs read seg and blk
+    const SegDesc& sd = g.segs[rec.seg];
     const int rows = sd.rows_per_wg;
-    const int row0 = (wg - job.wg_begin) * rows;
+    const int row0 = rec.row0;
     const V* __restrict__ z = static_cast<const V*>(fp.z[f]);
     V* __restrict__ rdm = static_cast<V*>(fp.rdm[f]);
     T* __restrict__ mag = static_cast<T*>(fp.mag[f]);

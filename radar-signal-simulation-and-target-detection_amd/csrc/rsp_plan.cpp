@@ -148,6 +148,7 @@ struct rsp_plan {
     // stage-3 range CFAR (rsp_stage3_cfar, rsp_process_stage2_cfar): the segments' gate counts, whether
     // d_aux holds a stage-2 result, and device buffers that grow on demand (freed with the plan)
     int32_t gates[3] = {0, 0, 0};
+    std::vector<K2Rec> k2rec;     // host copy of DevConsts::k2rec (rsp_query_k2_records)
     bool aux_valid = false;
     struct DevBuf {
         void* p = nullptr;
@@ -780,15 +781,16 @@ int32_t rsp_plan_create_ex(const rsp_sig_config* cfg, const rsp_cfar_params* cfa
     // ---- constants to the device, in the plan's precision
     DevConsts& k = p->k;
     double *dra, *dva, *dang, *dkl;
-    int* dord;
+    K2Rec* drec;
     if ((rc = p->upload_r(&k.Atab, h.atab)) || (rc = p->upload_c(&k.twP, h.twP)) || (rc = p->upload_c(&k.twPp, h.twPp)) ||
         (rc = p->upload_c(&k.twD, h.twD)) || (rc = p->upload_c(&k.twQ, h.twQ)) || (rc = p->upload_r(&k.win, h.win)) ||
         (rc = p->upload_r(&k.taps, h.taps)) || (rc = p->upload_c(&k.H, h.H)) || (rc = p->upload_c(&k.twM, h.twM)) ||
         (rc = p->upload(&dra, h.range_axis)) || (rc = p->upload(&dva, h.velocity_axis)) ||
-        (rc = p->upload(&dang, h.beam_angles)) || (rc = p->upload(&dkl, h.klut)) || (rc = p->upload(&dord, h.k2order)))
+        (rc = p->upload(&dang, h.beam_angles)) || (rc = p->upload(&dkl, h.klut)) || (rc = p->upload(&drec, h.k2rec)))
         return bail(rc);
     k.range_axis = dra; k.velocity_axis = dva; k.beam_angles = dang; k.klut = dkl;
-    k.k2order = dord;
+    k.k2rec = drec;
+    p->k2rec = std::move(h.k2rec);
     k.deltaR = pre->deltaR; k.deltaV = pre->deltaV;
     const Geometry& g = p->g;
     if (pre->tx_pulse) {
@@ -846,6 +848,11 @@ int32_t rsp_query_k2_layout(const rsp_plan* p, rsp_k2_layout* out) {
     if (!p || !out) return fail(RSP_ERR_INVALID, "null argument");
     rsp_fill_k2_layout(p->g, p->gates, out);
     return RSP_OK;
+}
+
+int32_t rsp_query_k2_records(const rsp_plan* p, rsp_k2_record* out, int32_t cap, int32_t* n) {
+    if (!p) return fail(RSP_ERR_INVALID, "null argument");
+    return rsp_fill_k2_records(p->k2rec, out, cap, n);
 }
 
 int32_t rsp_process_cube(rsp_plan* p, const void* cube, int32_t dtype, int32_t layout, int32_t frame_idx,

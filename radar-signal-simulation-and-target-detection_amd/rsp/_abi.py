@@ -96,6 +96,10 @@ class K2Layout(ct.Structure):
                 ('njobs', ct.c_int32), ('nwg', ct.c_int32), ('seg', K2Segment * 3)]
 
 
+class K2Record(ct.Structure):
+    _fields_ = [(n, ct.c_int32) for n in ('seg', 'blk', 'row0', 'wg')]
+
+
 class Stage3CfarParams(ct.Structure):
     _fields_ = [('refCells_R', ct.c_int32), ('saveCells_R', ct.c_int32), ('CFARmethod_R', ct.c_int32),
                 ('MTD_0v_num', ct.c_int32), ('T_CFAR', ct.c_double)]
@@ -218,6 +222,11 @@ PROTOTYPES = {
     'rsp_plan_describe_k2': (ct.c_int32, [ct.POINTER(SigConfig), ct.POINTER(CfarParams), ct.POINTER(ClusterParams),
                                           ct.POINTER(Precomputed), ct.POINTER(PlanOptions), ct.c_int32,
                                           ct.POINTER(K2Layout)]),
+    'rsp_query_k2_records': (ct.c_int32, [_P, ct.POINTER(K2Record), ct.c_int32, ct.POINTER(ct.c_int32)]),
+    'rsp_plan_describe_k2_records': (ct.c_int32, [ct.POINTER(SigConfig), ct.POINTER(CfarParams),
+                                                  ct.POINTER(ClusterParams), ct.POINTER(Precomputed),
+                                                  ct.POINTER(PlanOptions), ct.c_int32, ct.POINTER(K2Record), ct.c_int32,
+                                                  ct.POINTER(ct.c_int32)]),
     'rsp_process_cube': (ct.c_int32, [_P, _P, ct.c_int32, ct.c_int32, ct.c_int32, ct.POINTER(FrameOut)]),
     'rsp_process_targets': (ct.c_int32, [_P, ct.POINTER(TargetIn), ct.c_int32, ct.c_int32, ct.c_uint64,
                                          ct.c_double, ct.POINTER(FrameOut)]),

@@ -162,6 +162,28 @@ def describe_k2(config, cfar_params, cluster_params, precomputed_data, precision
     return _k2_dict(L)
 
 
+K2_RECORD_FIELDS = ('seg', 'blk', 'row0', 'wg')   # rsp_k2_record
+
+
+def _k2_records(call):
+    n = ct.c_int32(0)
+    check(call(None, 0, ct.byref(n)))
+    rec = (_abi.K2Record * max(n.value, 1))()
+    check(call(rec, n.value, ct.byref(n)))
+    return np.array([[getattr(r, f) for f in K2_RECORD_FIELDS] for r in rec[:n.value]], dtype=np.int32).reshape(-1, 4)
+
+
+def describe_k2_records(config, cfar_params, cluster_params, precomputed_data, precision='c128', k1_tiled=False,
+                        ncu=256):
+    """``Plan.k2_records()`` of the plan these arguments would give, without a device
+    (rsp_plan_describe_k2_records); refusals as ``describe``."""
+    keep = []
+    cfg, cfar, cluster, pre = _marshal(config, cfar_params, cluster_params, precomputed_data, keep)
+    opt = _options(0, 1, precision, k1_tiled, 'amplitude')
+    return _k2_records(lambda out, cap, n: lib().rsp_plan_describe_k2_records(
+        ct.byref(cfg), ct.byref(cfar), ct.byref(cluster), ct.byref(pre), ct.byref(opt), int(ncu), out, cap, n))
+
+
 HIT_DTYPE = np.dtype([('v_idx', np.int32), ('r_idx', np.int32), ('beam_idx', np.int32), ('reserved', np.int32),
                       ('amp', np.float64), ('threshold', np.float64)])   # rsp_stage3_hit
 STAGE3_WANT = ('mtd', 'amp', 'flags', 'threshold', 'hits')
@@ -289,6 +311,11 @@ class Plan:
         L = _abi.K2Layout()
         check(lib().rsp_query_k2_layout(self.h, ct.byref(L)))
         return _k2_dict(L)
+
+    def k2_records(self):
+        """The pulse-compression workgroups in dispatch order (rsp_query_k2_records): an int32 array
+        [nwg, 4] of ``K2_RECORD_FIELDS``, row i what workgroup i of a k2_pc launch reads."""
+        return _k2_records(lambda out, cap, n: lib().rsp_query_k2_records(self.h, out, cap, n))
 
     # ---- synchronous frame paths ---------------------------------------------------------
     def _frame_out(self, want_rdm, want_cfar):
