@@ -165,6 +165,11 @@ const char* rsp_last_error(void);
                                  of main_plot_snr_vs_angle_error.m:455-462, instead of fsf:282-290's
                                  amplitude ratio (|S_A| - |S_B|) / (|S_A| + |S_B| + eps).  K2 then
                                  writes every frame's complex RD map (the caller's, or plan-owned) */
+#define RSP_PLAN_K2_ALL_ROWS 4   /* the queue pulse-compresses every Doppler row of every frame.
+                                 Without it a plan whose CFAR window is the compile-time 5/5/10/10
+                                 one computes the rows under test, [hV, prtNum - hV) with hV = 15, and
+                                 of the rows outside them only those a detection reads (rsp_k2_row_set);
+                                 the results are the same bit for bit.  For tests and A/B timing */
 typedef struct rsp_plan_options {
     int32_t device;              /* HIP device ordinal (0)                                   */
     int32_t frames_per_launch;   /* frames batched into each kernel launch by the queue (1)  */
@@ -268,6 +273,33 @@ typedef struct rsp_k2_record {
 } rsp_k2_record;
 int32_t rsp_query_k2_records(const rsp_plan* plan, rsp_k2_record* out, int32_t cap, int32_t* n);
 
+/* The rows of one pulse-compression launch and its record table.  Row i < total of a set is Doppler
+ * row base + j + (j >= split ? gap : 0), j = i mod n, of beam i / n; a record's row0 counts rows of
+ * the set.  RSP_K2_ROWS_ALL: every row, the table of rsp_query_k2_records.  RSP_K2_ROWS_BAND: the
+ * rows the cross CFAR tests.  RSP_K2_ROWS_EDGE: the hV rows on either side of them, launched after
+ * the CFAR for the rows a detection reads.  A plan without the band route (another CFAR window,
+ * prtNum <= 2 hV) reports n = total = nwg = 0 and no records for the last two. */
+#define RSP_K2_ROWS_ALL 0
+#define RSP_K2_ROWS_BAND 1
+#define RSP_K2_ROWS_EDGE 2
+typedef struct rsp_k2_row_set {
+    int32_t n, base, split, gap;
+    int32_t total;            /* rows of the launch: beam_num * n                               */
+    int32_t nwg;              /* workgroups = records of the table                              */
+} rsp_k2_row_set;
+int32_t rsp_query_k2_row_set(const rsp_plan* plan, int32_t which, rsp_k2_row_set* set, rsp_k2_record* out,
+                             int32_t cap, int32_t* n);
+
+/* What the queue's band route did since the last reset (or the plan's creation): frames that went
+ * through launch batches, those of them on the band route, edge rows pulse-compressed on demand
+ * (counted once per row, on the first segment's workgroups) and cells whose full CFAR test waited
+ * for such rows. */
+typedef struct rsp_band_counters {
+    int64_t frames, band_frames, edge_rows, deferred_cells;
+} rsp_band_counters;
+int32_t rsp_band_counters_get(const rsp_plan* plan, rsp_band_counters* out);
+int32_t rsp_band_counters_reset(rsp_plan* plan);
+
 /* What rsp_plan_create_ex would build for these arguments on a device of `ncu` compute units,
  * without a device: the same checks (opt->device aside), refusals and messages, and the values
  * rsp_query_sizes and rsp_query_k1_route report for the created plan.  `sizes` / `route` may be
@@ -288,6 +320,12 @@ int32_t rsp_plan_describe_k2_records(const rsp_sig_config* cfg, const rsp_cfar_p
                                      const rsp_cluster_params* cluster, const rsp_precomputed* pre,
                                      const rsp_plan_options* opt, int32_t ncu, rsp_k2_record* out, int32_t cap,
                                      int32_t* n);
+
+/* rsp_query_k2_row_set without a device */
+int32_t rsp_plan_describe_k2_row_set(const rsp_sig_config* cfg, const rsp_cfar_params* cfar,
+                                     const rsp_cluster_params* cluster, const rsp_precomputed* pre,
+                                     const rsp_plan_options* opt, int32_t ncu, int32_t which, rsp_k2_row_set* set,
+                                     rsp_k2_record* out, int32_t cap, int32_t* n);
 
 /* Cube-in path: S5..S11 of fun_process_single_frame on one host cube
  * (layout RSP_LAYOUT_PNC, dtype RSP_C64 or RSP_C128; converted to the plan's precision

@@ -92,7 +92,8 @@ void rsp_synth_targets(const SynthConsts& sc, const rsp_target_in* t, int nt, do
     }
 }
 
-void rsp_stage_bytes(const Geometry& g, int es, int nf, bool rdm, int cap, int64_t* out) {
+void rsp_stage_bytes(const Geometry& g, int es, int nf, bool rdm, int cap, int64_t* out, int k2_rows) {
+    const int64_t kr = k2_rows < 0 ? g.P : k2_rows;                       // Doppler rows per beam K2 launches
     const int64_t rs = es / 2;                                            // real element bytes
     const int64_t cube = (int64_t)g.C * g.nU * g.P * es;                  // used fast-time samples
     const int64_t z = (int64_t)g.B * g.nU * g.P * es;                     // Doppler-domain rows
@@ -100,7 +101,7 @@ void rsp_stage_bytes(const Geometry& g, int es, int nf, bool rdm, int cap, int64
     if (cap > 0) out[0] = nf * (cube + z);
     // the complex RD map, when written, is read by K3 only at the detected cells (2 values per
     // detection, not a map-sized stream), so K3's bytes stay the magnitude maps
-    if (cap > 1) out[1] = nf * (z + mag + (rdm ? (int64_t)g.B * g.P * g.G * es : 0));
+    if (cap > 1) out[1] = nf * ((z + mag) * kr / g.P + (rdm ? (int64_t)g.B * kr * g.G * es : 0));
     if (cap > 2) out[2] = nf * k3_map_bytes(g, (int)rs);   // the rows under test
 }
 

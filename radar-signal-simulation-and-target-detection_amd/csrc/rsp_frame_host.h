@@ -66,7 +66,8 @@ void rsp_synth_targets(const SynthConsts& sc, const rsp_target_in* t, int nt, do
 
 // Algorithmic bytes of rsp_profile_stages_rdm per launch of nf frames (DESIGN.md "Measurement"):
 // the first min(cap, 3) of K1, K2, K3.  es: bytes of a complex element; rdm: K2 writes the complex
-// RD map (the caller's maps, or the lane's own with the complex-ratio monopulse).
-void rsp_stage_bytes(const Geometry& g, int es, int nf, bool rdm, int cap, int64_t* out);
+// RD map (the caller's maps, or the lane's own with the complex-ratio monopulse).  k2_rows: the
+// Doppler rows per beam the K2 launch covers (the band route's rows under test; < 0: all P).
+void rsp_stage_bytes(const Geometry& g, int es, int nf, bool rdm, int cap, int64_t* out, int k2_rows = -1);
 // ... and of rsp_profile_stage3's three forms over `cells` cells
 void rsp_stage3_bytes(int64_t cells, int es, int64_t out[3]);

@@ -349,29 +349,6 @@ int derive_k1_tile(Geometry& g, const std::vector<Interval>& U) {
 }
 
 // ---- K2 jobs and dispatch order -------------------------------------------------------------
-int derive_k2_jobs(PlanHost& h) {
-    Geometry& g = h.g;
-    const int rows_total = g.B * g.P;
-    int wg = 0;
-    for (size_t si = 0; si < h.segs.size(); ++si) {
-        const SegDesc& s = h.segs[si];
-        const int nwg = (rows_total + s.rows_per_wg - 1) / s.rows_per_wg;
-        const int nbl = (s.type == 1) ? s.nblocks : 1;
-        for (int blk = 0; blk < nbl; ++blk) {
-            h.jobs.push_back(K2Job{(int)si, blk, wg, nwg});
-            wg += nwg;
-        }
-    }
-    g.nseg = (int)h.segs.size();
-    g.njobs = (int)h.jobs.size();
-    if (g.nseg > RSP_MAX_SEG || g.njobs > RSP_MAX_JOBS)
-        return fail(RSP_ERR_UNSUPPORTED, "%d overlap-save jobs exceed %d", g.njobs, RSP_MAX_JOBS);
-    for (int q = 0; q < g.nseg; ++q) g.segs[q] = h.segs[q];
-    for (int q = 0; q < g.njobs; ++q) g.jobs[q] = h.jobs[q];
-    g.nwg_k2 = wg;
-    return RSP_OK;
-}
-
 // K2 dispatch order.  (1) Workgroups of a job covering adjacent rows form groups of gs
 // (below), at key (i + 1/2) / ngroups_j, so that the narrow FIR, medium and long jobs are
 // interleaved in proportion through the launch.  (2) Workgroups go to the 8 XCDs
@@ -381,12 +358,25 @@ int derive_k2_jobs(PlanHost& h) {
 // 128 / (NT esz) adjacent rows, a workgroup rows_per_wg of them, so gs = the most
 // workgroups one line spans over the jobs (x2: NT = 4, one-row long blocks -> 2; x4:
 // NT = 1 -> 8).  Workgroups left over go last.
-int derive_k2_order(PlanHost& h) {
-    const Geometry& g = h.g;
+}  // namespace
+
+int k2_build_records(const Geometry& g, const std::vector<SegDesc>& segs, int rows_total, std::vector<K2Job>* jobs_out,
+                     std::vector<int>* order_out, std::vector<K2Rec>* rec) {
+    std::vector<K2Job> jobs;
+    int nwg_total = 0;
+    for (size_t si = 0; si < segs.size(); ++si) {
+        const SegDesc& s = segs[si];
+        const int nwg = (rows_total + s.rows_per_wg - 1) / s.rows_per_wg;
+        const int nbl = (s.type == 1) ? s.nblocks : 1;
+        for (int blk = 0; blk < nbl; ++blk) {
+            jobs.push_back(K2Job{(int)si, blk, nwg_total, nwg});
+            nwg_total += nwg;
+        }
+    }
     const int esz = (int)cplx_bytes(g);
     int gs = 1;
-    for (const K2Job& jb : h.jobs) {
-        const int rw = std::max(h.segs[jb.seg].rows_per_wg, 1);
+    for (const K2Job& jb : jobs) {
+        const int rw = std::max(segs[jb.seg].rows_per_wg, 1);
         gs = std::max(gs, std::min(8, 128 / std::max(rw * g.NZ * esz, 1)));
     }
     // (3) The overlap-save blocks of one row read overlapping sample windows (Lh - 1 samples
@@ -398,9 +388,9 @@ int derive_k2_order(PlanHost& h) {
     struct Unit { double key; std::vector<int> wgs; };
     std::vector<Unit> units;
     std::vector<int> single;
-    for (int si = 0; si < (int)h.segs.size(); ++si) {
+    for (int si = 0; si < (int)segs.size(); ++si) {
         std::vector<const K2Job*> blks;
-        for (const K2Job& jb : h.jobs)
+        for (const K2Job& jb : jobs)
             if (jb.seg == si) blks.push_back(&jb);
         if (blks.empty()) continue;
         const int wc = blks[0]->wg_count, ng = wc / gs;   // every block of a segment covers all rows
@@ -421,24 +411,61 @@ int derive_k2_order(PlanHost& h) {
             if (q[c].size() < q[x].size()) x = c;
         q[x].insert(q[x].end(), u.wgs.begin(), u.wgs.end());
     }
-    std::vector<int>& order = h.k2order;
+    std::vector<int> order;
     size_t qmax = 0;
     for (auto& v : q) qmax = std::max(qmax, v.size());
     for (size_t sl = 0; sl < qmax; ++sl)
         for (int x = 0; x < 8; ++x)
             if (sl < q[x].size()) order.push_back(q[x][sl]);
     for (int w : single) order.push_back(w);
-    if ((int)order.size() != g.nwg_k2)
-        return fail(RSP_ERR_INVALID, "K2 dispatch order covers %d of %d workgroups", (int)order.size(), g.nwg_k2);
+    if ((int)order.size() != nwg_total)
+        return fail(RSP_ERR_INVALID, "K2 dispatch order covers %d of %d workgroups", (int)order.size(), nwg_total);
     // The same order as records: what k2_pc would find for workgroup `wg` by searching the job list
-    h.k2rec.reserve(order.size());
+    rec->clear();
+    rec->reserve(order.size());
     for (int wg : order) {
         size_t ji = 0;
-        while (ji + 1 < h.jobs.size() && wg >= h.jobs[ji + 1].wg_begin) ++ji;
-        const K2Job& jb = h.jobs[ji];
-        h.k2rec.push_back(K2Rec{jb.seg, jb.blk, (wg - jb.wg_begin) * h.segs[jb.seg].rows_per_wg, wg});
+        while (ji + 1 < jobs.size() && wg >= jobs[ji + 1].wg_begin) ++ji;
+        const K2Job& jb = jobs[ji];
+        rec->push_back(K2Rec{jb.seg, jb.blk, (wg - jb.wg_begin) * segs[jb.seg].rows_per_wg, wg});
     }
+    if (jobs_out) *jobs_out = std::move(jobs);
+    if (order_out) *order_out = std::move(order);
     return RSP_OK;
+}
+
+K2Rows k2_row_set(const Geometry& g, int which) {
+    const int hV = RSP_K3_FAST_HV;
+    if (which == K2SET_ALL) return K2Rows{g.P, 0, g.P, 0, g.B * g.P};
+    if (!k3_fast_params(g) || g.P <= 2 * hV) return K2Rows{0, 0, 0, 0, 0};
+    if (which == K2SET_BAND) return K2Rows{g.P - 2 * hV, hV, g.P - 2 * hV, 0, g.B * (g.P - 2 * hV)};
+    return K2Rows{2 * hV, 0, hV, g.P - 2 * hV, g.B * 2 * hV};
+}
+
+namespace {
+
+// The all-rows jobs travel in the Geometry (g.jobs, g.nwg_k2); the segments must be final.
+int derive_k2_jobs(PlanHost& h) {
+    Geometry& g = h.g;
+    int rc = k2_build_records(g, h.segs, g.B * g.P, &h.jobs, &h.k2order, &h.k2rec);
+    if (rc) return rc;
+    g.nseg = (int)h.segs.size();
+    g.njobs = (int)h.jobs.size();
+    if (g.nseg > RSP_MAX_SEG || g.njobs > RSP_MAX_JOBS)
+        return fail(RSP_ERR_UNSUPPORTED, "%d overlap-save jobs exceed %d", g.njobs, RSP_MAX_JOBS);
+    for (int q = 0; q < g.nseg; ++q) g.segs[q] = h.segs[q];
+    for (int q = 0; q < g.njobs; ++q) g.jobs[q] = h.jobs[q];
+    g.nwg_k2 = (int)h.k2rec.size();
+    return RSP_OK;
+}
+
+// The band and edge sets' tables (after derive_k3_tiling: the sets follow K3's window)
+int derive_k2_sets(PlanHost& h) {
+    const Geometry& g = h.g;
+    for (int w = 0; w < 3; ++w) h.k2rows[w] = k2_row_set(g, w);
+    if (!h.k2rows[K2SET_BAND].n) return RSP_OK;
+    int rc = k2_build_records(g, h.segs, h.k2rows[K2SET_BAND].total, nullptr, nullptr, &h.k2rec_band);
+    return rc ? rc : k2_build_records(g, h.segs, h.k2rows[K2SET_EDGE].total, nullptr, nullptr, &h.k2rec_edge);
 }
 
 // ---- K3 tiling ------------------------------------------------------------------------------
@@ -602,7 +629,7 @@ int rsp_plan_check_args(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, 
     if (!cfg || !cfar || !cluster || !pre || !opt) return fail(RSP_ERR_INVALID, "null argument");
     if (opt->precision != RSP_C64 && opt->precision != RSP_C128)
         return fail(RSP_ERR_INVALID, "precision must be RSP_C128 or RSP_C64, got %d", opt->precision);
-    if (opt->flags & ~(RSP_PLAN_K1_TILED | RSP_PLAN_MONOPULSE_COMPLEX))
+    if (opt->flags & ~(RSP_PLAN_K1_TILED | RSP_PLAN_MONOPULSE_COMPLEX | RSP_PLAN_K2_ALL_ROWS))
         return fail(RSP_ERR_INVALID, "unknown plan flags 0x%x", opt->flags);
     const int C = cfg->channel_num, B = cfg->beam_num, P = cfg->prtNum, N = cfg->point_PRT;
     const int g1 = pre->N_gate_narrow, g2 = pre->N_gate_medium, g3 = pre->N_gate_long, G = pre->N_total_gate;
@@ -649,7 +676,7 @@ int rsp_plan_derive(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, cons
         (rc = derive_k3_tiling(g)))
         return rc;
     build_tables(pre, h);
-    if ((rc = derive_k2_order(h))) return rc;
+    if ((rc = derive_k2_sets(h))) return rc;
     h.z_elems = (size_t)B * g.nzc * g.NZ * P;
     h.rdm_elems = (size_t)B * P * G;
     h.mag_elems = (size_t)B * P * g.Gp;
@@ -770,6 +797,26 @@ extern "C" int32_t rsp_plan_describe_k2_records(const rsp_sig_config* cfg, const
     PlanHost h;
     if ((rc = rsp_plan_derive(cfg, cfar, cluster, pre, opt, ncu, &h))) return rc;
     return rsp_fill_k2_records(h.k2rec, out, cap, n);
+}
+
+int rsp_fill_k2_row_set(const K2Rows rows[3], const std::vector<K2Rec>* const rec[3], int32_t which, rsp_k2_row_set* set,
+                        rsp_k2_record* out, int32_t cap, int32_t* n) {
+    if (which < 0 || which > 2) return fail(RSP_ERR_INVALID, "row set %d (RSP_K2_ROWS_ALL, _BAND or _EDGE)", which);
+    const K2Rows& r = rows[which];
+    if (set) *set = rsp_k2_row_set{r.n, r.base, r.split, r.gap, r.total, (int32_t)rec[which]->size()};
+    return rsp_fill_k2_records(*rec[which], out, cap, n);
+}
+
+extern "C" int32_t rsp_plan_describe_k2_row_set(const rsp_sig_config* cfg, const rsp_cfar_params* cfar,
+                                                const rsp_cluster_params* cluster, const rsp_precomputed* pre,
+                                                const rsp_plan_options* opt, int32_t ncu, int32_t which,
+                                                rsp_k2_row_set* set, rsp_k2_record* out, int32_t cap, int32_t* n) {
+    int rc = rsp_plan_check_args(cfg, cfar, cluster, pre, opt);
+    if (rc) return rc;
+    PlanHost h;
+    if ((rc = rsp_plan_derive(cfg, cfar, cluster, pre, opt, ncu, &h))) return rc;
+    const std::vector<K2Rec>* const rec[3] = {&h.k2rec, &h.k2rec_band, &h.k2rec_edge};
+    return rsp_fill_k2_row_set(h.k2rows, rec, which, set, out, cap, n);
 }
 
 // ---- stage-3 range CFAR (debug_simulated_data_processing_v2.m:419-511) ----

@@ -61,6 +61,26 @@ struct K2Rec {
     int seg, blk, row0, wg;
 };
 
+// The rows of one k2_pc launch: row i of the set, i < total = B n, is Doppler row
+// v = base + j + (j >= split ? gap : 0), j = i mod n, of beam b = i / n.  Three sets: every row
+// (n = P); the band of rows K3's compile-time window tests, [hV, P - hV); the edge rows around it,
+// [0, hV) and [P - hV, P), which the fast path computes only where a detection reads them.
+struct K2Rows {
+    int n, base, split, gap, total;
+};
+// rho = b P + v of row i: the row's index in z, the RD map and the magnitude map.  Everything a
+// row's workgroup computes depends on rho alone, whichever set, launch or workgroup holds it.
+RSP_HD inline int k2_rho(const K2Rows& s, int P, int i) {
+    const int b = i / s.n, j = i - b * s.n;
+    return b * P + s.base + j + (j >= s.split ? s.gap : 0);
+}
+enum { K2SET_ALL = 0, K2SET_BAND = 1, K2SET_EDGE = 2 };
+// hV of the compile-time 5/5/10/10 window, the one the band route exists for
+#define RSP_K3_FAST_HV 15
+// beams whose edge-row flags fit a frame's flag block (2 hV bytes per beam)
+#define RSP_NEED_BMAX 16
+#define RSP_NEED_BYTES (RSP_NEED_BMAX * 2 * RSP_K3_FAST_HV)
+
 #define RSP_MAX_SEG 3
 #define RSP_MAX_JOBS 16
 #define RSP_MAX_IVL 4
@@ -289,7 +309,18 @@ struct PlanHost {
     std::vector<double> range_axis, velocity_axis, beam_angles, klut;
     std::vector<int> k2order;        // pulse-compression workgroup dispatch order
     std::vector<K2Rec> k2rec;        // the same as per-workgroup records: what the plan uploads
+    // the band and edge row sets (K2SET_BAND, K2SET_EDGE) and their record tables, built like k2rec
+    // (n = 0 and no records: the plan has no such set, see k2_row_set)
+    K2Rows k2rows[3] = {};
+    std::vector<K2Rec> k2rec_band, k2rec_edge;
 };
+// The row set `which` of a plan: n = 0 for the band and edge sets of a plan whose K3 is not the
+// compile-time 5/5/10/10 kernel (they follow that window's hV) or whose P has no row under test.
+K2Rows k2_row_set(const Geometry& g, int which);
+// One record table: the jobs (segment x block) over `rows_total` rows, interleaved in proportion and
+// laid out over the XCDs (derive_k2_order says how).  jobs / order may be null.
+int k2_build_records(const Geometry& g, const std::vector<SegDesc>& segs, int rows_total, std::vector<K2Job>* jobs,
+                     std::vector<int>* order, std::vector<K2Rec>* rec);
 
 // Stage-3 range CFAR (k_s3_cfar, rsp_stage3.hip).  A workgroup resolves RSP_S3_ROWS Doppler rows
 // (4 waves, a row per wave and pass) of RSP_S3_CH range cells on the map's own column grid, each
@@ -348,3 +379,6 @@ void rsp_fill_k2_layout(const Geometry& g, const int32_t gates[RSP_MAX_SEG], rsp
 // rsp_query_k2_records / rsp_plan_describe_k2_records: the first min(cap, rec.size()) records into out
 // (may be NULL when cap is 0), rec.size() into *n.
 int rsp_fill_k2_records(const std::vector<K2Rec>& rec, rsp_k2_record* out, int32_t cap, int32_t* n);
+// rsp_query_k2_row_set / rsp_plan_describe_k2_row_set: set `which` of rows / rec (all, band, edge)
+int rsp_fill_k2_row_set(const K2Rows rows[3], const std::vector<K2Rec>* const rec[3], int32_t which, rsp_k2_row_set* set,
+                        rsp_k2_record* out, int32_t cap, int32_t* n);

@@ -48,7 +48,13 @@ struct FramePtrs {
     void* smap[RSP_MAX_F];         // optional: rdm_for_cfar_all [B-1][P][G] as K3 thresholds it (fsf:184-187)
     unsigned long long* trace;     // diagnostic builds (-DRSP_DEBUG_KNOBS): 4 stamps per workgroup
     DevDet* dets[RSP_MAX_F];
+    // record 0 of a frame's detection list: [0] detections, [1] deferred cells, [2] edge rows
+    // computed on demand; zeroed by K1 (in the pipeline) with the frame's flag block
     int* count[RSP_MAX_F];
+    // band route (else null): RSP_NEED_BYTES flags of the frame's edge rows, byte b 2hV + e for edge
+    // row e of beam b, and its deferred cells, (pair << 16 | v, r) each
+    unsigned char* need[RSP_MAX_F];
+    int2* defer[RSP_MAX_F];
 };
 
 struct DevConsts {
@@ -72,8 +78,17 @@ struct DevConsts {
 // Launchers (rsp_kernels.hip).  `mode` bits for K1: 1 = apply DBF, 2 = apply MTD.
 hipError_t launch_k1(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, int mode, hipStream_t s);
 hipError_t launch_stream_copy(const void* in, void* out, size_t n16, int ncu, hipStream_t s);
-hipError_t launch_k2(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, int rows, hipStream_t s);
-hipError_t launch_k3(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, hipStream_t s);
+// K2 of every row (the plan's table k.k2rec), or of one row set with its record table; on_demand:
+// the edge set, each workgroup only if fp.need flags one of its rows
+hipError_t launch_k2(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, hipStream_t s);
+hipError_t launch_k2_set(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, const K2Rows& rows,
+                         const K2Rec* recs, int nwg, bool on_demand, hipStream_t s);
+// K3: whole (K3_WHOLE), or the band route's two phases: K3_DEFER leaves the cells whose test reads an
+// edge row on fp.defer and flags those rows in fp.need; K3_FINISH (after the on-demand K2) tests them.
+// defer_cap: entries of each frame's deferred list.
+enum { K3_WHOLE = 0, K3_DEFER = 1, K3_FINISH = 2 };
+hipError_t launch_k3(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, hipStream_t s,
+                     int phase = K3_WHOLE, int defer_cap = 0);
 hipError_t launch_mtd_cols(const Geometry& g, const DevConsts& k, const void* pc, void* rdm, hipStream_t s);
 // S4 + S4.1: tab holds RSP_MAX_SYNTH_TARGETS x (P + C) complex doubles (the per-target phasors)
 hipError_t launch_synth(const Geometry& g, const double* tx, const SynthTargets& tg, int nt, void* tab, int frame_idx,

@@ -908,6 +908,16 @@ __device__ __forceinline__ void k1_dft_rq_r(int R, V* buf, int rs, int ncols, in
 // input channels are the beams).  Non-power-of-two P = R Q takes the factored DFT (k1_dft_rq),
 // any other the direct DFT (O(P^2) per column).
 // RQ: the instantiation that runs the factored DFT (its registers stay out of the others).
+// K3's state of frame f, zeroed by the workgroup that takes the frame's first tile: the detection
+// counter, the deferred-cell and on-demand-row counters next to it and, on the band route, the
+// frame's edge-row flags, so that no flag survives into the lane's next batch.
+__device__ __forceinline__ void k1_zero_frame_state(const FramePtrs& fp, int f) {
+    static_assert(K1_THREADS >= RSP_NEED_BYTES / 4 && RSP_NEED_BYTES % 4 == 0, "one flag word per thread");
+    if (!fp.count[f]) return;
+    if (threadIdx.x < 3) fp.count[f][threadIdx.x] = 0;
+    if (fp.need[f] && threadIdx.x < RSP_NEED_BYTES / 4) reinterpret_cast<int*>(fp.need[f])[threadIdx.x] = 0;
+}
+
 template <class T, int BMAX, int CP, bool RQ>
 __global__ __launch_bounds__(K1_THREADS, 2) void k1_dbf_mtd(Geometry g, DevConsts k, FramePtrs fp, int mode) {
     typedef cx<T> V;
@@ -915,7 +925,7 @@ __global__ __launch_bounds__(K1_THREADS, 2) void k1_dbf_mtd(Geometry g, DevConst
     V* Y = reinterpret_cast<V*>(rsp_lds);   // [B][NT][Ppad] | twiddles
     const int f = blockIdx.y, tile = blockIdx.x;
     const int B = g.B, C = g.C, P = g.P, NT = g.NT, Ppad = g.Ppad;
-    if (tile == 0 && threadIdx.x == 0 && fp.count[f]) *fp.count[f] = 0;   // K3's detection counter
+    if (tile == 0) k1_zero_frame_state(fp, f);
     V* twl = Y + B * NT * Ppad;
     const bool fft = (mode & 2) && g.pow2P;
     const bool rq = RQ && (mode & 2);   // factored DFT: twl = twQ | W_P^i
@@ -1204,7 +1214,7 @@ __global__ __launch_bounds__(K1_THREADS, 1) void k1p_dbf_mtd(Geometry g, DevCons
         if (!EARLY && Tn < total) issue(Tn);   // next tile's loads fly during this tile's FFT + z stores
         const FrameTile ft = frame_tile(g, TT);
         const int f = ft.f, tile = ft.tile;
-        if (tile == 0 && threadIdx.x == 0 && fp.count[f]) *fp.count[f] = 0;   // K3's detection counter
+        if (tile == 0) k1_zero_frame_state(fp, f);
         V* __restrict__ z = static_cast<V*>(fp.z[f]);
         const StoreZ<V> sz{buf_rsrc(z, (unsigned)(B * g.nzc * P * g.NZ * sizeof(V))), lgNT, g.nzc, tile, P, half, ilog2(g.NZ)};
         // K1_DIF: in place, one barrier between its two passes (P = 256 as 16 x 16: K1 2.23 -> 2.13
@@ -1330,7 +1340,7 @@ __global__ __launch_bounds__(K1_THREADS, 1) void k1q_dbf_mtd(Geometry g, DevCons
         K1_STAMP(it, 1);
         const FrameTile ft = frame_tile(g, TT);
         const int f = ft.f, tile = ft.tile;
-        if (tile == 0 && threadIdx.x == 0 && fp.count[f]) *fp.count[f] = 0;   // K3's detection counter
+        if (tile == 0) k1_zero_frame_state(fp, f);
         __syncthreads();   // the tile (and, the first time, the tables) in LDS
         K1_STAMP(it, 2);
         V* __restrict__ z = static_cast<V*>(fp.z[f]);
@@ -1348,11 +1358,11 @@ template <class V>
 struct StoreRdm {   // last inverse pass: keep outputs i in [Lh-1, Lh-1+V) that map to gates < gend;
                     // also writes |x| (the CFAR input, fsf:184-185) into the magnitude map.
                     // Branch-free: rejected outputs get an out-of-range buffer offset.
-    __amdgpu_buffer_rsrc_t rdm, mag; int G; int Gp; int row0; int rows_total; int Lh1; int g0; int gend; bool has_rdm;
+    __amdgpu_buffer_rsrc_t rdm, mag; int G; int Gp; int row0; K2Rows rw; int P; int Lh1; int g0; int gend; bool has_rdm;
     __device__ __forceinline__ void put(int, int row, int o, int, V x) const {
         const int gg = g0 + o - Lh1;
-        const int rho = row0 + row;
-        const bool ok = o >= Lh1 && gg < gend && rho < rows_total;
+        const int rho = k2_rho(rw, P, row0 + row);
+        const bool ok = o >= Lh1 && gg < gend && row0 + row < rw.total;
         if (has_rdm) buf_st<RSP_RDM_AUX>(rdm, ok ? (unsigned)(rho * G + gg) * (unsigned)sizeof(V) : RSP_OOB, x);
         buf_st1(mag, ok ? (unsigned)(rho * Gp + gg) * (unsigned)sizeof(scal<V>) : RSP_OOB, cmag(x));
     }
@@ -1369,9 +1379,10 @@ struct StoreRowK {
     __amdgpu_buffer_rsrc_t rr, mr;
     unsigned lh1v, lh1s;   // Lh1 in bytes of V / of S
     int rskip;
-    __device__ __forceinline__ StoreRowK(V* rdm, S* mag, int G, int Gp, int rho, int rows_total, int Lh1, int g0,
+    // rho: the row's index in the maps (k2_rho); valid: the row exists (its set index < the set's total)
+    __device__ __forceinline__ StoreRowK(V* rdm, S* mag, int G, int Gp, int rho, bool valid, int Lh1, int g0,
                                          int gend) {
-        const unsigned n = rho < rows_total ? (unsigned)(gend - g0) : 0u;
+        const unsigned n = valid ? (unsigned)(gend - g0) : 0u;
         if (RDM) rr = buf_rsrc(rdm + (size_t)rho * G + g0, n * (unsigned)sizeof(V));
         mr = buf_rsrc(mag + (size_t)rho * Gp + g0, n * (unsigned)sizeof(S));
         lh1v = (unsigned)Lh1 * (unsigned)sizeof(V);
@@ -1397,17 +1408,18 @@ struct StoreRowK {
 // increasing in the compacted sample n' (tile-major, slot-minor), so a resource based at
 // n' = off (sample lo) that spans n' = off + hi - lo masks every sample outside [lo, hi] --
 // below wraps past num_records, above is past it.  rel(n') = the byte offset of n' in the
-// window (may wrap); zrow_window() returns the resource (num_records 0 for rows past
-// rows_total, which are uniform per wave here).
+// window (may wrap); zrow_window() returns the resource of row i of the launch's row set
+// (num_records 0 for rows past rows_total, which are uniform per wave here).
 struct ZWin {
     __amdgpu_buffer_rsrc_t r;
     int e_lo, PNT, lgNT, NT1;
     __device__ __forceinline__ int rel(int np) const { return (np >> lgNT) * PNT + (np & NT1) - e_lo; }
 };
 template <class V>
-__device__ __forceinline__ ZWin zrow_window(const Geometry& g, const V* z, int rho, int rows_total, int off, int lo,
-                                            int hi) {
+__device__ __forceinline__ ZWin zrow_window(const Geometry& g, const K2Rows& rw, const V* z, int i, int rows_total,
+                                            int off, int lo, int hi) {
     ZWin w;
+    const int rho = k2_rho(rw, g.P, i);
     const int b = rho / g.P, v = rho - b * g.P;
     w.lgNT = ilog2(g.NZ);
     w.NT1 = g.NZ - 1;
@@ -1416,7 +1428,7 @@ __device__ __forceinline__ ZWin zrow_window(const Geometry& g, const V* z, int r
     w.e_lo = (off >> w.lgNT) * w.PNT + (off & w.NT1);
     const int e_hi = (nph >> w.lgNT) * w.PNT + (nph & w.NT1);
     const V* base = z + ((size_t)b * g.nzc * g.P + v) * g.NZ + w.e_lo;
-    w.r = buf_rsrc(base, rho < rows_total ? (unsigned)(e_hi - w.e_lo + 1) * (unsigned)sizeof(V) : 0u);
+    w.r = buf_rsrc(base, i < rows_total ? (unsigned)(e_hi - w.e_lo + 1) * (unsigned)sizeof(V) : 0u);
     return w;
 }
 // The R0 samples n' = np0 + r NB0, r < R0, of one pass-0 butterfly through its row's window zw (a
@@ -1509,13 +1521,14 @@ __device__ __forceinline__ void k2_epi_row(const cx<T>* src, int pad0, int nkeep
         k2_epi_trip<T, SH, 1, RDM>(src, pad0, e0, nkeep, rr, mr);
 }
 template <class T, int SH>
-__device__ __forceinline__ void k2_epilogue(const cx<T>* L, int rs, int rows, int row0, int rows_total, int Lh1, int g0,
-                                            int gend, cx<T>* __restrict__ rdm, T* __restrict__ mag, int G, int Gp) {
+__device__ __forceinline__ void k2_epilogue(const cx<T>* L, int rs, int rows, int row0, const K2Rows& rw, int P, int Lh1,
+                                            int g0, int gend, cx<T>* __restrict__ rdm, T* __restrict__ mag, int G,
+                                            int Gp) {
     typedef cx<T> V;
     const int nkeep = gend - g0;
     for (int r = 0; r < rows; ++r) {
-        const int rho = row0 + r;   // uniform
-        if (rho >= rows_total) break;
+        if (row0 + r >= rw.total) break;
+        const int rho = k2_rho(rw, P, row0 + r);   // uniform
         const V* src = L + r * rs + Lh1;
         const int pad0 = SH ? Lh1 : 0;
         const __amdgpu_buffer_rsrc_t mr = buf_rsrc(mag + (size_t)rho * Gp + g0, (unsigned)nkeep * (unsigned)sizeof(T));
@@ -1561,7 +1574,8 @@ __device__ __forceinline__ auto k2_tw_src(const V* lds, const V* glob) {
 template <class T, int LGM, int PTS, bool EPI, bool NOPAD>
 __device__ __forceinline__ void k2_fft_job(const Geometry& g, const DevConsts& k, const SegDesc& sd, const K2Job& job,
                                            const cx<T>* __restrict__ z, cx<T>* __restrict__ rdm, T* __restrict__ mag,
-                                           int row0, int rows_total, cx<T>* L) {
+                                           int row0, const K2Rows& rw, cx<T>* L) {
+    const int rows_total = rw.total;
     typedef cx<T> V;
     constexpr int SH = k2_sh_np<T, NOPAD>();
     constexpr int M = 1 << LGM;
@@ -1593,7 +1607,7 @@ __device__ __forceinline__ void k2_fft_job(const Geometry& g, const DevConsts& k
     if constexpr (WROW) {
         const int rl = __builtin_amdgcn_readfirstlane(tid / nb0);
         // waves past the block's rows (fewer rows than 256 / nb0) load nothing
-        const ZWin zw = zrow_window(g, z, row0 + rl, rl < rows ? rows_total : 0, off, lo, hi);
+        const ZWin zw = zrow_window(g, rw, z, row0 + rl, rl < rows ? rows_total : 0, off, lo, hi);
         k2_load_wrow<nb0>(g, zw, a + (tid & (nb0 - 1)) - lo + off, v0[0]);
     }
     const __amdgpu_buffer_rsrc_t zr = buf_rsrc(z, (unsigned)(g.B * g.nzc * P * g.NZ * sizeof(V)));
@@ -1601,7 +1615,7 @@ __device__ __forceinline__ void k2_fft_job(const Geometry& g, const DevConsts& k
     for (int t = 0; t < (WROW ? 0 : NB0); ++t) {
         const int beta = tid + t * K2_THREADS;
         const int rl = beta / nb0, j = beta & (nb0 - 1);
-        const int rho = row0 + rl;
+        const int ri = row0 + rl, rho = k2_rho(rw, P, ri);
         const int b = rho / P, v = rho - b * P;
         // z index of sample n0 + r nb0: when NT | nb0 the tile advances by nb0/NT per r and the
         // in-tile slot is fixed, so element r sits at zb + r (nb0 P) (one multiply per thread)
@@ -1612,14 +1626,14 @@ __device__ __forceinline__ void k2_fft_job(const Geometry& g, const DevConsts& k
 #pragma unroll
             for (int r = 0; r < R0; ++r) {
                 const int n = a + j + r * nb0;
-                const bool ok = rho < rows_total && n >= lo && n <= hi;
+                const bool ok = ri < rows_total && n >= lo && n <= hi;
                 v0[t][r] = buf_ld<V>(zr, ok ? (unsigned)(zb + r * nb0 * P) * (unsigned)sizeof(V) : RSP_OOB);
             }
         } else {
 #pragma unroll
             for (int r = 0; r < R0; ++r) {
                 const int n = a + j + r * nb0;
-                const bool ok = rho < rows_total && n >= lo && n <= hi;
+                const bool ok = ri < rows_total && n >= lo && n <= hi;
                 v0[t][r] = buf_ld<V>(zr, ok ? (unsigned)zaddr(g, b, v, n - lo + off) * (unsigned)sizeof(V) : RSP_OOB);
             }
         }
@@ -1679,7 +1693,7 @@ __device__ __forceinline__ void k2_fft_job(const Geometry& g, const DevConsts& k
         // inverse passes 1 .. NP-1 (reversed radices) into LDS; then the valid overlap-save outputs
         // = stitched gates go to the maps
         fft_range<PlanI, 1, NP, 16, true, SH, K2_THREADS, CMP, XZ>(L, rs, rows, twI, StoreLds<V>{L}, StoreLds<V>{L});
-        k2_epilogue<T, SH>(L, rs, rows, row0, rows_total, Lh1, g0, gend, rdm, mag, G, g.Gp);
+        k2_epilogue<T, SH>(L, rs, rows, row0, rw, P, Lh1, g0, gend, rdm, mag, G, g.Gp);
     } else if constexpr (WROW) {
         // inverse passes 1 .. NP-2 into LDS, then the last one (Ns = nb0, input not swizzled:
         // XZ applies to the pass after an Ns = 1 pass only) stores the kept gates straight into
@@ -1687,19 +1701,20 @@ __device__ __forceinline__ void k2_fft_job(const Geometry& g, const DevConsts& k
         fft_range<PlanI, 1, NP - 1, 16, true, SH, K2_THREADS, CMP, XZ>(L, rs, rows, twI, StoreLds<V>{L}, StoreLds<V>{L});
         static_assert(NP >= 3 || XZ == 0, "last pass input is never swizzled");
         const auto twl_last = twI + TWIL;
-        const int rho = row0 + __builtin_amdgcn_readfirstlane(tid / nb0);
+        const int ri = row0 + __builtin_amdgcn_readfirstlane(tid / nb0), rho = k2_rho(rw, P, ri);
+        const bool valid = ri < rows_total;
         if (rdm)
             sh_pass<R0, true, NB0, SH, K2_THREADS, M, nb0, CMP, 0, false>(
-                L, rs, rows, twl_last, StoreRowK<V, true, nb0, R0>(rdm, mag, G, g.Gp, rho, rows_total, Lh1, g0, gend));
+                L, rs, rows, twl_last, StoreRowK<V, true, nb0, R0>(rdm, mag, G, g.Gp, rho, valid, Lh1, g0, gend));
         else
             sh_pass<R0, true, NB0, SH, K2_THREADS, M, nb0, CMP, 0, false>(
-                L, rs, rows, twl_last, StoreRowK<V, false, nb0, R0>(rdm, mag, G, g.Gp, rho, rows_total, Lh1, g0, gend));
+                L, rs, rows, twl_last, StoreRowK<V, false, nb0, R0>(rdm, mag, G, g.Gp, rho, valid, Lh1, g0, gend));
     } else {
         fft_range<PlanI, 1, NP, 16, true, SH, K2_THREADS, CMP, XZ, false>(
             L, rs, rows, twI, StoreLds<V>{L},
-            StoreRdm<V>{buf_rsrc(rdm, (unsigned)(rows_total * G * sizeof(V))),
-                        buf_rsrc(mag, (unsigned)(rows_total * g.Gp * sizeof(T))), G, g.Gp, row0, rows_total, Lh1, g0,
-                        gend, rdm != nullptr});
+            StoreRdm<V>{buf_rsrc(rdm, (unsigned)(g.B * P * G * sizeof(V))),
+                        buf_rsrc(mag, (unsigned)(g.B * P * g.Gp * sizeof(T))), G, g.Gp, row0, rw, P, Lh1, g0, gend,
+                        rdm != nullptr});
     }
 }
 
@@ -1717,7 +1732,8 @@ __device__ __forceinline__ void k2_fft_job(const Geometry& g, const DevConsts& k
 template <class T, int M, int R0, int R1, bool EPI, bool NOPAD>
 __device__ __forceinline__ void k2_fft_job_mix(const Geometry& g, const DevConsts& k, const SegDesc& sd, const K2Job& job,
                                                const cx<T>* __restrict__ z, cx<T>* __restrict__ rdm, T* __restrict__ mag,
-                                               int row0, int rows_total, cx<T>* L) {
+                                               int row0, const K2Rows& rw, cx<T>* L) {
+    const int rows_total = rw.total;
     typedef cx<T> V;
     constexpr int SH = k2_sh_np<T, NOPAD>();
     static_assert(M == R0 * R1 * R0, "palindromic 3-pass plan");
@@ -1749,7 +1765,7 @@ __device__ __forceinline__ void k2_fft_job_mix(const Geometry& g, const DevConst
     const int rl = rows == 1 ? 0 : __builtin_amdgcn_readfirstlane(tid / nb0);
     const int j = tid - rl * nb0;
     if (tid < nb0 * rows) {
-        const ZWin zw = zrow_window(g, z, row0 + rl, rows_total, off, lo, hi);
+        const ZWin zw = zrow_window(g, rw, z, row0 + rl, rows_total, off, lo, hi);
         k2_load_wrow<nb0>(g, zw, a + j - lo + off, v0[0]);
         if constexpr (!EPI) {
             const __amdgpu_buffer_rsrc_t hr = buf_rsrc(H + sd.H_off, (unsigned)(M * sizeof(V)));
@@ -1823,20 +1839,21 @@ __device__ __forceinline__ void k2_fft_job_mix(const Geometry& g, const DevConst
         __syncthreads();   // every read of the pass before any write
         sh_store<R0, true, NB0, SH, K2_THREADS, M, NS2>(v, rs, rows, StoreLds<V>{L}, tid);
         __syncthreads();
-        k2_epilogue<T, SH>(L, rs, rows, row0, rows_total, Lh1, g0, gend, rdm, mag, G, g.Gp);
+        k2_epilogue<T, SH>(L, rs, rows, row0, rw, g.P, Lh1, g0, gend, rdm, mag, G, g.Gp);
     } else if constexpr (EPI) {
         sh_pass<R0, true, NB0, SH, K2_THREADS, M, NS2, CMP>(L, rs, rows, twI + TW2, StoreLds<V>{L});
-        k2_epilogue<T, SH>(L, rs, rows, row0, rows_total, Lh1, g0, gend, rdm, mag, G, g.Gp);
+        k2_epilogue<T, SH>(L, rs, rows, row0, rw, g.P, Lh1, g0, gend, rdm, mag, G, g.Gp);
     } else {
         static_assert(EPI || (rows == 1 && NS2 == nb0), "last pass: thread j's outputs are j + r NS2 of one row");
         V v[NB0][R0];
         sh_load<R0, true, NB0, SH, K2_THREADS, M, NS2, CMP>(L, rs, rows, twI + TW2, v, tid);
+        const int rho = k2_rho(rw, g.P, row0);
         if (rdm)
             sh_store<R0, true, NB0, SH, K2_THREADS, M, NS2>(
-                v, rs, rows, StoreRowK<V, true, NS2, R0>(rdm, mag, G, g.Gp, row0, rows_total, Lh1, g0, gend), tid);
+                v, rs, rows, StoreRowK<V, true, NS2, R0>(rdm, mag, G, g.Gp, rho, row0 < rows_total, Lh1, g0, gend), tid);
         else
             sh_store<R0, true, NB0, SH, K2_THREADS, M, NS2>(
-                v, rs, rows, StoreRowK<V, false, NS2, R0>(rdm, mag, G, g.Gp, row0, rows_total, Lh1, g0, gend), tid);
+                v, rs, rows, StoreRowK<V, false, NS2, R0>(rdm, mag, G, g.Gp, rho, row0 < rows_total, Lh1, g0, gend), tid);
     }
 }
 
@@ -1849,7 +1866,8 @@ __device__ __forceinline__ void k2_fft_job_mix(const Geometry& g, const DevConst
 // the gates from the last pass, which measured faster at that occupancy (x2 at 2 per CU: 225 vs
 // 248 us per 8 frames).
 template <class T, int WGS>
-__global__ __launch_bounds__(K2_THREADS, WGS) void k2_pc(Geometry g, DevConsts k, FramePtrs fp, int rows_total) {
+__global__ __launch_bounds__(K2_THREADS, WGS) void k2_pc(Geometry g, DevConsts k, FramePtrs fp, K2Rows rw,
+                                                         const K2Rec* __restrict__ recs, int on_demand) {
     constexpr bool EPI = WGS >= 3;
     constexpr bool NOPAD = WGS == 4;
     typedef cx<T> V;
@@ -1857,11 +1875,23 @@ __global__ __launch_bounds__(K2_THREADS, WGS) void k2_pc(Geometry g, DevConsts k
     const int f = blockIdx.y;
     // the plan's dispatch order (job kinds interleaved) as one record per workgroup: a single scalar
     // load, where a dispatch-order entry and a search of g.jobs were 3 to 5 dependent ones
-    const K2Rec rec = k.k2rec[blockIdx.x];
+    const K2Rec rec = recs[blockIdx.x];
     const K2Job job{rec.seg, rec.blk, 0, 0};   // the block jobs read seg and blk
     const SegDesc& sd = g.segs[rec.seg];
     const int rows = sd.rows_per_wg;
-    const int row0 = rec.row0;
+    const int row0 = rec.row0;   // of the launch's row set rw
+    const int rows_total = rw.total;
+    if (on_demand) {
+        // the edge set after K3's first phase: row i's flag is byte i of the frame's block (beam-major,
+        // 2 hV per beam, as the set counts its rows).  A workgroup none of whose rows is asked for
+        // returns; one with any computes them all, so a row's values never depend on its neighbours'
+        // flags.  Uniform: scalar loads and a scalar branch.
+        const unsigned char* __restrict__ need = fp.need[f];
+        int any = 0;
+        for (int r = 0; r < rows && row0 + r < rows_total; ++r) any |= need[row0 + r];
+        if (!any) return;
+        if (rec.seg == 0 && rec.blk == 0 && threadIdx.x == 0) atomicAdd(fp.count[f] + 2, min(rows, rows_total - row0));
+    }
     const V* __restrict__ z = static_cast<const V*>(fp.z[f]);
     V* __restrict__ rdm = static_cast<V*>(fp.rdm[f]);
     T* __restrict__ mag = static_cast<T*>(fp.mag[f]);
@@ -1872,25 +1902,25 @@ __global__ __launch_bounds__(K2_THREADS, WGS) void k2_pc(Geometry g, DevConsts k
     K2_TAG((unsigned long long)(sd.type * 16 + sd.logM));
 
     if (sd.type == 1 && sd.logM == 0) {   // mixed-radix block
-        k2_fft_job_mix<T, 2560, 16, 10, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L);
+        k2_fft_job_mix<T, 2560, 16, 10, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rw, L);
     } else if (sd.type == 1) {
         // workgroups sized for the 2560-point block (WGS >= 3) run 2048 points of 2^k rows, up to
         // one 2048-point row; the others RSP_K2_POINTS, up to one 4096-point row
         constexpr int PTS = WGS >= 3 ? 2048 : RSP_K2_POINTS;
         constexpr int LGTOP = WGS >= 3 ? 11 : 12;   // the largest block: the default
         switch (sd.logM) {
-            case 6: k2_fft_job<T, 6, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
-            case 7: k2_fft_job<T, 7, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
-            case 8: k2_fft_job<T, 8, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
-            case 9: k2_fft_job<T, 9, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
-            case 10: k2_fft_job<T, 10, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
+            case 6: k2_fft_job<T, 6, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rw, L); break;
+            case 7: k2_fft_job<T, 7, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rw, L); break;
+            case 8: k2_fft_job<T, 8, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rw, L); break;
+            case 9: k2_fft_job<T, 9, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rw, L); break;
+            case 10: k2_fft_job<T, 10, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rw, L); break;
             case 11:
                 if constexpr (LGTOP > 11) {
-                    k2_fft_job<T, 11, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L);
+                    k2_fft_job<T, 11, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rw, L);
                     break;
                 }
                 [[fallthrough]];
-            default: k2_fft_job<T, LGTOP, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rows_total, L); break;
+            default: k2_fft_job<T, LGTOP, PTS, EPI, NOPAD>(g, k, sd, job, z, rdm, mag, row0, rw, L); break;
         }
     } else {
         // direct FIR (narrow segment): filter() + circshift(-fir_delay) (fsf:111-112).  Each
@@ -1907,8 +1937,8 @@ __global__ __launch_bounds__(K2_THREADS, WGS) void k2_pc(Geometry g, DevConsts k
                 val[u] = V{};
                 if (e < nw) {
                     const int rl = e / WP, i = e - rl * WP - PADL;
-                    const int rho = row0 + rl;
-                    if (rho < rows_total && i >= 0) {
+                    if (row0 + rl < rows_total && i >= 0) {
+                        const int rho = k2_rho(rw, P, row0 + rl);
                         const int b = rho / P, v = rho - b * P;
                         val[u] = z[zaddr(g, b, v, i + off)];
                     }
@@ -1932,8 +1962,8 @@ __global__ __launch_bounds__(K2_THREADS, WGS) void k2_pc(Geometry g, DevConsts k
         const int ngrp = (nout + 3) >> 2;
         for (int e = tid; e < rows * ngrp; e += K2_THREADS) {
             const int rl = e / ngrp, q0 = 4 * (e - rl * ngrp);
-            const int rho = row0 + rl;
-            if (rho >= rows_total) continue;
+            if (row0 + rl >= rows_total) continue;
+            const int rho = k2_rho(rw, P, row0 + rl);
             const int gg0 = sd.ga + q0;
             int kk0 = (gg0 + sd.delay) % sd.Ls;
             if (kk0 < 0) kk0 += sd.Ls;
@@ -2107,17 +2137,93 @@ template <class T> struct U16;   // one 16-B unit of a map row
 template <> struct U16<float> { typedef f32x4 U; static constexpr int E = 4; };
 template <> struct U16<double> { typedef d2 U; static constexpr int E = 2; };
 
+// ---- the CFAR test's arithmetic, shared by k3_cfar and k3_finish ---------------------------
+// mean() = sum / n over the slices of fsf:197-203 (max(a/n, b/n) = max(a, b)/n).  double: the
+// correctly rounded quotient, as MATLAB, without a division: q0 = x * RN(1/n), r = x - q0 n
+// (exact, one FMA), q = RN(q0 + r RN(1/n)) is RN(x/n) (Markstein's theorem: RN(1/n) within half
+// an ulp, q0 within one ulp of x/n; no underflow for these sums).  float: a multiply by 1/n
+// (<= 1 ulp from the quotient).
+template <class T>
+__device__ __forceinline__ T k3_quot(T x, T fn, T in) {
+    if constexpr (sizeof(T) == 8) {
+        const T q0 = x * in;
+        return __builtin_fma(__builtin_fma(-q0, fn, x), in, q0);
+    } else {
+        return x * in;
+    }
+}
+// The noise level of the four slice sums.  ONE (n_R = n_V, the reference's 5/5): max(nR, nV) is one
+// quotient of the largest slice sum.
+template <bool ONE, class T>
+__device__ __forceinline__ T k3_noise2(T lr, T tr, T lv, T tv, T fR, T iR, T fV, T iV) {
+    if (ONE) return k3_quot(fmax(fmax(lr, tr), fmax(lv, tv)), fR, iR);
+    const T nR = k3_quot(fmax(lr, tr), fR, iR), nV = k3_quot(fmax(lv, tv), fV, iV);
+    return nR > nV ? nR : nV;
+}
+// S(v, r) = |A| + |B| (fsf:184-187) from the magnitude maps of beams pair, pair + 1: the same two
+// values and the same add as k3_cfar's tile load
+template <class T>
+struct K3Maps {
+    const T* __restrict__ MA;
+    const T* __restrict__ MB;
+    int Gp;
+    __device__ __forceinline__ T operator()(int vv, int rr) const {
+        const size_t o = (size_t)vv * Gp + rr;
+        return MA[o] + MB[o];
+    }
+};
+// The four slice sums of cell (v, r) of the compile-time window from the maps, in sum() order.
+// has_lv / has_tv false: that Doppler slice is left at 0 (its rows are not in the maps yet).
+template <int RR, int RV, int GR, int GV, class T>
+__device__ __forceinline__ void k3_map_sums(const K3Maps<T>& sg, int v, int r, T& lr, T& tr, T& lv, T& tv,
+                                            bool has_lv = true, bool has_tv = true) {
+    lr = 0; tr = 0; lv = 0; tv = 0;
+    for (int qq = 0; qq < RR; ++qq) lr += sg(v, r - (GR + RR) + qq);
+    for (int qq = 0; qq < RR; ++qq) tr += sg(v, r + GR + 1 + qq);
+    for (int qq = 0; qq < RV; ++qq) {
+        if (has_lv) lv += sg(v + qq - GV - RV, r);
+        if (has_tv) tv += sg(v + qq + GV + 1, r);
+    }
+}
+
+// ---- the band route (K2 of the rows under test, the edge rows on demand) ---------------------
+// A cell whose test or S9 reads a row outside [hV, P - hV): its Doppler slices reach hV rows up and
+// down, S9 two.
+__device__ __forceinline__ bool k3_edge_cell(int v, int P) {
+    return v < 2 * RSP_K3_FAST_HV || v >= P - 2 * RSP_K3_FAST_HV;
+}
+// K3_DEFER: an edge cell that passes the test on the slices it has (below) goes on the frame's deferred list (the count keeps
+// counting past the capacity; the host grows the list and runs the phases again), and the edge rows
+// its slices (v - hV .. v - hV + refV - 1 and the mirror) and S9 (v - 2 .. v + 2) read are flagged
+// for both beams of the pair.
+__device__ __forceinline__ void k3_defer_cell(const FramePtrs& fp, int f, int P, int pair, int v, int r, int cap) {
+    constexpr int hV = RSP_K3_FAST_HV;
+    const int i = atomicAdd(fp.count[f] + 1, 1);
+    if (i < cap) fp.defer[f][i] = int2{(pair << 16) | v, r};
+    unsigned char* need = fp.need[f] + pair * 2 * hV;
+#pragma unroll 1
+    for (int q = 0; q < 15; ++q) {
+        const int vv = q < 5 ? v - hV + q : (q < 10 ? v + hV - 9 + q : v - 12 + q);   // left slice, right slice, S9
+        const int e = vv < hV ? vv : vv - (P - 2 * hV);   // edge row index, when vv is one
+        if (vv >= 0 && vv < P && (vv < hV || vv >= P - hV)) need[e] = need[2 * hV + e] = 1;
+    }
+}
+
 // RR/RV/GR/GV = reference/guard cell counts when known at compile time (the reference's
 // 5/5/10/10, v8:45-46), 0 = runtime; RTC = the tile width g.cfar_RT when they are (32 or 64),
 // so that the LDS row stride and every window offset are compile-time constants.  Tiles: RT
 // range cells x all P Doppler cells of one beam pair, tile starts aligned to 4 cells so that
 // the magnitude rows load as 16-B units.
-template <class T, int RR, int RV, int GR, int GV, int RTC>
-__global__ __launch_bounds__(RSP_THREADS, RSP_K3_WGS) void k3_cfar(Geometry g, DevConsts k, FramePtrs fp) {
+// DEFER (the band route's first phase, FAST only; the maps then hold rows [hV, P - hV) alone): a
+// prefilter survivor at an edge cell (k3_edge_cell) is not tested here but left to k3_finish
+// (k3_defer_cell); every other cell goes through exactly the code of the whole kernel.
+template <class T, int RR, int RV, int GR, int GV, int RTC, bool DEFER = false>
+__global__ __launch_bounds__(RSP_THREADS, RSP_K3_WGS) void k3_cfar(Geometry g, DevConsts k, FramePtrs fp, int defer_cap) {
     T* S = reinterpret_cast<T*>(rsp_lds);   // [P][W] | queue[K3_QCAP] | qn, base
     typedef typename U16<T>::U U;
     constexpr int EPU = U16<T>::E;
     constexpr bool FAST = RR > 0 && RV > 0 && GR > 0 && GV > 0 && (RTC == 32 || RTC == 64);
+    static_assert(!DEFER || (FAST && RV + GV == RSP_K3_FAST_HV && RR == RV), "the band route follows the 5/5/10/10 window");
     // FAST (the compile-time 5/5/10/10 kernel): the tile holds the band's own cells only, no halo;
     // the prefilter takes whichever range slice lies inside the tile, survivors and S9 read the
     // rest from the maps.  The generic kernel's tile holds the halo (g.cfar_W, g.cfar_hR).
@@ -2157,10 +2263,7 @@ __global__ __launch_bounds__(RSP_THREADS, RSP_K3_WGS) void k3_cfar(Geometry g, D
     const cx<T>* __restrict__ RA = g.mono_c ? static_cast<const cx<T>*>(fp.rdm[f]) + (size_t)pair * P * G : nullptr;
     const cx<T>* __restrict__ RB = RA ? RA + (size_t)P * G : nullptr;
     // S(v, r) from the maps: the same two values and the same add as the tile load below
-    auto sg = [&](int vv, int rr) -> T {
-        const size_t o = (size_t)vv * Gp + rr;
-        return MA[o] + MB[o];
-    };
+    const K3Maps<T> sg{MA, MB, Gp};
     if (threadIdx.x == 0) qn[0] = 0;
     // ---- load S = |A| + |B| (fsf:184-187) from the magnitude maps: 16 B per lane,
     //      K3_VEC units of each beam in flight per thread
@@ -2248,27 +2351,11 @@ __global__ __launch_bounds__(RSP_THREADS, RSP_K3_WGS) void k3_cfar(Geometry g, D
     }
     if (v1 <= v0 || cut_hi <= cut_lo) return;
     const double Tc = g.T;
-    // mean() = sum / n over the slices of fsf:197-203 (max(a/n, b/n) = max(a, b)/n).  double: the
-    // correctly rounded quotient, as MATLAB, without a division: q0 = x * RN(1/n), r = x - q0 n
-    // (exact, one FMA), q = RN(q0 + r RN(1/n)) is RN(x/n) (Markstein's theorem: RN(1/n) within half
-    // an ulp, q0 within one ulp of x/n; no underflow for these sums).  float: a multiply by 1/n
-    // (<= 1 ulp from the quotient).  With n_R = n_V (the reference's 5/5) max(nR, nV) is one
-    // quotient of the largest slice sum.
+    // mean() = sum / n over the slices of fsf:197-203: k3_quot, k3_noise2
     const T fR = (T)rR, fV = (T)rV;
     const T iR = (T)1 / fR, iV = (T)1 / fV;
-    auto quot = [&](T x, T fn, T in) -> T {
-        if constexpr (sizeof(T) == 8) {
-            const T q0 = x * in;
-            return __builtin_fma(__builtin_fma(-q0, fn, x), in, q0);
-        } else {
-            return x * in;
-        }
-    };
-    auto noise2 = [&](T lr, T tr, T lv, T tv) -> T {
-        if (FAST && RR == RV) return quot(fmax(fmax(lr, tr), fmax(lv, tv)), fR, iR);
-        const T nR = quot(fmax(lr, tr), fR, iR), nV = quot(fmax(lv, tv), fV, iV);
-        return nR > nV ? nR : nV;
-    };
+    auto quot = [&](T x, T fn, T in) -> T { return k3_quot(x, fn, in); };
+    auto noise2 = [&](T lr, T tr, T lv, T tv) -> T { return k3_noise2<FAST && RR == RV>(lr, tr, lv, tv, fR, iR, fV, iV); };
     const S9Consts s9c{k.range_axis, k.velocity_axis, k.beam_angles, k.klut, k.deltaR, k.deltaV};
     // hits past the LDS queue are only counted here (qn keeps counting); the overflow pass below
     // finds them again
@@ -2349,15 +2436,19 @@ __global__ __launch_bounds__(RSP_THREADS, RSP_K3_WGS) void k3_cfar(Geometry g, D
                     }
                     const int ri = r + i;
                     if (ri >= cut_lo && ri < cut_hi && (!pf || !(cv[i] <= Tt * quot(lr, fR, iR)))) {
-                        T tr = 0, lv = 0, tv = 0;   // every slice from the maps, in sum() order
-                        lr = 0;
-                        for (int qq = 0; qq < RR; ++qq) lr += sg(v, ri + DL + qq);
-                        for (int qq = 0; qq < RR; ++qq) tr += sg(v, ri + DR + qq);
-                        for (int qq = 0; qq < RV; ++qq) {
-                            lv += sg(v + qq - GV - RV, ri);
-                            tv += sg(v + qq + GV + 1, ri);
+                        // DEFER: the Doppler slice below a cell with v < 2 hV, or above one with
+                        // v >= P - 2 hV, lies in rows the maps do not hold yet.  The noise level is
+                        // a monotone function of the largest slice sum (sums of magnitudes, >= 0), so
+                        // a cell that fails the test on the slices it has cannot be a hit (the
+                        // prefilter's argument, T > 0); one that passes waits for k3_finish.
+                        const bool no_lv = DEFER && v < 2 * RSP_K3_FAST_HV, no_tv = DEFER && v >= P - 2 * RSP_K3_FAST_HV;
+                        T tr, lv, tv;   // every slice from the maps, in sum() order
+                        k3_map_sums<RR, RV, GR, GV>(sg, v, ri, lr, tr, lv, tv, !no_lv, !no_tv);
+                        if (no_lv || no_tv) {
+                            if (!pf || !(cv[i] <= Tt * noise2(lr, tr, lv, tv))) k3_defer_cell(fp, f, P, pair, v, ri, defer_cap);
+                        } else {
+                            K3_HIT(v, c + i, cv[i], lr, tr, lv, tv);
                         }
-                        K3_HIT(v, c + i, cv[i], lr, tr, lv, tv);
                     }
                 }
             }
@@ -2438,6 +2529,7 @@ __global__ __launch_bounds__(RSP_THREADS, RSP_K3_WGS) void k3_cfar(Geometry g, D
     for (int e = threadIdx.x; e < ncell; e += RSP_THREADS) {
         if (bm[e >> 5] >> (e & 31) & 1u) continue;
         const int v = v0 + e / ncr, r = cut_lo + (e - (e / ncr) * ncr);
+        if (DEFER && k3_edge_cell(v, P)) continue;   // deferred or ruled out by the loop above
         T lr = 0, tr = 0, lv = 0, tv = 0;
         for (int qq = 0; qq < rR; ++qq) {
             lr += st(v, r - gR - rR + qq);
@@ -2450,6 +2542,33 @@ __global__ __launch_bounds__(RSP_THREADS, RSP_K3_WGS) void k3_cfar(Geometry g, D
         if (st(v, r) > (T)Tc * noise2(lr, tr, lv, tv)) {
             const int idx = atomicAdd(fp.count[f], 1);
             if (idx < g.max_dets) s9_estimate<T>(s9c, st, P, G, Gp, v, r, pair, MA, MB, RA, RB, &fp.dets[f][idx]);
+        }
+    }
+}
+
+// The band route's last phase, after the on-demand K2: the full test of each deferred cell through
+// the same sums in the same order as k3_cfar's survivors, the same noise level and the same S9; hits
+// join the frame's detection list.  Grid (K3_FIN_WGS, frames): a fixed small grid that strides over
+// the list, whose length only the device knows.
+#define K3_FIN_WGS 4
+template <class T, int RR, int RV, int GR, int GV>
+__global__ __launch_bounds__(RSP_THREADS) void k3_finish(Geometry g, DevConsts k, FramePtrs fp, int defer_cap) {
+    const int f = blockIdx.y, P = g.P, G = g.G, Gp = g.Gp;
+    const int n = min(fp.count[f][1], defer_cap);   // past the capacity: counted, the host runs the phases again
+    const T fR = (T)RR, fV = (T)RV, iR = (T)1 / fR, iV = (T)1 / fV;
+    const S9Consts s9c{k.range_axis, k.velocity_axis, k.beam_angles, k.klut, k.deltaR, k.deltaV};
+    for (int i = blockIdx.x * RSP_THREADS + threadIdx.x; i < n; i += K3_FIN_WGS * RSP_THREADS) {
+        const int2 e = fp.defer[f][i];
+        const int pair = e.x >> 16, v = e.x & 0xFFFF, r = e.y;
+        const T* MA = static_cast<const T*>(fp.mag[f]) + (size_t)pair * P * Gp;
+        const K3Maps<T> sg{MA, MA + (size_t)P * Gp, Gp};
+        T lr, tr, lv, tv;
+        k3_map_sums<RR, RV, GR, GV>(sg, v, r, lr, tr, lv, tv);
+        if (sg(v, r) > (T)g.T * k3_noise2<RR == RV>(lr, tr, lv, tv, fR, iR, fV, iV)) {
+            const int idx = atomicAdd(fp.count[f], 1);
+            if (idx < g.max_dets)
+                s9_estimate<T>(s9c, sg, P, G, Gp, v, r, pair, sg.MA, sg.MB, (const cx<T>*)nullptr, (const cx<T>*)nullptr,
+                               &fp.dets[f][idx]);
         }
     }
 }
@@ -2721,18 +2840,18 @@ hipError_t launch_k1(const Geometry& g, const DevConsts& k, const FramePtrs& fp,
 }
 
 template <class T>
-static hipError_t launch_k2_p(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, int rows,
-                              hipStream_t s) {
+static hipError_t launch_k2_p(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, const K2Rows& rows,
+                              const K2Rec* recs, int nwg, bool on_demand, hipStream_t s) {
     // workgroups sized for the 2560-point block (complex double): 4 per CU, the row's LDS alone
     const bool w4 = k2_wg_per_cu(g) == 4;
     const size_t lds = w4 ? (size_t)g.k2_pts * sizeof(cx<T>)
                           : (size_t)(k2_lds_data(g.k2_pts, k2_sh<T>()) + k2_tw_lds_max()) * sizeof(cx<T>);
     const auto kernel = w4 ? k2_pc<T, 4> : k2_pc<T, 2>;
-    if (g.nwg_k2 == 0) {   // nothing to launch; the LDS attribute is set all the same
+    if (nwg == 0) {   // nothing to launch; the LDS attribute is set all the same
         const hipError_t e = allow_lds(kernel, lds);
         return e != hipSuccess ? e : hipGetLastError();
     }
-    return launch(kernel, dim3(g.nwg_k2, nf), dim3(K2_THREADS), lds, s, g, k, fp, rows);
+    return launch(kernel, dim3(nwg, nf), dim3(K2_THREADS), lds, s, g, k, fp, rows, recs, on_demand ? 1 : 0);
 }
 
 // Streaming copy (rsp_hbm_copy_probe): CU16 x 16 B per lane, all loads in flight before the
@@ -2755,23 +2874,35 @@ hipError_t launch_stream_copy(const void* in, void* out, size_t n16, int, hipStr
     return hipGetLastError();
 }
 
-hipError_t launch_k2(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, int rows, hipStream_t s) {
-    return g.prec == RSP_PREC_F64 ? launch_k2_p<double>(g, k, fp, nf, rows, s)
-                                  : launch_k2_p<float>(g, k, fp, nf, rows, s);
+hipError_t launch_k2_set(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, const K2Rows& rows,
+                         const K2Rec* recs, int nwg, bool on_demand, hipStream_t s) {
+    return g.prec == RSP_PREC_F64 ? launch_k2_p<double>(g, k, fp, nf, rows, recs, nwg, on_demand, s)
+                                  : launch_k2_p<float>(g, k, fp, nf, rows, recs, nwg, on_demand, s);
+}
+
+hipError_t launch_k2(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, hipStream_t s) {
+    return launch_k2_set(g, k, fp, nf, k2_row_set(g, K2SET_ALL), k.k2rec, g.nwg_k2, false, s);
 }
 
 template <class T>
-static hipError_t launch_k3_p(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, hipStream_t s) {
+static hipError_t launch_k3_p(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, hipStream_t s, int phase,
+                              int defer_cap) {
     const size_t lds = (size_t)g.cfar_rows * g.cfar_W * sizeof(T) + (K3_QCAP + 4) * sizeof(int);
     const dim3 grid(k3_ntiles(g) * g.cfar_nband * (g.B - 1) * nf);   // 1-D; k3_cfar remaps it XCD-aware
     const bool ref = k3_fast_params(g);   // the reference's cfar_params (v8:45-46); the plan sized the tile for it
-    const auto kernel = ref && g.cfar_RT == 64   ? k3_cfar<T, 5, 5, 10, 10, 64>
+    if (phase != K3_WHOLE && !ref) return hipErrorInvalidValue;   // the band route is the compile-time kernel's
+    if (phase == K3_FINISH)
+        return launch(k3_finish<T, 5, 5, 10, 10>, dim3(K3_FIN_WGS, nf), dim3(RSP_THREADS), 0, s, g, k, fp, defer_cap);
+    const auto kernel = phase == K3_DEFER ? (g.cfar_RT == 64 ? k3_cfar<T, 5, 5, 10, 10, 64, true>
+                                                             : k3_cfar<T, 5, 5, 10, 10, 32, true>)
+                        : ref && g.cfar_RT == 64 ? k3_cfar<T, 5, 5, 10, 10, 64>
                         : ref && g.cfar_RT == 32 ? k3_cfar<T, 5, 5, 10, 10, 32>
                                                  : k3_cfar<T, 0, 0, 0, 0, 0>;
-    return launch(kernel, grid, dim3(RSP_THREADS), lds, s, g, k, fp);
+    return launch(kernel, grid, dim3(RSP_THREADS), lds, s, g, k, fp, defer_cap);
 }
 
-hipError_t launch_k3(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, hipStream_t s) {
+hipError_t launch_k3(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, hipStream_t s, int phase,
+                     int defer_cap) {
     if (g.B < 2) return hipSuccess;
     if (g.G - 2 * (g.refR + g.guardR) <= 0) {   // no range cell under test: no detections, the maps on request
         bool want = false;
@@ -2782,7 +2913,8 @@ hipError_t launch_k3(const Geometry& g, const DevConsts& k, const FramePtrs& fp,
         else hipLaunchKernelGGL(k3_smap<float>, grid, dim3(RSP_THREADS), 0, s, g, fp);
         return hipGetLastError();
     }
-    return g.prec == RSP_PREC_F64 ? launch_k3_p<double>(g, k, fp, nf, s) : launch_k3_p<float>(g, k, fp, nf, s);
+    return g.prec == RSP_PREC_F64 ? launch_k3_p<double>(g, k, fp, nf, s, phase, defer_cap)
+                                  : launch_k3_p<float>(g, k, fp, nf, s, phase, defer_cap);
 }
 
 template <class T, int LGP>

@@ -60,6 +60,12 @@ struct Lane {
     DevDet* h_dets = nullptr;   // mapped pinned F x (1 + hcap), same layout, written by k_dets_to_host
     DevDet* h_dets_dev = nullptr;
     int hcap = 0;               // host read-back capacity per frame (grows on demand)
+    // band route: the frames' edge-row flags (F x RSP_NEED_BYTES) and deferred-cell lists (F x fcap
+    // entries; grow on demand like the detection lists)
+    unsigned char* need = nullptr;
+    int2* defer = nullptr;
+    int fcap = 0;
+    bool band = false;          // the batch in flight took the band route
     FramePtrs fp{};             // the batch in flight (K3 runs again after a device-list growth)
     int nf = 0;
     int frame_ids[RSP_MAX_F];
@@ -149,6 +155,14 @@ struct rsp_plan {
     // d_aux holds a stage-2 result, and device buffers that grow on demand (freed with the plan)
     int32_t gates[3] = {0, 0, 0};
     std::vector<K2Rec> k2rec;     // host copy of DevConsts::k2rec (rsp_query_k2_records)
+    // band route (launch_batch): the three row sets, the band and edge record tables on the device
+    // and on the host, whether the plan may take it at all, and what it did (rsp_band_counters_get)
+    K2Rows k2rows[3] = {};
+    std::vector<K2Rec> k2rec_band, k2rec_edge;
+    const K2Rec* drec_band = nullptr;
+    const K2Rec* drec_edge = nullptr;
+    bool band_ok = false;
+    rsp_band_counters ctr{};
     bool aux_valid = false;
     struct DevBuf {
         void* p = nullptr;
@@ -239,6 +253,7 @@ rsp_plan::~rsp_plan() {
         if (L.stream) (void)hipStreamSynchronize(L.stream);
         if (L.h_dets) (void)hipHostFree(L.h_dets);
         if (L.dets) (void)hipFree(L.dets);
+        if (L.defer) (void)hipFree(L.defer);
         if (L.done) (void)hipEventDestroy(L.done);
         for (auto& e : L.tev)
             if (e) (void)hipEventDestroy(e);
@@ -283,6 +298,18 @@ int lane_host_alloc(rsp_plan* p, Lane& L, int cap) {
     return RSP_OK;
 }
 
+// Deferred-cell lists of a lane, F x cap entries; swapped in only on success, like the detection lists
+int lane_defer_alloc(rsp_plan* p, Lane& L, int cap) {
+    const int ncap = std::max(cap, 1);
+    int2* nd = nullptr;
+    if (hipMalloc((void**)&nd, sizeof(int2) * (size_t)ncap * p->F) != hipSuccess)
+        return fail(RSP_ERR_NOMEM, "hipMalloc of %d-cell deferred lists failed", ncap);
+    if (L.defer) HIPCHK(hipFree(L.defer));
+    L.defer = nd;
+    L.fcap = ncap;
+    return RSP_OK;
+}
+
 int pow2_at_least(int x) {
     int c = 1;
     while (c < x && c < (1 << 30)) c <<= 1;
@@ -299,6 +326,12 @@ int setup_lane(rsp_plan* p, Lane& L) {
     if ((rc = p->dalloc_bytes(&L.rdm, p->rdm_elems * p->esz * (p->g.mono_c ? p->F : 1)))) return rc;
     if ((rc = p->dalloc_bytes(&L.mag, p->mag_elems * p->F * p->rsz))) return rc;
     if ((rc = lane_dets_alloc(p, L, std::min(p->det_bound, 4096)))) return rc;
+    if (p->band_ok) {
+        void* q = nullptr;
+        if ((rc = p->dalloc_bytes(&q, (size_t)RSP_NEED_BYTES * p->F))) return rc;
+        L.need = static_cast<unsigned char*>(q);
+        if ((rc = lane_defer_alloc(p, L, std::min(p->det_bound, 1024)))) return rc;
+    }
     return lane_host_alloc(p, L, std::min(p->det_bound, 1024));
 }
 
@@ -331,11 +364,48 @@ FramePtrs lane_ptrs(const rsp_plan* p, const Lane& L, const void* const* in, int
     return fp;
 }
 
-// K3 of nf frames on the lane's stream, its detection lists at the lane's present capacity
+// The band route's flag blocks and deferred lists of the lane as they are now (null off the route)
+void lane_band_ptrs(const Lane& L, int nf, FramePtrs& fp) {
+    for (int f = 0; f < nf; ++f) {
+        fp.need[f] = L.band ? L.need + (size_t)RSP_NEED_BYTES * f : nullptr;
+        fp.defer[f] = L.band ? L.defer + (size_t)L.fcap * f : nullptr;
+    }
+}
+
+// Whether a batch takes the band route: K2 of the rows under test, K3 with the edge cells deferred,
+// K2 of the flagged edge rows, K3's finish.  Only where nobody reads the other rows: no frame writes
+// its RD map (fp.rdm: the caller's, or the complex-ratio monopulse's) and no CFAR map is asked for.
+bool band_route(const rsp_plan* p, const FramePtrs& fp, int nf) {
+    if (!p->band_ok) return false;
+    for (int f = 0; f < nf; ++f)
+        if (fp.rdm[f] || fp.smap[f]) return false;
+    return true;
+}
+
+// K2 of nf frames on the lane's stream: the rows under test on the band route, else every row
+hipError_t launch_k2_lane(const rsp_plan* p, const Lane& L, const FramePtrs& fp, int nf) {
+    if (!L.band) return launch_k2(p->g, p->k, fp, nf, L.stream);
+    return launch_k2_set(p->g, p->k, fp, nf, p->k2rows[K2SET_BAND], p->drec_band, (int)p->k2rec_band.size(), false, L.stream);
+}
+
+// K3 of nf frames on the lane's stream, its lists at the lane's present capacities; on the band
+// route its two phases with the on-demand K2 of the edge rows between them
 hipError_t launch_k3_lane(const rsp_plan* p, const Lane& L, const FramePtrs& fp, int nf) {
     Geometry g3 = p->g;
     g3.max_dets = L.dcap;
-    return launch_k3(g3, p->k, fp, nf, L.stream);
+    if (!L.band) return launch_k3(g3, p->k, fp, nf, L.stream);
+    hipError_t e = launch_k3(g3, p->k, fp, nf, L.stream, K3_DEFER, L.fcap);
+    if (e == hipSuccess)
+        e = launch_k2_set(p->g, p->k, fp, nf, p->k2rows[K2SET_EDGE], p->drec_edge, (int)p->k2rec_edge.size(), true, L.stream);
+    return e != hipSuccess ? e : launch_k3(g3, p->k, fp, nf, L.stream, K3_FINISH, L.fcap);
+}
+
+// A frame's counters (record 0 of its list) and, on the band route, the flag blocks: what K1 zeroes
+// in the pipeline, for the launches that run K3 without a K1 before it
+hipError_t zero_k3_state(const Lane& L, int nf) {
+    hipError_t e = hipMemset2DAsync(L.dets, sizeof(DevDet) * (L.dcap + 1), 0, 3 * sizeof(int), nf, L.stream);
+    if (e == hipSuccess && L.band) e = hipMemsetAsync(L.need, 0, (size_t)RSP_NEED_BYTES * nf, L.stream);
+    return e;
 }
 
 // Enqueue K1 -> K2 -> K3 for nf frames on lane L, plus the async detection read-back.
@@ -345,6 +415,8 @@ int launch_batch(rsp_plan* p, Lane& L, const void* const* in, const int* ids, in
                  const int* slots = nullptr, void* const* rdm = nullptr) {
     FramePtrs fp = lane_ptrs(p, L, in, nf, rdm);
     fp.smap[0] = smap;
+    L.band = band_route(p, fp, nf);
+    lane_band_ptrs(L, nf, fp);
     if (slots)   // producer-ring frames: K1 after their upload / synthesis
         for (int f = 0; f < nf; ++f)
             if (slots[f] >= 0) HIPCHK(hipStreamWaitEvent(L.stream, p->slot_ready[slots[f]], 0));
@@ -355,7 +427,7 @@ int launch_batch(rsp_plan* p, Lane& L, const void* const* in, const int* ids, in
         for (int f = 0; f < nf; ++f)
             if (slots[f] >= 0) HIPCHK(hipEventRecord(p->slot_free[slots[f]], L.stream));
     if (L.timed) HIPCHK(hipEventRecord(L.tev[1], L.stream));
-    HIPCHK(launch_k2(p->g, p->k, fp, nf, p->g.B * p->g.P, L.stream));
+    HIPCHK(launch_k2_lane(p, L, fp, nf));
     if (L.timed) HIPCHK(hipEventRecord(L.tev[2], L.stream));
     HIPCHK(launch_k3_lane(p, L, fp, nf));
     if (L.timed) HIPCHK(hipEventRecord(L.tev[3], L.stream));
@@ -387,20 +459,48 @@ int harvest(rsp_plan* p, Lane& L, std::vector<std::vector<rsp_detection>>* keep_
         p->stage_launches += 1;
         p->stage_frames += L.nf;
     }
-    int cnt[RSP_MAX_F], maxc = 0, rc;
+    // record 0 of a frame: detections, deferred cells, edge rows computed on demand
+    int cnt[RSP_MAX_F], dfc[RSP_MAX_F], erows[RSP_MAX_F], maxc = 0, rc;
     for (int f = 0; f < L.nf; ++f) {
-        cnt[f] = *reinterpret_cast<const int*>(L.h_dets + (size_t)f * (L.hcap + 1));
-        maxc = std::max(maxc, cnt[f]);
+        const int* h = reinterpret_cast<const int*>(L.h_dets + (size_t)f * (L.hcap + 1));
+        cnt[f] = h[0]; dfc[f] = h[1]; erows[f] = h[2];
     }
-    const bool regrow = maxc > L.dcap;
-    if (regrow) {   // rare: grow the device lists, run K3 again with them, read back directly
-        if ((rc = lane_dets_alloc(p, L, std::min(p->det_bound, pow2_at_least(maxc))))) return rc;
+    bool regrow = false;
+    for (;;) {
+        // rare: grow the device lists, run K3 again with them, read back directly.  A deferred list
+        // that was too short leaves the detection count short too, so the counts are read again and
+        // the detection lists may grow in a second round.
+        int maxf = 0;
+        maxc = 0;
+        for (int f = 0; f < L.nf; ++f) {
+            maxc = std::max(maxc, cnt[f]);
+            maxf = std::max(maxf, dfc[f]);
+        }
+        const bool more_d = maxc > L.dcap, more_f = L.band && maxf > L.fcap;
+        if (!more_d && !more_f) break;
+        regrow = true;
+        if (more_d && (rc = lane_dets_alloc(p, L, std::min(p->det_bound, pow2_at_least(maxc))))) return rc;
+        if (more_f && (rc = lane_defer_alloc(p, L, std::min(p->det_bound, pow2_at_least(maxf))))) return rc;
         FramePtrs fp = L.fp;
         lane_det_ptrs(L, L.nf, fp);
-        HIPCHK(hipMemset2DAsync(L.dets, sizeof(DevDet) * (L.dcap + 1), 0, sizeof(int), L.nf, L.stream));
+        lane_band_ptrs(L, L.nf, fp);
+        HIPCHK(zero_k3_state(L, L.nf));
         HIPCHK(launch_k3_lane(p, L, fp, L.nf));
         HIPCHK(hipStreamSynchronize(L.stream));
         L.fp = fp;
+        for (int f = 0; f < L.nf; ++f) {
+            int h[3];
+            HIPCHK(hipMemcpy(h, L.dets + (size_t)(L.dcap + 1) * f, sizeof h, hipMemcpyDeviceToHost));
+            cnt[f] = h[0]; dfc[f] = h[1]; erows[f] = h[2];
+        }
+    }
+    p->ctr.frames += L.nf;
+    if (L.band) {
+        p->ctr.band_frames += L.nf;
+        for (int f = 0; f < L.nf; ++f) {
+            p->ctr.edge_rows += erows[f];
+            p->ctr.deferred_cells += dfc[f];
+        }
     }
     if (keep_dets) keep_dets->assign(L.nf, {});
     for (int f = 0; f < L.nf; ++f) {
@@ -587,7 +687,7 @@ int stage2_device(rsp_plan* p, const void* iq, int dtype) {
     void* rdm[1] = {L.rdm};
     const FramePtrs fp = lane_ptrs(p, L, in, 1, rdm);
     HIPCHK(launch_k1(gs, p->k, fp, 1, 0, L.stream));
-    HIPCHK(launch_k2(gs, p->k, fp, 1, gs.B * gs.P, L.stream));      // PC rows (b, m) -> L.rdm
+    HIPCHK(launch_k2(gs, p->k, fp, 1, L.stream));                  // PC rows (b, m) -> L.rdm
     HIPCHK(launch_mtd_cols(gs, p->k, L.rdm, p->d_aux, L.stream));  // S7 over pulses
     HIPCHK(hipStreamSynchronize(L.stream));
     p->aux_valid = true;
@@ -791,6 +891,17 @@ int32_t rsp_plan_create_ex(const rsp_sig_config* cfg, const rsp_cfar_params* cfa
     k.range_axis = dra; k.velocity_axis = dva; k.beam_angles = dang; k.klut = dkl;
     k.k2rec = drec;
     p->k2rec = std::move(h.k2rec);
+    for (int w = 0; w < 3; ++w) p->k2rows[w] = h.k2rows[w];
+    p->band_ok = !(opt->flags & RSP_PLAN_K2_ALL_ROWS) && h.k2rows[K2SET_BAND].n > 0 && !h.g.mono_c && h.g.B >= 2 &&
+                 h.g.B <= RSP_NEED_BMAX;
+    if (h.k2rows[K2SET_BAND].n > 0) {
+        K2Rec *db, *de;
+        if ((rc = p->upload(&db, h.k2rec_band)) || (rc = p->upload(&de, h.k2rec_edge))) return bail(rc);
+        p->drec_band = db;
+        p->drec_edge = de;
+        p->k2rec_band = std::move(h.k2rec_band);
+        p->k2rec_edge = std::move(h.k2rec_edge);
+    }
     k.deltaR = pre->deltaR; k.deltaV = pre->deltaV;
     const Geometry& g = p->g;
     if (pre->tx_pulse) {
@@ -853,6 +964,25 @@ int32_t rsp_query_k2_layout(const rsp_plan* p, rsp_k2_layout* out) {
 int32_t rsp_query_k2_records(const rsp_plan* p, rsp_k2_record* out, int32_t cap, int32_t* n) {
     if (!p) return fail(RSP_ERR_INVALID, "null argument");
     return rsp_fill_k2_records(p->k2rec, out, cap, n);
+}
+
+int32_t rsp_query_k2_row_set(const rsp_plan* p, int32_t which, rsp_k2_row_set* set, rsp_k2_record* out, int32_t cap,
+                             int32_t* n) {
+    if (!p) return fail(RSP_ERR_INVALID, "null argument");
+    const std::vector<K2Rec>* const rec[3] = {&p->k2rec, &p->k2rec_band, &p->k2rec_edge};
+    return rsp_fill_k2_row_set(p->k2rows, rec, which, set, out, cap, n);
+}
+
+int32_t rsp_band_counters_get(const rsp_plan* p, rsp_band_counters* out) {
+    if (!p || !out) return fail(RSP_ERR_INVALID, "null argument");
+    *out = p->ctr;
+    return RSP_OK;
+}
+
+int32_t rsp_band_counters_reset(rsp_plan* p) {
+    if (!p) return fail(RSP_ERR_INVALID, "null argument");
+    p->ctr = rsp_band_counters{};
+    return RSP_OK;
 }
 
 int32_t rsp_process_cube(rsp_plan* p, const void* cube, int32_t dtype, int32_t layout, int32_t frame_idx,
@@ -1312,6 +1442,10 @@ int32_t rsp_profile_stages_rdm(rsp_plan* p, const void* const* d_cubes, int32_t 
         const void* in[RSP_MAX_F];
         for (int f = 0; f < nf; ++f) in[f] = d_cubes[(j * nf + f) % n_cubes];
         fps[j] = lane_ptrs(p, L, in, nf, d_rdms);   // as the queue: complex RDM stores only into d_rdms
+        // ... and the launches the queue makes: stage 1 the band launch, stage 2 K3's phases with the
+        // on-demand K2 between them, where the queue takes the band route
+        L.band = band_route(p, fps[j], nf);
+        lane_band_ptrs(L, nf, fps[j]);
     }
     const Geometry& g = p->g;
     for (int s = 0; s < 3 && s < cap; ++s) {
@@ -1319,9 +1453,9 @@ int32_t rsp_profile_stages_rdm(rsp_plan* p, const void* const* d_cubes, int32_t 
         auto run = [&]() -> hipError_t {
             const FramePtrs& fj = fps[it++ % nsets];
             if (s == 0) return launch_k1(g, p->k, fj, nf, 3, L.stream);
-            if (s == 1) return launch_k2(g, p->k, fj, nf, g.B * g.P, L.stream);
-            // counts are zeroed by K1 in the pipeline; here by a tiny 2-D memset per launch
-            hipError_t e = hipMemset2DAsync(L.dets, sizeof(DevDet) * (L.dcap + 1), 0, sizeof(int), nf, L.stream);
+            if (s == 1) return launch_k2_lane(p, L, fj, nf);
+            // counts and flags are zeroed by K1 in the pipeline; here by tiny memsets per launch
+            hipError_t e = zero_k3_state(L, nf);
             return e != hipSuccess ? e : launch_k3_lane(p, L, fj, nf);
         };
         float ms = 0;
@@ -1329,7 +1463,7 @@ int32_t rsp_profile_stages_rdm(rsp_plan* p, const void* const* d_cubes, int32_t 
         if (ms_out) ms_out[s] = ms;
     }
     if (frames_out) *frames_out = nf;
-    if (bytes_out) rsp_stage_bytes(g, (int)p->esz, nf, d_rdms || g.mono_c, cap, bytes_out);
+    if (bytes_out) rsp_stage_bytes(g, (int)p->esz, nf, d_rdms || g.mono_c, cap, bytes_out, L.band ? p->k2rows[K2SET_BAND].n : -1);
     return RSP_OK;
 }
 

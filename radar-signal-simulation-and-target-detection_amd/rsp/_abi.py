@@ -100,6 +100,14 @@ class K2Record(ct.Structure):
     _fields_ = [(n, ct.c_int32) for n in ('seg', 'blk', 'row0', 'wg')]
 
 
+class K2RowSet(ct.Structure):
+    _fields_ = [(n, ct.c_int32) for n in ('n', 'base', 'split', 'gap', 'total', 'nwg')]
+
+
+class BandCounters(ct.Structure):
+    _fields_ = [(n, ct.c_int64) for n in ('frames', 'band_frames', 'edge_rows', 'deferred_cells')]
+
+
 class Stage3CfarParams(ct.Structure):
     _fields_ = [('refCells_R', ct.c_int32), ('saveCells_R', ct.c_int32), ('CFARmethod_R', ct.c_int32),
                 ('MTD_0v_num', ct.c_int32), ('T_CFAR', ct.c_double)]
@@ -128,6 +136,7 @@ class VcfarInfo(ct.Structure):
 
 RSP_PLAN_K1_TILED = 1
 RSP_PLAN_MONOPULSE_COMPLEX = 2
+RSP_PLAN_K2_ALL_ROWS = 4
 
 
 class PlanOptions(ct.Structure):
@@ -227,6 +236,14 @@ PROTOTYPES = {
                                                   ct.POINTER(ClusterParams), ct.POINTER(Precomputed),
                                                   ct.POINTER(PlanOptions), ct.c_int32, ct.POINTER(K2Record), ct.c_int32,
                                                   ct.POINTER(ct.c_int32)]),
+    'rsp_query_k2_row_set': (ct.c_int32, [_P, ct.c_int32, ct.POINTER(K2RowSet), ct.POINTER(K2Record), ct.c_int32,
+                                          ct.POINTER(ct.c_int32)]),
+    'rsp_plan_describe_k2_row_set': (ct.c_int32, [ct.POINTER(SigConfig), ct.POINTER(CfarParams),
+                                                  ct.POINTER(ClusterParams), ct.POINTER(Precomputed),
+                                                  ct.POINTER(PlanOptions), ct.c_int32, ct.c_int32, ct.POINTER(K2RowSet),
+                                                  ct.POINTER(K2Record), ct.c_int32, ct.POINTER(ct.c_int32)]),
+    'rsp_band_counters_get': (ct.c_int32, [_P, ct.POINTER(BandCounters)]),
+    'rsp_band_counters_reset': (ct.c_int32, [_P]),
     'rsp_process_cube': (ct.c_int32, [_P, _P, ct.c_int32, ct.c_int32, ct.c_int32, ct.POINTER(FrameOut)]),
     'rsp_process_targets': (ct.c_int32, [_P, ct.POINTER(TargetIn), ct.c_int32, ct.c_int32, ct.c_uint64,
                                          ct.c_double, ct.POINTER(FrameOut)]),

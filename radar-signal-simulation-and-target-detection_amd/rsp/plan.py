@@ -91,7 +91,7 @@ def _marshal(config, cfar_params, cluster_params, pre, keep):
     return cfg, cfar, cluster, pre_c
 
 
-def _options(device, frames_per_launch, precision, k1_tiled, monopulse):
+def _options(device, frames_per_launch, precision, k1_tiled, monopulse, k2_all_rows=False):
     if precision not in ('c128', 'c64'):
         raise ValueError("precision must be 'c128' or 'c64'")
     opt = _abi.PlanOptions()
@@ -102,7 +102,8 @@ def _options(device, frames_per_launch, precision, k1_tiled, monopulse):
         raise ValueError("monopulse must be 'amplitude' (fsf:282-290) or 'complex' "
                          "(main_plot_snr_vs_angle_error.m:455-462), got %r" % (monopulse,))
     opt.flags = (_abi.RSP_PLAN_K1_TILED if k1_tiled else 0) | \
-        (_abi.RSP_PLAN_MONOPULSE_COMPLEX if monopulse == 'complex' else 0)
+        (_abi.RSP_PLAN_MONOPULSE_COMPLEX if monopulse == 'complex' else 0) | \
+        (_abi.RSP_PLAN_K2_ALL_ROWS if k2_all_rows else 0)
     return opt
 
 
@@ -184,6 +185,34 @@ def describe_k2_records(config, cfar_params, cluster_params, precomputed_data, p
         ct.byref(cfg), ct.byref(cfar), ct.byref(cluster), ct.byref(pre), ct.byref(opt), int(ncu), out, cap, n))
 
 
+K2_ROW_SETS = {'all': 0, 'band': 1, 'edge': 2}   # RSP_K2_ROWS_*
+
+
+def _k2_row_set(call):
+    rs = _abi.K2RowSet()
+    rec = _k2_records(lambda out, cap, n: call(ct.byref(rs), out, cap, n))
+    return {k: getattr(rs, k) for k, _ in _abi.K2RowSet._fields_}, rec
+
+
+def k2_set_rows(rs, P):
+    """(beam, Doppler row), 0-based, of every row of the row-set dict ``rs``: an int array [total, 2]."""
+    i = np.arange(rs['total'])
+    j = i % max(rs['n'], 1)
+    return np.stack([i // max(rs['n'], 1), rs['base'] + j + np.where(j >= rs['split'], rs['gap'], 0)], axis=1)
+
+
+def describe_k2_row_set(config, cfar_params, cluster_params, precomputed_data, which, precision='c128',
+                        k1_tiled=False, ncu=256):
+    """``Plan.k2_row_set(which)`` of the plan these arguments would give, without a device
+    (rsp_plan_describe_k2_row_set); refusals as ``describe``."""
+    keep = []
+    cfg, cfar, cluster, pre = _marshal(config, cfar_params, cluster_params, precomputed_data, keep)
+    opt = _options(0, 1, precision, k1_tiled, 'amplitude')
+    return _k2_row_set(lambda rs, out, cap, n: lib().rsp_plan_describe_k2_row_set(
+        ct.byref(cfg), ct.byref(cfar), ct.byref(cluster), ct.byref(pre), ct.byref(opt), int(ncu),
+        K2_ROW_SETS[which], rs, out, cap, n))
+
+
 HIT_DTYPE = np.dtype([('v_idx', np.int32), ('r_idx', np.int32), ('beam_idx', np.int32), ('reserved', np.int32),
                       ('amp', np.float64), ('threshold', np.float64)])   # rsp_stage3_hit
 STAGE3_WANT = ('mtd', 'amp', 'flags', 'threshold', 'hits')
@@ -250,15 +279,17 @@ class Plan:
     ``monopulse``: 'amplitude' (fsf:282-290, the default) or 'complex' -- S9's angle from
     real((S_A - S_B) / (S_A + S_B + eps)) of the complex map, the estimator of the inline S9 in
     main_plot_snr_vs_angle_error.m:455-462 (RSP_PLAN_MONOPULSE_COMPLEX).
+    ``k2_all_rows``: pulse-compress every Doppler row of every frame (RSP_PLAN_K2_ALL_ROWS) instead
+    of the rows under test plus the edge rows a detection reads; same results, for tests and timing.
     """
 
     def __init__(self, config, cfar_params, cluster_params, precomputed_data, device=0, frames_per_launch=1,
-                 precision='c128', k1_tiled=False, monopulse='amplitude'):
+                 precision='c128', k1_tiled=False, monopulse='amplitude', k2_all_rows=False):
         self.config = config
         self._keep = []
         self.cfg, self.cfar, self.cluster, self.pre = _marshal(config, cfar_params, cluster_params, precomputed_data,
                                                                self._keep)
-        opt = _options(device, frames_per_launch, precision, k1_tiled, monopulse)
+        opt = _options(device, frames_per_launch, precision, k1_tiled, monopulse, k2_all_rows)
         h = ct.c_void_p()
         check(lib().rsp_plan_create_ex(ct.byref(self.cfg), ct.byref(self.cfar), ct.byref(self.cluster),
                                        ct.byref(self.pre), ct.byref(opt), ct.byref(h)))
@@ -316,6 +347,22 @@ class Plan:
         """The pulse-compression workgroups in dispatch order (rsp_query_k2_records): an int32 array
         [nwg, 4] of ``K2_RECORD_FIELDS``, row i what workgroup i of a k2_pc launch reads."""
         return _k2_records(lambda out, cap, n: lib().rsp_query_k2_records(self.h, out, cap, n))
+
+    def k2_row_set(self, which):
+        """Row set ``which`` ('all', 'band', 'edge') of the pulse-compression launches and its record
+        table (rsp_query_k2_row_set): ``(rows, records)``, rows a dict of ``n, base, split, gap, total,
+        nwg`` (all 0 for 'band' / 'edge' in a plan without the band route), records as ``k2_records``."""
+        return _k2_row_set(lambda rs, out, cap, n: lib().rsp_query_k2_row_set(self.h, K2_ROW_SETS[which], rs, out,
+                                                                              cap, n))
+
+    def band_counters(self, reset=False):
+        """What the band route did since the last reset (rsp_band_counters_get): ``frames``,
+        ``band_frames``, ``edge_rows`` computed on demand, ``deferred_cells``."""
+        c = _abi.BandCounters()
+        check(lib().rsp_band_counters_get(self.h, ct.byref(c)))
+        if reset:
+            check(lib().rsp_band_counters_reset(self.h))
+        return {k: getattr(c, k) for k, _ in _abi.BandCounters._fields_}
 
     # ---- synchronous frame paths ---------------------------------------------------------
     def _frame_out(self, want_rdm, want_cfar):
