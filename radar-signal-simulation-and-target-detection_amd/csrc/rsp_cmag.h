@@ -1,5 +1,5 @@
 // rsp_cmag.h -- |x| of a complex value, the one magnitude routine of the device code: k2_pc's
-// magnitude maps (rsp_kernels.hip) and the stage-3 CFAR's amplitudes (rsp_stage3.hip).
+// magnitude maps (rsp_k2.hip) and the stage-3 CFAR's amplitudes (rsp_stage3.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

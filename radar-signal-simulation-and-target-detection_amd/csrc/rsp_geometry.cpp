@@ -111,7 +111,7 @@ void push_pass_twiddles(std::vector<cd>& out, int Ns, int R, bool cmp) {
 // Per-pass Stockham twiddle tables of a radix plan, concatenated as plan_tw_off() lays them out:
 // pass q >= 1 owns Ns_q x (R_q - 1) entries T[k][r-1] = exp(-2 pi i k r / (Ns_q R_q)).  Compact
 // tables (cmp): r = 1, 2, 4, 8 only, stored column-major, [i][k] = T[k][2^i] (load_tw in
-// rsp_kernels.hip).  The angle's numerator is reduced modulo the period first, so every entry is
+// rsp_fft_passes.h).  The angle's numerator is reduced modulo the period first, so every entry is
 // the correctly rounded double of the exact root of unity's angle.
 void build_plan_twiddles(const RadixPlan& p, std::vector<cd>& out, bool cmp) {
     for (int q = 1; q < p.np; ++q) push_pass_twiddles(out, plan_ns(p, q), p.rad[q], cmp);
@@ -319,7 +319,7 @@ int derive_k1_tile(Geometry& g, const std::vector<Interval>& U) {
             g.twq_elems = twq;
         }
     }
-    // pow2: + one pad per 16 (K1_SH), see rsp_kernels.hip; factored DFT: the row stride in
+    // pow2: + one pad per 16 (K1_SH), see rsp_k1.hip; factored DFT: the row stride in
     // P..P+15 whose pass-2 reads are conflict-free (rq_pick_stride)
     g.Ppad = g.pow2P ? P + P / 16 : (g.rqQ ? rq_pick_stride(g.rqR, g.rqQ, B) : P + 4);
     const int max_pts = f64 ? 4096 : 8192;

@@ -174,7 +174,7 @@ struct SynthTargets {         // by value in the kernel arguments (2 KiB): no up
 inline int rq_table_elems(int twq_elems, int P) { return twq_elems + (P > 2 * RQ_RK ? P : 2 * RQ_RK); }
 
 // LDS pad shift of a pulse-compression workgroup's rows (one pad per 32 points; k2_sh in
-// rsp_kernels.hip says why) and the complex LDS slots of pts points with their pads.
+// rsp_k2.hip says why) and the complex LDS slots of pts points with their pads.
 constexpr int RSP_K2_SH = 5;
 RSP_HD constexpr int k2_lds_data(int pts, int sh) { return pts + (pts >> sh); }
 
@@ -230,7 +230,7 @@ RSP_HD constexpr int plan_ns(RadixPlan p, int q) {
 }
 RSP_HD constexpr int plan_len(RadixPlan p) { return plan_ns(p, p.np); }
 // Twiddle entries per butterfly index k of a radix-R pass: full rows W^(k r), r = 1 .. R - 1, or
-// (cmp) compact tables W^(k 2^i), 2^i < R (load_tw in rsp_kernels.hip)
+// (cmp) compact tables W^(k 2^i), 2^i < R (load_tw in rsp_fft_passes.h)
 RSP_HD constexpr int tw_row(int R, bool cmp) { return cmp ? clog2(R - 1) + 1 : R - 1; }
 // Offset of pass q's table inside the plan's concatenated per-pass tables: pass i >= 1 owns Ns_i rows
 // of tw_row(R_i) entries (pass 0: Ns = 1, no twiddles); q = np: the tables' total

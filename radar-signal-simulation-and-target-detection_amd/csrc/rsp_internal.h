@@ -75,7 +75,9 @@ struct DevConsts {
     double deltaR, deltaV;
 };
 
-// Launchers (rsp_kernels.hip).  `mode` bits for K1: 1 = apply DBF, 2 = apply MTD.
+// Launchers of the frame chain, each in its stage's unit: launch_k1 (rsp_k1.hip), launch_k2* (rsp_k2.hip),
+// launch_k3 (rsp_k3.hip), launch_stream_copy / launch_mtd_cols / launch_synth / launch_dets_to_host
+// (rsp_frame_aux.hip).  `mode` bits for K1: 1 = apply DBF, 2 = apply MTD.
 hipError_t launch_k1(const Geometry& g, const DevConsts& k, const FramePtrs& fp, int nf, int mode, hipStream_t s);
 hipError_t launch_stream_copy(const void* in, void* out, size_t n16, int ncu, hipStream_t s);
 // K2 of every row (the plan's table k.k2rec), or of one row set with its record table; on_demand:

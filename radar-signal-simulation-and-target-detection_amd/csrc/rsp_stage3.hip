@@ -26,7 +26,7 @@
 // Every operation is a single IEEE operation of T (no fused multiply-add can form: no product feeds
 // an add), `/` is the correctly rounded division (the Makefile passes no fast-math flag, and hipcc's
 // default for float is the correctly rounded one).
-#include "rsp_internal.h"
+#include "rsp_device.h"
 #include "rsp_cmag.h"
 #include <type_traits>
 
@@ -37,11 +37,6 @@ constexpr int WAVES = RSP_THREADS / 64, PASSES = ROWS / WAVES;   // a wave takes
 constexpr int QCAP = 512;                                        // hit records of the LDS queue
 static_assert(ROWS % WAVES == 0 && CH == 4 * 64 && ROWS <= 256, "one wave per Doppler row, 4 cells per lane");
 static_assert(sizeof(rsp_stage3_hit) == 32, "hit record layout");
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-template <class T> struct Cx;
-template <> struct Cx<float> { typedef f2 V; };
-template <> struct Cx<double> { typedef d2 V; };
 
 template <class T, bool CPLX>
 __global__ __launch_bounds__(RSP_THREADS) void k_s3_cfar(S3Desc d, const void* __restrict__ in, double* __restrict__ amp,
@@ -67,7 +62,7 @@ __global__ __launch_bounds__(RSP_THREADS) void k_s3_cfar(S3Desc d, const void* _
         const size_t rowoff = ((size_t)map * d.P + (live ? v : 0)) * G;
         if (live && (!notch || amp)) {
             // hi - lo <= W = NL * 64 columns: every load of the lane is issued before the first is used
-            typedef typename std::conditional<CPLX, typename Cx<T>::V, T>::type E;
+            typedef typename std::conditional<CPLX, cx<T>, T>::type E;
             constexpr int NL = W / 64;
             const E* __restrict__ src = static_cast<const E*>(in) + rowoff;
             E x[NL];

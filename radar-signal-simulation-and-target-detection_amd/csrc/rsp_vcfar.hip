@@ -18,7 +18,7 @@
 //      per wave and row on the global counter.  Hits are counted past hits_cap.
 // Every operation is a single IEEE operation of T (no product feeds an add, so no fused multiply-add
 // can form), `/` is the correctly rounded division (rsp_stage3.hip says why).
-#include "rsp_internal.h"
+#include "rsp_device.h"
 #include "rsp_cmag.h"
 #include <type_traits>
 
@@ -30,10 +30,6 @@ constexpr int QCAP = 512;   // hit records of the LDS queue
 constexpr int NLD = 4;      // rows of loads a wave has in flight while staging
 static_assert(COLS == 64 && ROWS % WAVES == 0 && ROWS <= 256, "a lane per column, a wave per row and step");
 static_assert(sizeof(rsp_stage3_hit) == 32, "hit record layout");
-
-template <class T> struct Cx;
-template <> struct Cx<float> { typedef f2 V; };
-template <> struct Cx<double> { typedef d2 V; };
 
 extern __shared__ __align__(16) unsigned char vc_tile[];
 
@@ -56,7 +52,7 @@ __global__ __launch_bounds__(RSP_THREADS) void k_vcfar(VcDesc d, const void* __r
     const T Tc = (T)d.T;
     if (threadIdx.x == 0) qn[0] = 0;
     {
-        typedef typename std::conditional<CPLX, typename Cx<T>::V, T>::type E;
+        typedef typename std::conditional<CPLX, cx<T>, T>::type E;
         const E* __restrict__ src = static_cast<const E*>(in) + mapoff + c;
         for (int t0 = tb + wave; t0 < te; t0 += NLD * WAVES) {
             E x[NLD];
@@ -163,14 +159,10 @@ hipError_t launch_t(const VcDesc& d, const void* in, int n_maps, double* amp, do
     const size_t lds = vc_lds_bytes(d.halo, sizeof(T));
     constexpr size_t queue = QCAP * (2 * sizeof(T) + sizeof(int)) + 2 * sizeof(int);   // the static LDS
     if (lds + queue > RSP_LDS_BYTES) return hipErrorInvalidValue;
-    if (lds + queue > 64 * 1024) {   // LDS above 64 KiB must be opted in per kernel
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_vcfar<T, CPLX>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    // launch() opts the tile in where it exceeds 64 KiB; at halo <= HMAX tile and queue stay below (48 + 10 KiB)
+    static_assert(vc_lds_bytes(HMAX, sizeof(double)) + QCAP * 20 + 8 <= 64 * 1024, "no opt-in inside the envelope");
     const dim3 grid((d.G + COLS - 1) / COLS, (d.P + ROWS - 1) / ROWS, n_maps);
-    hipLaunchKernelGGL((k_vcfar<T, CPLX>), grid, dim3(RSP_THREADS), lds, s, d, in, amp, thr, flags, hits, count, hits_cap);
-    return hipGetLastError();
+    return launch(k_vcfar<T, CPLX>, grid, dim3(RSP_THREADS), lds, s, d, in, amp, thr, flags, hits, count, hits_cap);
 }
 
 }  // namespace

@@ -132,6 +132,17 @@ def test_pmc_traffic_staleness(tmp_path):
     assert bench.pmc_traffic(str(tmp_path / 'missing.json'), ['k2_pc']) == (None, None, None)
 
 
+def test_kernel_hashes_refuse_a_kernel_defined_twice():
+    """tools/kernel_hashes.py merges the kernels of the library's code objects (one per device
+    translation unit); a mangled name that two of them define is an error, not a silent overwrite."""
+    sys.path.insert(0, os.path.join(ROOT, 'tools'))
+    import kernel_hashes
+    a = {'_Z5k2_pcv': b'\x01', '_Z7k3_cfarv': b'\x02'}
+    assert kernel_hashes.merge(dict(a), {'_Z7k_synthv': b'\x03'}) == dict(a, _Z7k_synthv=b'\x03')
+    with pytest.raises(SystemExit, match='_Z5k2_pcv'):
+        kernel_hashes.merge(dict(a), {'_Z5k2_pcv': b'\x01', '_Z7k_synthv': b'\x03'})
+
+
 def test_music_traffic_scales_with_the_launch(tmp_path):
     """config #5's roofline traffic is the PMC file's bytes per launch scaled from the instances
     that launch held (_instances_per_launch, 1024 when absent) to the bench's --batch."""

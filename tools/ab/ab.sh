@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B timing on one GPU box: per-stage HIP-event times of the shipped library and each variant
-# (exp/ab/librsp_<name>.so, built by `make -C csrc ab NAME=<name> DEFS=...`), interleaved 3 rounds.
+# (exp/ab/librsp_<name>.so, built by `make -C csrc ab NAME=<name> UNIT=<unit> DEFS=...`), interleaved 3 rounds.
 # usage: tools/ab.sh CONFIG PREC name...
 set -o pipefail
 cfg=$1; prec=$2; shift 2

@@ -1,16 +1,26 @@
 #!/bin/bash
-# Build exp/ab/librsp_<name>.so from the kernels/plan sources of git revision REV (default HEAD),
-# against the current headers and host objects: the "before" side of an A/B (tools/ab.sh).
+# Build exp/ab/librsp_<name>.so from the frame-chain units (K1, K2, K3, the auxiliary kernels, their two
+# shared headers) and plan source of git revision REV (default HEAD), against the current other
+# headers and the other objects of the shipped build: the "before" side of an A/B (tools/ab.sh).
+# REV must be a revision that has the per-stage units.
 # usage: tools/ab/build_head_variant.sh NAME [REV]
 set -e
 name=$1; rev=${2:-HEAD}
 C=radar-signal-simulation-and-target-detection_amd/csrc
 d=/tmp/rsp_variant_$name
+units="rsp_k1.hip rsp_k2.hip rsp_k3.hip rsp_frame_aux.hip rsp_plan.cpp"
 rm -rf $d && mkdir -p $d exp/ab
-for f in rsp_kernels.hip rsp_plan.cpp rsp_internal.h; do git show $rev:$C/$f > $d/$f; done
-F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Iinclude -I$d -Wall -Wno-unused-function"
-/opt/rocm/bin/hipcc $F -x hip -c $d/rsp_kernels.hip -o $d/k.o &
-/opt/rocm/bin/hipcc $F -x hip -c $d/rsp_plan.cpp -o $d/p.o &
+for f in $units rsp_internal.h rsp_device.h rsp_fft_passes.h; do git show $rev:$C/$f > $d/$f; done
+F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Iinclude -I$d -I$C -Wall -Wno-unused-function"
+objs=""
+for u in $units; do
+  /opt/rocm/bin/hipcc $F -x hip -c $d/$u -o $d/$u.o &
+  objs="$objs $d/$u.o"
+done
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o exp/ab/librsp_$name.so $d/k.o $d/p.o $C/build/rsp_music.hip.o $C/build/rsp_mat.cpp.o $C/build/rsp_host.cpp.o -lz -lpthread
+rest=""
+for o in $C/build/*.o; do
+  case " $units " in *" $(basename $o .o) "*) ;; *) rest="$rest $o" ;; esac
+done
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o exp/ab/librsp_$name.so $objs $rest -lz -lpthread
 echo built exp/ab/librsp_$name.so from $rev

@@ -1,7 +1,7 @@
 // Instruction census of one K2 job type (compiled with -S only, never linked): the product's
-// rsp_kernels.hip plus two kernels that run a single overlap-save block type on the queue's
-// path (no complex RD map), so that tools/ab/census.sh can count its instructions and registers.
-#include "../../radar-signal-simulation-and-target-detection_amd/csrc/rsp_kernels.hip"
+// K2 unit (rsp_k2.hip, nothing of K1 or K3) plus two kernels that run a single overlap-save block type
+// on the queue's path (no complex RD map), so that tools/ab/census.sh can count its instructions and registers.
+#include "../../radar-signal-simulation-and-target-detection_amd/csrc/rsp_k2.hip"
 
 namespace {
 template <int KIND>   // 1: the 2560-point mixed-radix block, 2: a 1024-point block

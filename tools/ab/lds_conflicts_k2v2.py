@@ -1,7 +1,7 @@
 """Bank-conflict model of the CURRENT K2 overlap-save passes in complex double (k2_fft_job with
 its palindromic power-of-two plans, k2_fft_job_mix for 2560 = 16 x 10 x 16), gfx950 rules of
 tools/ab/lds_conflicts64.py.  Addresses are generated exactly as sh_load/sh_store in
-rsp_kernels.hip compute them.
+rsp_fft_passes.h compute them.
 usage: lds_conflicts_k2v2.py [SH [rows]]      (prints per pass: reads / writes / twiddle-read cost factor,
 1.0 = conflict-free, and the LDS cycles per row weighted by instruction count)"""
 import sys

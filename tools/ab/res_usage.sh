@@ -1,8 +1,12 @@
 #!/bin/bash
-# Per-kernel VGPR / scratch / occupancy of rsp_kernels.hip (hipcc resource-usage remarks), one line each.
+# Per-kernel VGPR / scratch / occupancy of the frame chain's device units (hipcc resource-usage remarks),
+# one line each.  usage: res_usage.sh [UNIT.hip [extra compiler flags]]; no argument: every unit.
 cd "$(dirname "$0")/../../radar-signal-simulation-and-target-detection_amd/csrc"
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -Wno-unused-function -x hip -c ${1:-rsp_kernels.hip} ${@:2} \
-  -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c '
+units=${1:-rsp_k1.hip rsp_k2.hip rsp_k3.hip rsp_frame_aux.hip rsp_stage3.hip rsp_vcfar.hip}
+for u in $units; do
+/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I../../include -Wno-unused-function -x hip -c $u ${@:2} \
+  -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1
+done | python3 -c '
 import sys, re, subprocess
 cur = None
 rows = []

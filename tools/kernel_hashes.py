@@ -11,8 +11,13 @@ hashed together in mangled-name order.  bench.py compares these with the hashes 
 file recorded when it was measured: a kernel whose code changed since has no measured traffic.
 
 --instantiations prints one `hash mangled-name` line per kernel function instead, sorted by name,
-for a library or a single object file (build/rsp_kernels.hip.o): two builds whose lists are equal
+for a library or a single object file (build/rsp_k2.hip.o): two builds whose lists are equal
 run the same machine code in every template instantiation.
+
+The frame chain's kernels are spread over one translation unit per stage (rsp_k1.hip, rsp_k2.hip,
+rsp_k3.hip, rsp_frame_aux.hip, rsp_stage3.hip, rsp_vcfar.hip) plus rsp_music.hip, so a library has
+several code objects.  A kernel's mangled name found in two of them is an error (merge), and the
+Makefile's hash step fails.
 """
 import hashlib
 import json
@@ -75,32 +80,38 @@ def short_name(mangled):
             return name
 
 
+def merge(into, more):
+    """Add one code object's kernels to `into`.  A mangled name that is there already is an error: two
+    translation units define the same kernel, and a plain dict.update would hide one of them."""
+    dup = sorted(set(into) & set(more))
+    if dup:
+        raise SystemExit('kernel defined in two code objects: ' + ', '.join(dup))
+    into.update(more)
+    return into
+
+
 def kernels(path):
     """{mangled name: code bytes} of every kernel in the gfx950 code objects of a library or object."""
     blob = open(path, 'rb').read()
-    funcs = {}
-    for _, elf in code_objects(blob):
-        funcs.update(kernel_code(elf))
-    kd = set()
+    out = {}
     for _, elf in code_objects(blob):   # kernels = functions that have a kernel descriptor
-        kd |= {n[:-3] for n in re.findall(rb'([_A-Za-z0-9]+\.kd)\0', elf) for n in [n.decode()]}
-    return funcs, kd
+        kd = {n.decode()[:-3] for n in re.findall(rb'([_A-Za-z0-9]+\.kd)\0', elf)}
+        merge(out, {nm: code for nm, code in kernel_code(elf).items() if nm in kd})
+    return out
 
 
 def main():
     if '--instantiations' in sys.argv[1:]:
         path, = [a for a in sys.argv[1:] if a != '--instantiations']
-        funcs, kd = kernels(path)
+        funcs = kernels(path)
         for nm in sorted(funcs):
-            if nm in kd:
-                print(hashlib.sha256(funcs[nm]).hexdigest()[:16], nm)
+            print(hashlib.sha256(funcs[nm]).hexdigest()[:16], nm)
         return
     lib, out = sys.argv[1:3]
-    funcs, kd = kernels(lib)
+    funcs = kernels(lib)
     groups = {}
     for nm in sorted(funcs):
-        if nm in kd:
-            groups.setdefault(short_name(nm), []).append(nm)
+        groups.setdefault(short_name(nm), []).append(nm)
     res = {}
     for sn, names in sorted(groups.items()):
         h = hashlib.sha256()
