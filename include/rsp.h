@@ -570,6 +570,87 @@ int32_t rsp_process_stage2_gated_vcfar(rsp_plan* plan, const void* iq_gated, int
 int32_t rsp_profile_vcfar(rsp_plan* plan, const rsp_vcfar_params* params, int32_t iters, float* ms_out,
                           int64_t* bytes_out);
 
+/* ---- stage-1 DBF of the stage-2 path ----
+ * Every stage-2 script of the reference beamforms the raw 16-channel frame (raw_iq_data of a
+ * frame_sim_array_%d.mat, [prtNum x point_PRT x channel_num]) pulse by pulse before it calls
+ * process_stage2_mtd: `single_pulse_16ch * DBF_coeffs_data_C'` (debug_simulated_data_processing.m:
+ * 166-175, _v3.m:144-152; conj != 0 here, the form of fsf:95) or `iq_data_temp *
+ * DBF_coeffs_data_C.'` (main_test_with_simulated_data.m:207-214, one beam of it in
+ * debug_simulated_data_processing_v2.m:176-182; conj = 0).  For every position (p, n):
+ *   beams[p, n, b] = sum_c a[b][c] cube[p, n, c],   a = conj(W) (conj != 0) or a = W,
+ * W = DBF_coeffs_data_C, column-major B x C, interleaved (re, im) doubles.  The sum runs on the
+ * matrix cores in the plan's precision (complex double for RSP_C128, complex single for RSP_C64)
+ * exactly as K1's DBF: channels in groups of 4 in ascending order, per group the real parts of x
+ * before the imaginary parts, every step a fused multiply-add into the running sum.  Not MATLAB's
+ * summation order, so results agree with `x * W'` to rounding, not to the bit. */
+
+/* How k_dbf covers a plane of P N positions (rsp_dbf_describe). */
+typedef struct rsp_dbf_info {
+    int32_t positions;        /* S = P N                                                          */
+    int32_t CP, BMAX;         /* channels and beams rounded up to what the MFMA tiles hold (K1's)  */
+    int32_t sub_tile;         /* positions per MFMA sub-tile: 16 (complex double), 32 (single)     */
+    int32_t tiles_per_wave;   /* sub-tiles whose loads a wave keeps in flight together             */
+    int32_t waves, rounds;    /* waves per workgroup; rounds of tiles_per_wave sub-tiles per wave  */
+    int32_t wg_positions;     /* waves x rounds x tiles_per_wave x sub_tile                        */
+    int32_t workgroups;       /* ceil(S / wg_positions)                                            */
+    int32_t tail_positions;   /* S mod sub_tile: positions of the last, partly filled sub-tile     */
+    int32_t row_layout;       /* RSP_DBF_ROWS_* of the A table the kernel reads                    */
+    int32_t pitch;            /* elements between the planes of rsp_dbf's device buffers           */
+} rsp_dbf_info;
+#define RSP_DBF_ROWS_SPLIT 0   /* MFMA row m of an 8-beam block: beam m & 7, part m >> 3 (0 Re, 1 Im) */
+#define RSP_DBF_ROWS_PAIR 1    /* beam m >> 1, part m & 1                                              */
+
+/* The size checks of rsp_dbf, with the same refusals and messages, and the kernel's tiling, for a
+ * plan of `precision` (RSP_C128 / RSP_C64).  RSP_ERR_INVALID: P < 1, N < 1, C outside 1..32, B
+ * outside 1..16, unknown precision; RSP_ERR_UNSUPPORTED: 2 GB or more of input or output planes.
+ * `info` may be NULL.  No HIP call is made. */
+int32_t rsp_dbf_describe(int32_t P, int32_t N, int32_t C, int32_t B, int32_t precision, rsp_dbf_info* info);
+/* The matrix-core A operands of the DBF for weights W (column-major B x C): [MB][CP/4][2][64]
+ * doubles, MB = 1 (B <= 8) or 2; entry [mb][j][e][lane] is the coefficient of Re x_c (e = 0) or
+ * Im x_c (e = 1), c = 4 j + lane / 16, in MFMA row lane % 16 of block mb -- which (beam, part)
+ * that row is, row_layout says.  *n = the table's length; its first min(cap, *n) entries go to out.
+ * No HIP call is made. */
+int32_t rsp_dbf_table(const double* W, int32_t B, int32_t C, int32_t conj, int32_t row_layout, double* out, int32_t cap,
+                      int32_t* n);
+/* The table a plan of these arguments uploads for K1 (conj(W), RSP_DBF_ROWS_SPLIT), without a device. */
+int32_t rsp_plan_describe_dbf_table(const rsp_sig_config* cfg, const rsp_cfar_params* cfar,
+                                    const rsp_cluster_params* cluster, const rsp_precomputed* pre,
+                                    const rsp_plan_options* opt, int32_t ncu, double* out, int32_t cap, int32_t* n);
+
+/* The DBF of a raw cube of any shape: cube [P x N x C] (dtype RSP_C64 / RSP_C128, converted to the
+ * plan's precision as rsp_process_cube does) -> beams_out complex double [P x N x B].  Any P, N >= 1
+ * (odd too), 1 <= C <= 32, 1 <= B <= 16.  The plan gives only the device and the precision.
+ * Synchronous; drains the queue first.  Refusals (sizes, dtype, null pointers, in that order) come
+ * before any device work. */
+int32_t rsp_dbf(rsp_plan* plan, int32_t P, int32_t N, int32_t C, int32_t B, const void* cube, int32_t dtype,
+                const double* W, int32_t conj, double* beams_out);
+
+/* The stage-2 calls on the raw cube: the scripts' DBF loop and process_stage2_mtd in one call.
+ * cube is [P x n x C] with the plan's P and C.  n_gated = 0 (cols ignored): n is the plan's
+ * point_PRT; otherwise cube holds n_gated gated columns per channel, put back at their PRT
+ * positions as rsp_process_stage2_gated does with beams (cols NULL: the reference gating).
+ * W: column-major B x C as above, NULL = the plan's DBF_coeffs_data_C; conj as rsp_dbf.  The DBF
+ * runs inside the corner turn (K1 with its DBF stage and without the MTD), so the beams never
+ * reach device memory in PRT order; the pulse compression, the MTD over pulses and the detectors
+ * are those of the beams forms, and so are the outputs.  The result equals the beams form fed with
+ * rsp_dbf's beams to the bit.  The A operands of a call are uploaded only when W or conj differ
+ * from the previous raw call's. */
+int32_t rsp_process_raw_stage2(rsp_plan* plan, const void* cube, int32_t dtype, int32_t n_gated, const int32_t* cols,
+                               const double* W, int32_t conj, double* mtd_out, double* pc_out);
+int32_t rsp_process_raw_stage2_cfar(rsp_plan* plan, const void* cube, int32_t dtype, int32_t n_gated, const int32_t* cols,
+                                    const double* W, int32_t conj, const rsp_stage3_cfar_params* params, double* mtd_out,
+                                    double* amp_out, uint8_t* flags, double* threshold, rsp_stage3_hit* hits,
+                                    int64_t hits_cap, int64_t* n_hits);
+int32_t rsp_process_raw_stage2_vcfar(rsp_plan* plan, const void* cube, int32_t dtype, int32_t n_gated, const int32_t* cols,
+                                     const double* W, int32_t conj, const rsp_vcfar_params* params, double* mtd_out,
+                                     double* amp_out, uint8_t* flags, double* threshold, rsp_stage3_hit* hits,
+                                     int64_t hits_cap, int64_t* n_hits);
+/* Device time of k_dbf alone on a cube of P x N x C (zeros) into B beams, by HIP events on the
+ * plan's stream, averaged over `iters` launches; *bytes_out = algorithmic HBM bytes of a launch,
+ * element bytes x P N x (C + B). */
+int32_t rsp_profile_dbf(rsp_plan* plan, int32_t P, int32_t N, int32_t C, int32_t B, int32_t iters, float* ms_out,
+                        int64_t* bytes_out);
+
 /* ---- measurement ----
  * Time each device stage `iters` times on the plan's stream with HIP events.  Each launch
  * batches nf = min(n_cubes, frames_per_launch) frames taken from the device-resident

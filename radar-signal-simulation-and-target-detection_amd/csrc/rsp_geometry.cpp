@@ -502,29 +502,8 @@ int derive_k3_tiling(Geometry& g) {
 void build_tables(const rsp_precomputed* pre, PlanHost& h) {
     Geometry& g = h.g;
     const int C = g.C, B = g.B, P = g.P, G = g.G;
-    // conj(W): y = x * W' (fsf:95), W column-major B x C
-    auto wconj = [&](int b, int c) {
-        const size_t i = (size_t)b + (size_t)B * c;
-        return cd(pre->DBF_coeffs_data_C[2 * i], -pre->DBF_coeffs_data_C[2 * i + 1]);
-    };
-    // per-lane A operands of the DBF MFMA (k1_dbf_mtd): lane l holds A[row l&15][channel 4j + l>>4];
-    // row m: beam mb*8 + (m&7), m<8 -> Re(y), m>=8 -> Im(y); y = sum_c conj(W[b][c]) x_c (fsf:95)
-    const K1Cfg kc = k1_cfg(C, B);
-    const int mblk = kc.MB, nj = kc.NJ;
-    h.atab.assign((size_t)mblk * nj * 2 * 64, 0.0);
-    for (int mb = 0; mb < mblk; ++mb)
-        for (int j = 0; j < nj; ++j)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int m = lane & 15, c = 4 * j + (lane >> 4), b = mb * 8 + (m & 7);
-                double wr = 0, wi = 0;
-                if (b < B && c < C) {
-                    wr = wconj(b, c).real();
-                    wi = wconj(b, c).imag();
-                }
-                const bool im = m >= 8;
-                h.atab[((mb * nj + j) * 2 + 0) * 64 + lane] = im ? wi : wr;    // coefficient of Re(x_c)
-                h.atab[((mb * nj + j) * 2 + 1) * 64 + lane] = im ? wr : -wi;   // coefficient of Im(x_c)
-            }
+    // the DBF's MFMA A operands: conj(W), y = x * W' (fsf:95), in K1's row layout
+    rsp_dbf_atab(pre->DBF_coeffs_data_C, B, C, 1, DBF_ROWS_SPLIT, h.atab);
     h.twP.resize(P);
     if (g.pow2P) build_plan_twiddles(plan_pow2(g.logP), h.twPp, false);
     g.twPp_elems = (int)h.twPp.size();
@@ -574,6 +553,59 @@ bool k1q_fits(const Geometry& g) {
 }
 
 }  // namespace
+
+// per-lane A operands of the DBF MFMA (k1_dbf_mtd, k_dbf): lane l holds A[row l&15][channel 4j + l>>4];
+// row m of block mb is (beam, part) by `layout`; y = sum_c a[b][c] x_c, a = conj(W[b][c]) (fsf:95) or W[b][c]
+void rsp_dbf_atab(const double* W, int B, int C, int conj, int layout, std::vector<double>& atab) {
+    typedef std::complex<double> cd;
+    auto coef = [&](int b, int c) {
+        const size_t i = (size_t)b + (size_t)B * c;
+        return conj ? cd(W[2 * i], -W[2 * i + 1]) : cd(W[2 * i], W[2 * i + 1]);
+    };
+    const K1Cfg kc = k1_cfg(C, B);
+    const int mblk = kc.MB, nj = kc.NJ;
+    atab.assign((size_t)mblk * nj * 2 * 64, 0.0);
+    for (int mb = 0; mb < mblk; ++mb)
+        for (int j = 0; j < nj; ++j)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int m = lane & 15, c = 4 * j + (lane >> 4);
+                const int b = mb * 8 + (layout == DBF_ROWS_PAIR ? m >> 1 : m & 7);
+                double wr = 0, wi = 0;
+                if (b < B && c < C) {
+                    wr = coef(b, c).real();
+                    wi = coef(b, c).imag();
+                }
+                const bool im = layout == DBF_ROWS_PAIR ? (m & 1) != 0 : m >= 8;
+                atab[((mb * nj + j) * 2 + 0) * 64 + lane] = im ? wi : wr;    // coefficient of Re(x_c)
+                atab[((mb * nj + j) * 2 + 1) * 64 + lane] = im ? wr : -wi;   // coefficient of Im(x_c)
+            }
+}
+
+int rsp_dbf_check_sizes(int64_t P, int64_t N, int64_t C, int64_t B, int precision) {
+    if (precision != RSP_C64 && precision != RSP_C128)
+        return fail(RSP_ERR_INVALID, "precision must be RSP_C128 or RSP_C64, got %d", precision);
+    if (P < 1 || N < 1 || C < 1 || C > 32 || B < 1 || B > 16)
+        return fail(RSP_ERR_INVALID, "bad sizes P=%lld N=%lld C=%lld B=%lld (P, N >= 1, 1<=C<=32, 1<=B<=16)", (long long)P,
+                    (long long)N, (long long)C, (long long)B);
+    // a plane of P N positions, one pad position in complex single; C (or B) of them under 2 GB
+    const int64_t esz = precision == RSP_C128 ? 16 : 8, lim = (int64_t)1 << 31;
+    if (P >= lim || N >= lim || P * N >= lim || (P * N + 1) * esz * (C > B ? C : B) >= lim)
+        return fail(RSP_ERR_UNSUPPORTED, "%lld x %lld positions of %lld channels: the kernel addresses a cube with 32-bit offsets (< 2 GB)",
+                    (long long)P, (long long)N, (long long)(C > B ? C : B));
+    return RSP_OK;
+}
+
+int rsp_dbf_check_args(const void* plan, const void* cube, int dtype, const void* W, const void* out) {
+    if (dtype != RSP_C64 && dtype != RSP_C128) return fail(RSP_ERR_INVALID, "unknown dtype %d", dtype);
+    if (!W) return fail(RSP_ERR_INVALID, "null argument: W (the DBF weights, B x C)");
+    if (!plan || !cube || !out) return fail(RSP_ERR_INVALID, "null argument");
+    return RSP_OK;
+}
+
+DbfDesc dbf_desc(int S, int C, int B, int pitch, int opitch, int prec) {
+    const unsigned esz = prec == RSP_PREC_F64 ? 16 : 8;
+    return DbfDesc{S, C, B, pitch, opitch, (unsigned)C * (unsigned)pitch * esz, (unsigned)B * (unsigned)opitch * esz};
+}
 
 size_t k1_tiled_lds(const Geometry& g, bool rq) {
     return ((size_t)g.B * g.NT * g.Ppad + (rq ? rq_table_elems(g.twq_elems, g.P) : g.P)) * cplx_bytes(g);
@@ -920,5 +952,51 @@ extern "C" int32_t rsp_vcfar_describe(int32_t P, int32_t G, const rsp_vcfar_para
     info->cols = RSP_VC_COLS;
     info->row_tiles = (d.P + RSP_VC_ROWS - 1) / RSP_VC_ROWS;
     info->col_tiles = (d.G + RSP_VC_COLS - 1) / RSP_VC_COLS;
+    return RSP_OK;
+}
+
+extern "C" int32_t rsp_dbf_describe(int32_t P, int32_t N, int32_t C, int32_t B, int32_t precision, rsp_dbf_info* info) {
+    int rc = rsp_dbf_check_sizes(P, N, C, B, precision);
+    if (rc || !info) return rc;
+    const int prec = precision == RSP_C128 ? RSP_PREC_F64 : RSP_PREC_F32;
+    const K1Cfg kc = k1_cfg(C, B);
+    const int S = P * N;
+    info->positions = S;
+    info->CP = kc.CP;
+    info->BMAX = kc.BMAX;
+    info->sub_tile = dbf_sub_tile(prec);
+    info->tiles_per_wave = kc.TPW;
+    info->waves = RSP_DBF_THREADS / 64;
+    info->rounds = RSP_DBF_ROUNDS;
+    info->wg_positions = dbf_wg_positions(C, B, prec);
+    info->workgroups = dbf_workgroups(S, C, B, prec);
+    info->tail_positions = S % info->sub_tile;
+    info->row_layout = prec == RSP_PREC_F64 ? DBF_ROWS_SPLIT : DBF_ROWS_PAIR;
+    info->pitch = dbf_pitch(S, prec);
+    return RSP_OK;
+}
+
+extern "C" int32_t rsp_dbf_table(const double* W, int32_t B, int32_t C, int32_t conj, int32_t row_layout, double* out,
+                                 int32_t cap, int32_t* n) {
+    if (!W || !n || cap < 0 || (cap > 0 && !out)) return fail(RSP_ERR_INVALID, "null argument");
+    if (C < 1 || C > 32 || B < 1 || B > 16) return fail(RSP_ERR_INVALID, "bad sizes C=%d B=%d (1<=C<=32, 1<=B<=16)", C, B);
+    if (row_layout != DBF_ROWS_SPLIT && row_layout != DBF_ROWS_PAIR) return fail(RSP_ERR_INVALID, "unknown row layout %d", row_layout);
+    std::vector<double> t;
+    rsp_dbf_atab(W, B, C, conj, row_layout, t);
+    *n = (int32_t)t.size();
+    for (int i = 0; i < cap && i < (int)t.size(); ++i) out[i] = t[i];
+    return RSP_OK;
+}
+
+extern "C" int32_t rsp_plan_describe_dbf_table(const rsp_sig_config* cfg, const rsp_cfar_params* cfar,
+                                               const rsp_cluster_params* cluster, const rsp_precomputed* pre,
+                                               const rsp_plan_options* opt, int32_t ncu, double* out, int32_t cap, int32_t* n) {
+    if (!n || cap < 0 || (cap > 0 && !out)) return fail(RSP_ERR_INVALID, "null argument");
+    int rc = rsp_plan_check_args(cfg, cfar, cluster, pre, opt);
+    if (rc) return rc;
+    PlanHost h;
+    if ((rc = rsp_plan_derive(cfg, cfar, cluster, pre, opt, ncu, &h))) return rc;
+    *n = (int32_t)h.atab.size();
+    for (int i = 0; i < cap && i < (int)h.atab.size(); ++i) out[i] = h.atab[i];
     return RSP_OK;
 }

@@ -266,6 +266,45 @@ constexpr K1Cfg k1_cfg(int C, int B) {
     return K1Cfg{cp, bmax, nj, mb, tpw, 2 * tpw * nj <= 16 && 2 * tpw <= 4};
 }
 
+// The DBF's MFMA A operands per lane, [MB][CP/4][Re, Im][64] reals (MB, CP: k1_cfg(C, B)): lane l of
+// block (mb, j) holds A[row l & 15][channel 4 j + (l >> 4)], entry 0 the coefficient of Re x_c and
+// entry 1 that of Im x_c in the row's part of y_b = sum_c a[b][c] x_c, a = conj(W) (conj != 0, fsf:95)
+// or W; W column-major B x C, interleaved (re, im).  Padded beams and channels: zeros.  Which
+// (beam, part) row m of block mb is:
+//   DBF_ROWS_SPLIT  beam 8 mb + (m & 7), part m >> 3 (0 Re, 1 Im): K1's, and k_dbf's in complex double
+//   DBF_ROWS_PAIR   beam 8 mb + (m >> 1), part m & 1: k_dbf's in complex single
+enum { DBF_ROWS_SPLIT = 0, DBF_ROWS_PAIR = 1 };
+void rsp_dbf_atab(const double* W, int B, int C, int conj, int layout, std::vector<double>& atab);
+
+// ---- the stand-alone DBF (k_dbf, rsp_dbf.hip) ----
+// A workgroup of RSP_DBF_THREADS / 64 waves takes RSP_DBF_ROUNDS rounds of TPW sub-tiles per wave
+// (TPW = K1Cfg::TPW) of 16 (complex double) or 32 (complex single) positions each.
+#define RSP_DBF_THREADS 256
+#define RSP_DBF_ROUNDS 2
+struct DbfDesc {          // kernel argument
+    int S, C, B;          // positions (P N), channels, beams
+    int pitch, opitch;    // complex elements between channel planes / beam planes (even in complex single)
+    unsigned in_bytes, out_bytes;   // C pitch and B opitch elements: the buffer resources' range
+};
+RSP_HD constexpr int dbf_sub_tile(int prec) { return prec == RSP_PREC_F64 ? 16 : 32; }
+RSP_HD constexpr int dbf_wg_positions(int C, int B, int prec) {
+    return (RSP_DBF_THREADS / 64) * RSP_DBF_ROUNDS * k1_cfg(C, B).TPW * dbf_sub_tile(prec);
+}
+RSP_HD constexpr int dbf_workgroups(int S, int C, int B, int prec) {
+    return (S + dbf_wg_positions(C, B, prec) - 1) / dbf_wg_positions(C, B, prec);
+}
+// The plane pitch rsp_dbf gives its own device buffers: S, rounded up to even in complex single
+// (16-B loads and stores of position pairs)
+RSP_HD constexpr int dbf_pitch(int S, int prec) { return prec == RSP_PREC_F64 ? S : (S + 1) & ~1; }
+// The checks of rsp_dbf / rsp_profile_dbf / rsp_dbf_describe that need no device: sizes (P, N >= 1,
+// 1 <= C <= 32, 1 <= B <= 16, the plan's envelope), precision, and that either side of the kernel
+// stays within the 32-bit offsets of a buffer resource.  RSP_OK, or the refusal with its message set.
+int rsp_dbf_check_sizes(int64_t P, int64_t N, int64_t C, int64_t B, int precision);
+// ... and of the call's pointers and dtype
+int rsp_dbf_check_args(const void* plan, const void* cube, int dtype, const void* W, const void* out);
+// The kernel argument for planes at `pitch` / `opitch` elements (sizes already checked)
+DbfDesc dbf_desc(int S, int C, int B, int pitch, int opitch, int prec);
+
 // Which K1 slow-time FFTs run k1_fft_dif (the persistent and the tiled K1 agree, so their outputs
 // are bit-identical): P = 64, 128 always; P = 256 for plans of more than 8 channels (with 8, the
 // persistent K1's 8 sub-tiles of loads per wave and the DIF's registers spill: the Stockham passes)

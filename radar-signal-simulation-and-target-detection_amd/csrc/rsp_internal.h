@@ -58,7 +58,7 @@ struct FramePtrs {
 };
 
 struct DevConsts {
-    const void* Atab;        // DBF MFMA A operands per lane: [MB][CP/4][Re,Im][64] (build_dbf_atab), real
+    const void* Atab;        // DBF MFMA A operands per lane: [MB][CP/4][Re,Im][64] (rsp_dbf_atab), real
     const void* win;         // MTD window [P], real
     const void* twP;         // W_P^i table (direct DFT path), complex
     const void* twPp;        // per-pass Stockham twiddles of the P-point FFT, complex
@@ -105,6 +105,10 @@ hipError_t launch_s3(const S3Desc& d, int prec, bool cplx, const void* in, int n
 // Doppler CA-CFAR (rsp_vcfar.hip) of n_maps maps [n_maps][P][G]: inputs and outputs as launch_s3's.
 hipError_t launch_vcfar(const VcDesc& d, int prec, bool cplx, const void* in, int n_maps, double* amp, double* thr,
                         uint8_t* flags, rsp_stage3_hit* hits, int* count, int hits_cap, hipStream_t s);
+// Stand-alone DBF (rsp_dbf.hip): d.C channel planes x at d.pitch -> d.B beam planes y at d.opitch, both
+// complex of the precision, 16-B aligned; At = rsp_dbf_atab's table in the precision's row layout
+// (double DBF_ROWS_SPLIT, float DBF_ROWS_PAIR) as reals of the precision.
+hipError_t launch_dbf(const DbfDesc& d, int prec, const void* x, const void* At, void* y, hipStream_t s);
 // Queue read-back: count record + the detections of nf frames (device stride dcap + 1 records) into
 // mapped pinned host memory (stride hcap + 1), only the records that exist.
 hipError_t launch_dets_to_host(const void* dets, int dcap, void* host, int hcap, int nf, hipStream_t s);

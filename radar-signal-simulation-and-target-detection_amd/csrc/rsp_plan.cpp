@@ -169,6 +169,14 @@ struct rsp_plan {
         size_t cap = 0;
     };
     DevBuf s3_in, s3_amp, s3_thr, s3_flags, s3_hits, s3_count;
+    // stand-alone DBF (rsp_dbf, rsp_profile_dbf): channel planes, beam planes and the A operands of the call
+    DevBuf dbf_in, dbf_out, dbf_tab;
+    // raw-cube stage 2 (rsp_process_raw_stage2*): the plan's own weights, and the A operands of the last
+    // call whose W / conj were not the plan's (K1's layout; uploaded again only when they change)
+    std::vector<double> h_W;
+    DevBuf raw_tab;
+    std::vector<double> raw_W;
+    int raw_conj = 0;
     unsigned char* h_stage = nullptr;   // pinned staging for uploads
     size_t h_stage_bytes = 0;
     Lane lanes[RSP_LANES];
@@ -264,7 +272,7 @@ rsp_plan::~rsp_plan() {
     for (auto e : slot_free) if (e) (void)hipEventDestroy(e);
     if (up_stream) (void)hipStreamDestroy(up_stream);
     if (h_stage) (void)hipHostFree(h_stage);
-    for (DevBuf* b : {&s3_in, &s3_amp, &s3_thr, &s3_flags, &s3_hits, &s3_count})
+    for (DevBuf* b : {&s3_in, &s3_amp, &s3_thr, &s3_flags, &s3_hits, &s3_count, &dbf_in, &dbf_out, &dbf_tab, &raw_tab})
         if (b->p) (void)hipFree(b->p);
     for (void* p : dev_allocs) (void)hipFree(p);
 }
@@ -672,29 +680,7 @@ int run_sync_frame(rsp_plan* p, const void* d_in, int frame_idx, rsp_frame_out* 
     return RSP_OK;
 }
 
-// The device half of rsp_process_stage2: PC_results into lane 0's map, MTD_results into p->d_aux
-// (both [B][P][G] complex in the plan's precision); returns with the stream idle.
-int stage2_device(rsp_plan* p, const void* iq, int dtype) {
-    HIPCHK(hipSetDevice(p->device));
-    int rc = drain_all(p);
-    if (rc) return rc;
-    Lane& L = p->lanes[0];
-    Geometry gs = p->g;
-    gs.C = gs.B;   // input channels are the beams; K1 transposes only (no DBF, no MTD)
-    if ((rc = upload_cube(p, iq, dtype, gs.B, p->d_cube, L.stream))) return rc;
-    if (!p->d_aux && (rc = p->dalloc_bytes(&p->d_aux, p->rdm_elems * p->esz))) return rc;
-    const void* in[1] = {p->d_cube};
-    void* rdm[1] = {L.rdm};
-    const FramePtrs fp = lane_ptrs(p, L, in, 1, rdm);
-    HIPCHK(launch_k1(gs, p->k, fp, 1, 0, L.stream));
-    HIPCHK(launch_k2(gs, p->k, fp, 1, L.stream));                  // PC rows (b, m) -> L.rdm
-    HIPCHK(launch_mtd_cols(gs, p->k, L.rdm, p->d_aux, L.stream));  // S7 over pulses
-    HIPCHK(hipStreamSynchronize(L.stream));
-    p->aux_valid = true;
-    return RSP_OK;
-}
-
-// ---- stage-3 range CFAR ----
+// A device buffer that grows on demand (the stage-3 CFAR's, the DBF's; freed with the plan)
 int s3_reserve(rsp_plan::DevBuf& b, size_t bytes) {
     if (b.cap >= bytes && b.p) return RSP_OK;
     if (b.p) HIPCHK(hipFree(b.p));
@@ -708,6 +694,68 @@ int s3_reserve(rsp_plan::DevBuf& b, size_t bytes) {
     return RSP_OK;
 }
 
+// The input of a stage-2 call: beams [P x N x B] (raw = false), or the raw cube [P x N x C] with the
+// weights of its DBF (W null: the plan's) -- the scripts' DBF loop fused into the corner turn
+struct Stage2In {
+    const void* data;
+    int dtype;
+    bool raw;
+    const double* W;
+    int conj;
+};
+
+// The DBF A operands (K1's layout) of a raw call on the device: the plan's own table for its own
+// weights conjugated; else the call's, uploaded when W or conj differ from the last raw call's
+int raw_atab(rsp_plan* p, const Stage2In& in, const void** atab) {
+    if (!in.W && in.conj) {
+        *atab = p->k.Atab;
+        return RSP_OK;
+    }
+    const size_t nw = 2 * (size_t)p->g.B * p->g.C;
+    const double* W = in.W ? in.W : p->h_W.data();
+    const bool same = p->raw_tab.p && p->raw_conj == (in.conj != 0) && p->raw_W.size() == nw &&
+                      memcmp(p->raw_W.data(), W, nw * sizeof(double)) == 0;
+    if (!same) {
+        std::vector<double> t;
+        rsp_dbf_atab(W, p->g.B, p->g.C, in.conj, DBF_ROWS_SPLIT, t);
+        p->raw_W.clear();   // no key while the table is being replaced
+        int rc = s3_reserve(p->raw_tab, t.size() * p->rsz);
+        if (rc || (rc = p->put_reals(p->raw_tab.p, t.data(), t.size()))) return rc;
+        p->raw_W.assign(W, W + nw);
+        p->raw_conj = in.conj != 0;
+    }
+    *atab = p->raw_tab.p;
+    return RSP_OK;
+}
+
+// The device half of the stage-2 calls: PC_results into lane 0's map, MTD_results into p->d_aux
+// (both [B][P][G] complex in the plan's precision); returns with the stream idle.  Beams: K1
+// transposes only (its input channels are the beams); a raw cube: K1 runs its DBF as well (mode 1)
+// on the plan's own geometry.  K2 and k_mtd_cols are the same launches for both.
+int stage2_device(rsp_plan* p, const Stage2In& in) {
+    HIPCHK(hipSetDevice(p->device));
+    int rc = drain_all(p);
+    if (rc) return rc;
+    Lane& L = p->lanes[0];
+    Geometry gs = p->g;
+    DevConsts ks = p->k;
+    if (!in.raw) gs.C = gs.B;   // input channels are the beams; no DBF, no MTD
+    else if ((rc = raw_atab(p, in, &ks.Atab))) return rc;
+    if ((rc = upload_cube(p, in.data, in.dtype, gs.C, p->d_cube, L.stream))) return rc;
+    if (!p->d_aux && (rc = p->dalloc_bytes(&p->d_aux, p->rdm_elems * p->esz))) return rc;
+    const void* cube[1] = {p->d_cube};
+    void* rdm[1] = {L.rdm};
+    const FramePtrs fp = lane_ptrs(p, L, cube, 1, rdm);
+    HIPCHK(launch_k1(gs, ks, fp, 1, in.raw ? 1 : 0, L.stream));
+    HIPCHK(launch_k2(gs, ks, fp, 1, L.stream));                  // PC rows (b, m) -> L.rdm
+    HIPCHK(launch_mtd_cols(gs, ks, L.rdm, p->d_aux, L.stream));  // S7 over pulses
+    HIPCHK(hipStreamSynchronize(L.stream));
+    p->aux_valid = true;
+    return RSP_OK;
+}
+int stage2_device(rsp_plan* p, const void* iq, int dtype) { return stage2_device(p, Stage2In{iq, dtype, false, nullptr, 1}); }
+
+// ---- stage-3 range CFAR ----
 struct S3Out {   // host outputs of one CFAR call, each optional
     double* amp;
     uint8_t* flags;
@@ -779,18 +827,18 @@ int vc_run(rsp_plan* p, const VcDesc& d, bool cplx, const void* d_in, int n_maps
                     });
 }
 
-int s3_fused(rsp_plan* p, const void* iq, int dtype, const rsp_stage3_cfar_params* prm, double* mtd_out, const S3Out& o) {
+int s3_fused(rsp_plan* p, const Stage2In& in, const rsp_stage3_cfar_params* prm, double* mtd_out, const S3Out& o) {
     S3Desc d;
     int rc = rsp_stage3_derive(p->g.P, p->gates, prm, &d);   // refusals before any device work
-    if (rc || (rc = rsp_s3_check_cells(d.P, d.G, p->g.B)) || (rc = stage2_device(p, iq, dtype))) return rc;
+    if (rc || (rc = rsp_s3_check_cells(d.P, d.G, p->g.B)) || (rc = stage2_device(p, in))) return rc;
     if (mtd_out && (rc = rdm_out(p, p->d_aux, mtd_out))) return rc;
     return s3_run(p, d, true, p->d_aux, p->g.B, o);
 }
 
-int vc_fused(rsp_plan* p, const void* iq, int dtype, const rsp_vcfar_params* prm, double* mtd_out, const S3Out& o) {
+int vc_fused(rsp_plan* p, const Stage2In& in, const rsp_vcfar_params* prm, double* mtd_out, const S3Out& o) {
     VcDesc d;
     int rc = rsp_vcfar_derive(p->g.P, p->g.G, prm, &d);   // refusals before any device work
-    if (rc || (rc = rsp_s3_check_cells(d.P, d.G, p->g.B)) || (rc = stage2_device(p, iq, dtype))) return rc;
+    if (rc || (rc = rsp_s3_check_cells(d.P, d.G, p->g.B)) || (rc = stage2_device(p, in))) return rc;
     if (mtd_out && (rc = rdm_out(p, p->d_aux, mtd_out))) return rc;
     return vc_run(p, d, true, p->d_aux, p->g.B, o);
 }
@@ -876,6 +924,7 @@ int32_t rsp_plan_create_ex(const rsp_sig_config* cfg, const rsp_cfar_params* cfa
     p->g = h.g;
     p->det_bound = h.det_bound;
     p->z_elems = h.z_elems; p->rdm_elems = h.rdm_elems; p->mag_elems = h.mag_elems;
+    p->h_W.assign(pre->DBF_coeffs_data_C, pre->DBF_coeffs_data_C + 2 * (size_t)h.g.B * h.g.C);
     p->gates[0] = pre->N_gate_narrow; p->gates[1] = pre->N_gate_medium; p->gates[2] = pre->N_gate_long;
 
     // ---- constants to the device, in the plan's precision
@@ -1276,7 +1325,7 @@ int32_t rsp_process_stage2_cfar(rsp_plan* p, const void* iq, int32_t dtype, cons
                                 double* mtd_out, double* amp_out, uint8_t* flags, double* threshold, rsp_stage3_hit* hits,
                                 int64_t hits_cap, int64_t* n_hits) {
     const int rc = s3_args(p, iq, prm, hits_cap);
-    return rc ? rc : s3_fused(p, iq, dtype, prm, mtd_out, S3Out{amp_out, flags, threshold, hits, hits_cap, n_hits});
+    return rc ? rc : s3_fused(p, Stage2In{iq, dtype, false, nullptr, 1}, prm, mtd_out, S3Out{amp_out, flags, threshold, hits, hits_cap, n_hits});
 }
 
 int32_t rsp_process_stage2_gated_cfar(rsp_plan* p, const void* iq, int32_t dtype, int32_t n_gated, const int32_t* cols,
@@ -1288,7 +1337,7 @@ int32_t rsp_process_stage2_gated_cfar(rsp_plan* p, const void* iq, int32_t dtype
     std::vector<unsigned char> full;
     if ((rc = rsp_stage2_regate(p->g.P, p->g.N, p->g.B, iq, dtype, n_gated, cols, full))) return rc;
     const S3Out o{amp_out, flags, threshold, hits, hits_cap, n_hits};
-    return s3_fused(p, full.data(), dtype, prm, mtd_out, o);
+    return s3_fused(p, Stage2In{full.data(), dtype, false, nullptr, 1}, prm, mtd_out, o);
 }
 
 int32_t rsp_profile_stage3(rsp_plan* p, const rsp_stage3_cfar_params* prm, int32_t iters, float* ms_out, int64_t* bytes_out) {
@@ -1359,7 +1408,7 @@ int32_t rsp_process_stage2_vcfar(rsp_plan* p, const void* iq, int32_t dtype, con
                                  double* amp_out, uint8_t* flags, double* threshold, rsp_stage3_hit* hits, int64_t hits_cap,
                                  int64_t* n_hits) {
     const int rc = s3_args(p, iq, prm, hits_cap);
-    return rc ? rc : vc_fused(p, iq, dtype, prm, mtd_out, S3Out{amp_out, flags, threshold, hits, hits_cap, n_hits});
+    return rc ? rc : vc_fused(p, Stage2In{iq, dtype, false, nullptr, 1}, prm, mtd_out, S3Out{amp_out, flags, threshold, hits, hits_cap, n_hits});
 }
 
 int32_t rsp_process_stage2_gated_vcfar(rsp_plan* p, const void* iq, int32_t dtype, int32_t n_gated, const int32_t* cols,
@@ -1371,7 +1420,7 @@ int32_t rsp_process_stage2_gated_vcfar(rsp_plan* p, const void* iq, int32_t dtyp
     std::vector<unsigned char> full;
     if ((rc = rsp_stage2_regate(p->g.P, p->g.N, p->g.B, iq, dtype, n_gated, cols, full))) return rc;
     const S3Out o{amp_out, flags, threshold, hits, hits_cap, n_hits};
-    return vc_fused(p, full.data(), dtype, prm, mtd_out, o);
+    return vc_fused(p, Stage2In{full.data(), dtype, false, nullptr, 1}, prm, mtd_out, o);
 }
 
 int32_t rsp_profile_vcfar(rsp_plan* p, const rsp_vcfar_params* prm, int32_t iters, float* ms_out, int64_t* bytes_out) {
@@ -1416,6 +1465,118 @@ int32_t rsp_profile_vcfar(rsp_plan* p, const rsp_vcfar_params* prm, int32_t iter
         if (ms_out) ms_out[s] = ms;
     }
     if (bytes_out) rsp_stage3_bytes((int64_t)cells, (int)p->esz, bytes_out);
+    return RSP_OK;
+}
+
+// The raw cube of a raw-cube stage-2 call as the full-PRT [P x N x C] the device takes: the caller's, or
+// (n_gated != 0) its gated columns put back at their PRT positions in `full`
+static int raw_full_prt(const rsp_plan* p, const void* cube, int dtype, int n_gated, const int32_t* cols,
+                        std::vector<unsigned char>& full, const void** out) {
+    *out = cube;
+    if (!n_gated) return dtype == RSP_C64 || dtype == RSP_C128 ? RSP_OK : fail(RSP_ERR_INVALID, "unknown dtype %d", dtype);
+    const int rc = rsp_stage2_regate(p->g.P, p->g.N, p->g.C, cube, dtype, n_gated, cols, full);
+    *out = full.data();
+    return rc;
+}
+
+int32_t rsp_process_raw_stage2(rsp_plan* p, const void* cube, int32_t dtype, int32_t n_gated, const int32_t* cols,
+                               const double* W, int32_t conj, double* mtd_out, double* pc_out) {
+    if (!p || !cube) return fail(RSP_ERR_INVALID, "null argument");
+    std::vector<unsigned char> full;
+    const void* src;
+    int rc = raw_full_prt(p, cube, dtype, n_gated, cols, full, &src);
+    if (rc || (rc = stage2_device(p, Stage2In{src, dtype, true, W, conj}))) return rc;
+    if (pc_out && (rc = rdm_out(p, p->lanes[0].rdm, pc_out))) return rc;
+    if (mtd_out && (rc = rdm_out(p, p->d_aux, mtd_out))) return rc;
+    return RSP_OK;
+}
+
+int32_t rsp_process_raw_stage2_cfar(rsp_plan* p, const void* cube, int32_t dtype, int32_t n_gated, const int32_t* cols,
+                                    const double* W, int32_t conj, const rsp_stage3_cfar_params* prm, double* mtd_out,
+                                    double* amp_out, uint8_t* flags, double* threshold, rsp_stage3_hit* hits,
+                                    int64_t hits_cap, int64_t* n_hits) {
+    S3Desc d;
+    int rc = s3_args(p, cube, prm, hits_cap);
+    if (rc || (rc = rsp_stage3_derive(p->g.P, p->gates, prm, &d))) return rc;   // before the re-insertion's work too
+    std::vector<unsigned char> full;
+    const void* src;
+    if ((rc = raw_full_prt(p, cube, dtype, n_gated, cols, full, &src))) return rc;
+    return s3_fused(p, Stage2In{src, dtype, true, W, conj}, prm, mtd_out, S3Out{amp_out, flags, threshold, hits, hits_cap, n_hits});
+}
+
+int32_t rsp_process_raw_stage2_vcfar(rsp_plan* p, const void* cube, int32_t dtype, int32_t n_gated, const int32_t* cols,
+                                     const double* W, int32_t conj, const rsp_vcfar_params* prm, double* mtd_out,
+                                     double* amp_out, uint8_t* flags, double* threshold, rsp_stage3_hit* hits,
+                                     int64_t hits_cap, int64_t* n_hits) {
+    VcDesc d;
+    int rc = s3_args(p, cube, prm, hits_cap);
+    if (rc || (rc = rsp_vcfar_derive(p->g.P, p->g.G, prm, &d))) return rc;   // before the re-insertion's work too
+    std::vector<unsigned char> full;
+    const void* src;
+    if ((rc = raw_full_prt(p, cube, dtype, n_gated, cols, full, &src))) return rc;
+    return vc_fused(p, Stage2In{src, dtype, true, W, conj}, prm, mtd_out, S3Out{amp_out, flags, threshold, hits, hits_cap, n_hits});
+}
+
+// The device buffers and the kernel argument of a k_dbf launch of these sizes (already checked)
+static int dbf_reserve(rsp_plan* p, int S, int C, int B, DbfDesc* d) {
+    const int pitch = dbf_pitch(S, p->g.prec);
+    *d = dbf_desc(S, C, B, pitch, pitch, p->g.prec);
+    const K1Cfg kc = k1_cfg(C, B);
+    int rc;
+    if ((rc = s3_reserve(p->dbf_in, d->in_bytes)) || (rc = s3_reserve(p->dbf_out, d->out_bytes))) return rc;
+    return s3_reserve(p->dbf_tab, (size_t)kc.MB * kc.NJ * 2 * 64 * p->rsz);
+}
+
+int32_t rsp_dbf(rsp_plan* p, int32_t P, int32_t N, int32_t C, int32_t B, const void* cube, int32_t dtype, const double* W,
+                int32_t conj, double* beams_out) {
+    int rc = rsp_dbf_check_sizes(P, N, C, B, p ? (p->g.prec == RSP_PREC_F64 ? RSP_C128 : RSP_C64) : RSP_C128);
+    if (rc || (rc = rsp_dbf_check_args(p, cube, dtype, W, beams_out))) return rc;   // refusals before any device work
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    const bool f64 = p->g.prec == RSP_PREC_F64;
+    const size_t S = (size_t)P * N, esz = p->esz;
+    DbfDesc d;
+    if ((rc = dbf_reserve(p, (int)S, C, B, &d))) return rc;
+    hipStream_t s = p->lanes[0].stream;
+    std::vector<double> t;
+    rsp_dbf_atab(W, B, C, conj, f64 ? DBF_ROWS_SPLIT : DBF_ROWS_PAIR, t);
+    if ((rc = p->put_reals(p->dbf_tab.p, t.data(), t.size()))) return rc;
+    const void* src = cube;
+    if ((dtype == RSP_C128) != f64) {   // as upload_cube: a converting copy only when the dtypes differ
+        if ((rc = ensure_stage(p, S * C * esz))) return rc;
+        rsp_convert_reals(cube, dtype, 2 * S * C, p->h_stage);
+        src = p->h_stage;
+    }
+    HIPCHK(hipMemcpy2DAsync(p->dbf_in.p, (size_t)d.pitch * esz, src, S * esz, S * esz, C, hipMemcpyHostToDevice, s));
+    HIPCHK(launch_dbf(d, p->g.prec, p->dbf_in.p, p->dbf_tab.p, p->dbf_out.p, s));
+    // the beam planes, widened to double for a complex-single plan
+    std::vector<float> nar(f64 ? 0 : 2 * S * B);
+    void* dst = f64 ? (void*)beams_out : (void*)nar.data();
+    HIPCHK(hipMemcpy2DAsync(dst, S * esz, p->dbf_out.p, (size_t)d.opitch * esz, S * esz, B, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));   // the caller's cube (or the staging buffer) is borrowed for the call
+    if (!f64) rsp_convert_reals(nar.data(), RSP_C64, 2 * S * B, beams_out);
+    return RSP_OK;
+}
+
+int32_t rsp_profile_dbf(rsp_plan* p, int32_t P, int32_t N, int32_t C, int32_t B, int32_t iters, float* ms_out,
+                        int64_t* bytes_out) {
+    if (!p || iters < 1 || !ms_out) return fail(RSP_ERR_INVALID, "bad argument");
+    int rc = rsp_dbf_check_sizes(P, N, C, B, p->g.prec == RSP_PREC_F64 ? RSP_C128 : RSP_C64);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    const int S = P * N;
+    DbfDesc d;
+    if ((rc = dbf_reserve(p, S, C, B, &d))) return rc;
+    hipStream_t s = p->lanes[0].stream;
+    HIPCHK(hipMemsetAsync(p->dbf_in.p, 0, d.in_bytes, s));   // zeros, and zero weights: the time does not depend on the values
+    HIPCHK(hipMemsetAsync(p->dbf_tab.p, 0, p->dbf_tab.cap, s));
+    auto run = [&]() -> int {
+        HIPCHK(launch_dbf(d, p->g.prec, p->dbf_in.p, p->dbf_tab.p, p->dbf_out.p, s));
+        return RSP_OK;
+    };
+    if ((rc = time_launches(s, iters, run, ms_out))) return rc;
+    if (bytes_out) *bytes_out = (int64_t)p->esz * S * (C + B);
     return RSP_OK;
 }
 

@@ -6,6 +6,9 @@ Drop-in for the MATLAB reference's per-frame chain
 * ``fun_process_single_frame(targets, config, cfar_params, cluster_params,
   precomputed_data, frame_idx)``  -- fun_process_single_frame.m:13
 * ``process_stage2_mtd(iq_data, angle, config)``  -- process_stage2_mtd.m:1
+* ``dbf_beams(raw_iq_data, DBF_coeffs_data_C)`` / ``process_frame_stage2(raw_iq_data, angle, config,
+  DBF_coeffs_data_C)`` -- the DBF loop every stage-2 script runs first
+  (debug_simulated_data_processing.m:166-175), alone or fused with process_stage2_mtd
 * ``precompute(...)`` -- the driver's "%% 3" section (v8:79-155)
 * ``load_frame`` / ``save_frame`` -- the ``frame_sim_array_%d.mat`` load/save pair
   (main_simulate_echoes_with_array_v2.m:285, debug_simulated_data_processing_v3.m:20-22)
@@ -22,7 +25,7 @@ from .config import (named_config, make_config, default_cfar_params, default_clu
                      v8_2_targets, evolve_targets, V8_FIR, stage2_config, debug_v3_config,
                      debug_v2_cfar_config, v3_cfar_params)
 from .precompute import precompute
-from .plan import Plan, process_targets_multi, describe_vcfar
+from .plan import Plan, process_targets_multi, describe_vcfar, describe_dbf
 from ._abi import RspError
 from .matio import load_frame, save_frame
 from .music import MusicPlan, MUSIC_1D, MusicPlan2D, MUSIC_2D
@@ -121,6 +124,43 @@ def process_stage2_mtd(iq_data, angle, config, precomputed_data=None, gate_cols=
     if iq.shape[1] == p.N:
         return p.process_stage2(iq)
     return p.process_stage2(iq, gate_cols=gate_cols if gate_cols is not None else REFERENCE_GATE_COLS)
+
+
+def dbf_beams(raw_iq_data, DBF_coeffs_data_C, conj=True, device=0, precision='c128'):
+    """The DBF loop of the stage-2 scripts: ``iq_data_13beam(i, :, :) = squeeze(raw_iq_data(i, :, :)) *
+    DBF_coeffs_data_C'`` for every pulse i (debug_simulated_data_processing.m:166-175,
+    debug_simulated_data_processing_v3.m:144-152), or with ``conj=False`` the plain transpose ``.'``
+    of main_test_with_simulated_data.m:207-214 (one beam of it: debug_simulated_data_processing_v2.m:
+    176-182).  ``raw_iq_data`` is [prtNum, point_PRT, channel_num] of any shape, ``DBF_coeffs_data_C``
+    [beam_num, channel_num]; returns complex128 [prtNum, point_PRT, beam_num].  'c128' computes in
+    complex double like MATLAB, 'c64' in complex single (widened to double)."""
+    cfg, cfar, cluster, W, ang, k = named_config('plumbing')   # the plan gives the device and the precision only
+    p = _plan_for(cfg, cfar, cluster, precompute(cfg, W, ang, k, V8_FIR), device, precision)
+    return p.dbf(raw_iq_data, DBF_coeffs_data_C, conj=conj)
+
+
+def process_frame_stage2(raw_iq_data, angle, config, DBF_coeffs_data_C, conj=True, gate_cols=None,
+                         precomputed_data=None, device=0, precision='c128'):
+    """The stage-2 scripts from the raw frame on: the DBF loop (``dbf_beams``) and
+    ``process_stage2_mtd(iq_data_13beam, angle, config)`` in one call, without the beams leaving the
+    device.  ``raw_iq_data[m, n, c]`` is the raw 16-channel frame (``load_frame``'s cube), full PRT or
+    gated as ``process_stage2_mtd`` takes it (n = 3404: the v2 gating; others via ``gate_cols``);
+    ``DBF_coeffs_data_C`` is [beam_num, channel_num]; ``conj`` as ``dbf_beams``.  Returns
+    ``(MTD_results, PC_results)``, complex [P, G, B], equal to the two calls in a row to the bit."""
+    raw = np.asarray(raw_iq_data)
+    W = np.asarray(DBF_coeffs_data_C, np.complex128)
+    if raw.ndim != 3 or W.ndim != 2 or W.shape[1] != raw.shape[2]:
+        raise ValueError('raw_iq_data %r and DBF_coeffs_data_C %r: expected [P, n, C] and [B, C]' % (raw.shape, W.shape))
+    config = stage2_config(config)
+    config = dict(config, Sig_Config=dict(config['Sig_Config'], channel_num=int(raw.shape[2])))
+    if W.shape[0] != config['Sig_Config']['beam_num']:
+        raise ValueError('DBF_coeffs_data_C has %d rows, config has %d beams' % (W.shape[0], config['Sig_Config']['beam_num']))
+    if precomputed_data is None:
+        precomputed_data = _stage2_precompute(config)
+    p = _plan_for(config, default_cfar_params(), default_cluster_params(), precomputed_data, device, precision)
+    if raw.shape[1] == p.N:
+        return p.process_raw_stage2(raw, W, conj=conj)
+    return p.process_raw_stage2(raw, W, conj=conj, gate_cols=gate_cols if gate_cols is not None else REFERENCE_GATE_COLS)
 
 
 def local_execute_cfar(mtd_amplitude_map, cfar_params, config, device=0, precision='c128'):

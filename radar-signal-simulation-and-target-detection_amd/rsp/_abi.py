@@ -134,6 +134,13 @@ class VcfarInfo(ct.Structure):
                 ('rows', ct.c_int32), ('cols', ct.c_int32), ('row_tiles', ct.c_int32), ('col_tiles', ct.c_int32)]
 
 
+class DbfInfo(ct.Structure):
+    _fields_ = [(n, ct.c_int32) for n in ('positions', 'CP', 'BMAX', 'sub_tile', 'tiles_per_wave', 'waves', 'rounds',
+                                          'wg_positions', 'workgroups', 'tail_positions', 'row_layout', 'pitch')]
+
+
+RSP_DBF_ROWS_SPLIT, RSP_DBF_ROWS_PAIR = 0, 1
+
 RSP_PLAN_K1_TILED = 1
 RSP_PLAN_MONOPULSE_COMPLEX = 2
 RSP_PLAN_K2_ALL_ROWS = 4
@@ -295,6 +302,24 @@ PROTOTYPES = {
                                                     ct.POINTER(Stage3Hit), ct.c_int64, ct.POINTER(ct.c_int64)]),
     'rsp_profile_vcfar': (ct.c_int32, [_P, ct.POINTER(VcfarParams), ct.c_int32, ct.POINTER(ct.c_float),
                                        ct.POINTER(ct.c_int64)]),
+    'rsp_dbf_describe': (ct.c_int32, [ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, ct.POINTER(DbfInfo)]),
+    'rsp_dbf_table': (ct.c_int32, [_dp, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, _dp, ct.c_int32,
+                                   ct.POINTER(ct.c_int32)]),
+    'rsp_plan_describe_dbf_table': (ct.c_int32, [ct.POINTER(SigConfig), ct.POINTER(CfarParams),
+                                                 ct.POINTER(ClusterParams), ct.POINTER(Precomputed),
+                                                 ct.POINTER(PlanOptions), ct.c_int32, _dp, ct.c_int32,
+                                                 ct.POINTER(ct.c_int32)]),
+    'rsp_dbf': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, _P, ct.c_int32, _dp, ct.c_int32, _dp]),
+    'rsp_process_raw_stage2': (ct.c_int32, [_P, _P, ct.c_int32, ct.c_int32, ct.POINTER(ct.c_int32), _dp, ct.c_int32,
+                                            _dp, _dp]),
+    'rsp_process_raw_stage2_cfar': (ct.c_int32, [_P, _P, ct.c_int32, ct.c_int32, ct.POINTER(ct.c_int32), _dp, ct.c_int32,
+                                                 ct.POINTER(Stage3CfarParams), _dp, _dp, _U8, _dp,
+                                                 ct.POINTER(Stage3Hit), ct.c_int64, ct.POINTER(ct.c_int64)]),
+    'rsp_process_raw_stage2_vcfar': (ct.c_int32, [_P, _P, ct.c_int32, ct.c_int32, ct.POINTER(ct.c_int32), _dp, ct.c_int32,
+                                                  ct.POINTER(VcfarParams), _dp, _dp, _U8, _dp,
+                                                  ct.POINTER(Stage3Hit), ct.c_int64, ct.POINTER(ct.c_int64)]),
+    'rsp_profile_dbf': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32,
+                                     ct.POINTER(ct.c_float), ct.POINTER(ct.c_int64)]),
     'rsp_profile_stages': (ct.c_int32, [_P, ct.POINTER(_P), ct.c_int32, ct.c_int32, ct.POINTER(ct.c_float),
                                         ct.POINTER(ct.c_int64), ct.c_int32, ct.POINTER(ct.c_int32)]),
     'rsp_profile_stages_rdm': (ct.c_int32, [_P, ct.POINTER(_P), ct.c_int32, ct.POINTER(_P), ct.c_int32,

@@ -268,6 +268,55 @@ def describe_vcfar(P, G, cfar, method='ca'):
     return {k: getattr(info, k) for k, _ in _abi.VcfarInfo._fields_}
 
 
+DBF_ROW_LAYOUTS = {'split': _abi.RSP_DBF_ROWS_SPLIT, 'pair': _abi.RSP_DBF_ROWS_PAIR}
+
+
+def describe_dbf(P, N, C, B, precision='c128'):
+    """How k_dbf covers a [P, N, C] cube into B beams in a plan of ``precision``, without a device
+    (rsp_dbf_describe): ``positions`` = P N, ``CP``, ``BMAX``, ``sub_tile`` (positions per MFMA
+    sub-tile), ``tiles_per_wave``, ``waves``, ``rounds``, ``wg_positions``, ``workgroups``,
+    ``tail_positions`` (of the last, partly filled sub-tile), ``row_layout`` ('split' / 'pair') and
+    ``pitch``.  Refusals raise RspError with the code and message ``Plan.dbf`` gives."""
+    if precision not in ('c128', 'c64'):
+        raise ValueError("precision must be 'c128' or 'c64'")
+    info = _abi.DbfInfo()
+    check(lib().rsp_dbf_describe(int(P), int(N), int(C), int(B), _abi.RSP_C128 if precision == 'c128' else _abi.RSP_C64,
+                                 ct.byref(info)))
+    d = {k: getattr(info, k) for k, _ in _abi.DbfInfo._fields_}
+    d['row_layout'] = {v: k for k, v in DBF_ROW_LAYOUTS.items()}[d['row_layout']]
+    return d
+
+
+def _table(call):
+    n = ct.c_int32(0)
+    check(call(None, 0, ct.byref(n)))
+    t = np.empty(max(n.value, 1), np.float64)
+    check(call(_dptr(t), n.value, ct.byref(n)))
+    return t[:n.value].reshape(-1, 2, 64)
+
+
+def dbf_table(W, conj=True, row_layout='split'):
+    """The DBF's matrix-core A operands for weights ``W`` [B, C] (rsp_dbf_table): a float64 array
+    [MB * CP / 4, 2, 64]; entry [mb * CP / 4 + j, e, lane] is the coefficient of Re x_c (e = 0) or Im x_c
+    (e = 1), c = 4 j + lane // 16, in MFMA row lane % 16 of block mb.  ``row_layout`` 'split': that row
+    is beam 8 mb + m % 8, part m // 8 (K1's); 'pair': beam 8 mb + m // 2, part m % 2."""
+    W = np.asarray(W, np.complex128)
+    B, C = W.shape
+    Wcm = np.asfortranarray(W).ravel(order='F').view(np.float64)
+    return _table(lambda out, cap, n: lib().rsp_dbf_table(_dptr(Wcm), B, C, 1 if conj else 0, DBF_ROW_LAYOUTS[row_layout],
+                                                          out, cap, n))
+
+
+def describe_dbf_table(config, cfar_params, cluster_params, precomputed_data, precision='c128', ncu=256):
+    """The A operands a plan of these arguments uploads for K1, without a device
+    (rsp_plan_describe_dbf_table): as ``dbf_table(W, True, 'split')``."""
+    keep = []
+    cfg, cfar, cluster, pre = _marshal(config, cfar_params, cluster_params, precomputed_data, keep)
+    opt = _options(0, 1, precision, False, 'amplitude')
+    return _table(lambda out, cap, n: lib().rsp_plan_describe_dbf_table(
+        ct.byref(cfg), ct.byref(cfar), ct.byref(cluster), ct.byref(pre), ct.byref(opt), int(ncu), out, cap, n))
+
+
 class Plan:
     """One device plan = the reference's per-frame kernel bound to fixed config/precompute.
 
@@ -449,6 +498,49 @@ class Plan:
             check(lib().rsp_process_stage2_gated(self.h, ap, dt, iq.shape[1], cols, mo, po))
         return mtd, pc
 
+    def _stage2_detect(self, iq, nch, gate_cols, prm, want, hits_cap, full_fn, gated_fn=None, raw=None):
+        """The fused stage-2 + detector calls: ``iq`` [P, n, nch] (beams, or the raw cube with ``raw`` =
+        (W pointer or None, conj)), ``prm`` the detector's C parameters, ``full_fn`` / ``gated_fn`` the C
+        entries of the beams forms (raw: ``full_fn`` takes n_gated and cols itself).  Returns the dict
+        ``process_stage2_cfar`` documents."""
+        want = set(want)
+        if not want <= set(STAGE3_WANT):
+            raise ValueError('want: unknown output(s) %r' % (sorted(want - set(STAGE3_WANT)),))
+        iq = np.asarray(iq)
+        what = ('iq', 'B') if raw is None else ('cube', 'C')
+        a, iqp, dt = _complex_arg(iq)
+        shp = (self.P, self.G, self.B)
+        if gate_cols is None and iq.shape != (self.P, self.N, nch):
+            raise ValueError('%s shape %r != (P, N, %s) = %r' % (what[0], iq.shape, what[1], (self.P, self.N, nch)))
+        if gate_cols is not None and (iq.ndim != 3 or iq.shape[0] != self.P or iq.shape[2] != nch):
+            raise ValueError('%s shape %r: expected (P, n, %s) with P=%d %s=%d'
+                             % (what[0], iq.shape, what[1], self.P, what[1], nch))
+        res, ptr = {}, {}
+        for name, dtype in (('mtd', np.complex128), ('amp', np.float64), ('flags', np.uint8), ('threshold', np.float64)):
+            if name in want:
+                res[name] = np.empty(shp, dtype, order='F')
+                ptr[name] = res[name].ctypes.data_as(ct.POINTER(ct.c_uint8 if name == 'flags' else ct.c_double))
+            else:
+                ptr[name] = None
+        total = ct.c_int64()
+
+        def call(cap, hp, maps):
+            m = ptr if maps else dict.fromkeys(ptr)
+            tail = (ct.byref(prm), m['mtd'], m['amp'], m['flags'], m['threshold'], hp, cap, ct.byref(total))
+            if raw is not None:
+                ng, cols = (0, None) if gate_cols is None else (iq.shape[1], _gate_cols_arg(gate_cols))
+                check(full_fn(self.h, iqp, dt, ng, cols, raw[0], raw[1], *tail))
+            elif gate_cols is None:
+                check(full_fn(self.h, iqp, dt, *tail))
+            else:
+                check(gated_fn(self.h, iqp, dt, iq.shape[1], _gate_cols_arg(gate_cols), *tail))
+            return total.value
+
+        res['n_hits'], hits = _with_hits(call, max(4096, self.P * self.G * self.B // 8), hits_cap, 'hits' in want)
+        if 'hits' in want:
+            res['hits'] = hits
+        return res
+
     # ---- stage-3 range CFAR of the stage-2 path ---------------------------------------------
     def stage3_cfar(self, amp, cfar, segments=None, hits_cap=None, want_hits=True):
         """local_execute_cfar (debug_simulated_data_processing_v2.m:419-511) on real amplitude maps
@@ -498,39 +590,8 @@ class Plan:
         (uint8), 'threshold', 'hits' (HIT_DTYPE array, beam then find() order; with ``hits_cap``
         its first entries); ``n_hits`` always.  A call that wants the hits alone downloads nothing
         else."""
-        want = set(want)
-        if not want <= set(STAGE3_WANT):
-            raise ValueError('want: unknown output(s) %r' % (sorted(want - set(STAGE3_WANT)),))
-        iq = np.asarray(iq_beams)
-        a, iqp, dt = _complex_arg(iq)
-        shp = (self.P, self.G, self.B)
-        if gate_cols is None and iq.shape != (self.P, self.N, self.B):
-            raise ValueError('iq shape %r != (P, N, B) = %r' % (iq.shape, (self.P, self.N, self.B)))
-        if gate_cols is not None and (iq.ndim != 3 or iq.shape[0] != self.P or iq.shape[2] != self.B):
-            raise ValueError('iq shape %r: expected (P, n, B) with P=%d B=%d' % (iq.shape, self.P, self.B))
-        prm = _stage3_params(cfar)
-        res, ptr = {}, {}
-        for name, dtype in (('mtd', np.complex128), ('amp', np.float64), ('flags', np.uint8), ('threshold', np.float64)):
-            if name in want:
-                res[name] = np.empty(shp, dtype, order='F')
-                ptr[name] = res[name].ctypes.data_as(ct.POINTER(ct.c_uint8 if name == 'flags' else ct.c_double))
-            else:
-                ptr[name] = None
-        total = ct.c_int64()
-
-        def call(cap, hp, maps):
-            m = ptr if maps else dict.fromkeys(ptr)
-            tail = (ct.byref(prm), m['mtd'], m['amp'], m['flags'], m['threshold'], hp, cap, ct.byref(total))
-            if gate_cols is None:
-                check(lib().rsp_process_stage2_cfar(self.h, iqp, dt, *tail))
-            else:
-                check(lib().rsp_process_stage2_gated_cfar(self.h, iqp, dt, iq.shape[1], _gate_cols_arg(gate_cols), *tail))
-            return total.value
-
-        res['n_hits'], hits = _with_hits(call, max(4096, self.P * self.G * self.B // 8), hits_cap, 'hits' in want)
-        if 'hits' in want:
-            res['hits'] = hits
-        return res
+        return self._stage2_detect(iq_beams, self.B, gate_cols, _stage3_params(cfar), want, hits_cap,
+                                   lib().rsp_process_stage2_cfar, lib().rsp_process_stage2_gated_cfar)
 
     def profile_stage3(self, cfar, iters=20):
         """HIP-event time of k_s3_cfar over the B beams of the plan's last stage-2 result
@@ -578,39 +639,8 @@ class Plan:
         leaving the device (rsp_process_stage2_vcfar / _gated_vcfar).  ``iq_beams``, ``gate_cols``,
         ``want`` and ``hits_cap`` as ``process_stage2_cfar``; ``cfar`` and ``method`` as
         ``doppler_cfar``."""
-        want = set(want)
-        if not want <= set(STAGE3_WANT):
-            raise ValueError('want: unknown output(s) %r' % (sorted(want - set(STAGE3_WANT)),))
-        iq = np.asarray(iq_beams)
-        a, iqp, dt = _complex_arg(iq)
-        shp = (self.P, self.G, self.B)
-        if gate_cols is None and iq.shape != (self.P, self.N, self.B):
-            raise ValueError('iq shape %r != (P, N, B) = %r' % (iq.shape, (self.P, self.N, self.B)))
-        if gate_cols is not None and (iq.ndim != 3 or iq.shape[0] != self.P or iq.shape[2] != self.B):
-            raise ValueError('iq shape %r: expected (P, n, B) with P=%d B=%d' % (iq.shape, self.P, self.B))
-        prm = _vcfar_params(cfar, method)
-        res, ptr = {}, {}
-        for name, dtype in (('mtd', np.complex128), ('amp', np.float64), ('flags', np.uint8), ('threshold', np.float64)):
-            if name in want:
-                res[name] = np.empty(shp, dtype, order='F')
-                ptr[name] = res[name].ctypes.data_as(ct.POINTER(ct.c_uint8 if name == 'flags' else ct.c_double))
-            else:
-                ptr[name] = None
-        total = ct.c_int64()
-
-        def call(cap, hp, maps):
-            m = ptr if maps else dict.fromkeys(ptr)
-            tail = (ct.byref(prm), m['mtd'], m['amp'], m['flags'], m['threshold'], hp, cap, ct.byref(total))
-            if gate_cols is None:
-                check(lib().rsp_process_stage2_vcfar(self.h, iqp, dt, *tail))
-            else:
-                check(lib().rsp_process_stage2_gated_vcfar(self.h, iqp, dt, iq.shape[1], _gate_cols_arg(gate_cols), *tail))
-            return total.value
-
-        res['n_hits'], hits = _with_hits(call, max(4096, self.P * self.G * self.B // 8), hits_cap, 'hits' in want)
-        if 'hits' in want:
-            res['hits'] = hits
-        return res
+        return self._stage2_detect(iq_beams, self.B, gate_cols, _vcfar_params(cfar, method), want, hits_cap,
+                                   lib().rsp_process_stage2_vcfar, lib().rsp_process_stage2_gated_vcfar)
 
     def profile_vcfar(self, cfar, method='ca', iters=20):
         """HIP-event time of k_vcfar over the B beams of the plan's last stage-2 result
@@ -619,6 +649,86 @@ class Plan:
         ms, by = (ct.c_float * 3)(), (ct.c_int64 * 3)()
         check(lib().rsp_profile_vcfar(self.h, ct.byref(prm), int(iters), ms, by))
         return {k: (ms[i], by[i]) for i, k in enumerate(('real', 'fused_all', 'fused_hits'))}
+
+    # ---- stage-1 DBF of the stage-2 path, and stage 2 on the raw cube ----------------------------
+    def dbf(self, cube, W, conj=True, out=None):
+        """The stage-2 scripts' DBF loop (rsp_dbf; include/rsp.h restates the semantics): raw
+        ``cube[m, n, c]`` of any shape [P, N, C] and weights ``W`` [B, C] (DBF_coeffs_data_C) ->
+        beams [P, N, B] complex128, ``cube[m, n, :] @ W'`` (``conj``, debug_simulated_data_processing.m:
+        166-175) or ``@ W.'`` (main_test_with_simulated_data.m:207-214).  The plan gives the device and
+        the precision only.  ``out``: a Fortran-contiguous complex128 [P, N, B] array to write into."""
+        cube = np.asarray(cube)
+        W = np.asarray(W, np.complex128)
+        if cube.ndim == 2:
+            cube = cube[:, :, None]
+        if cube.ndim != 3 or W.ndim != 2 or W.shape[1] != cube.shape[2]:
+            raise ValueError('cube %r and W %r: expected [P, N, C] and [B, C]' % (cube.shape, W.shape))
+        a, ap, dt = _complex_arg(cube)
+        P, N, C = cube.shape
+        B = W.shape[0]
+        Wcm = np.asfortranarray(W).ravel(order='F').view(np.float64)   # B x C column-major (MATLAB)
+        if out is None:
+            out = np.empty((P, N, B), np.complex128, order='F')
+        elif out.shape != (P, N, B) or out.dtype != np.complex128 or not out.flags.f_contiguous:
+            raise ValueError('out must be a Fortran-contiguous complex128 array of shape %r' % ((P, N, B),))
+        check(lib().rsp_dbf(self.h, P, N, C, B, ap, dt, _dptr(Wcm), 1 if conj else 0,
+                            out.ctypes.data_as(ct.POINTER(ct.c_double))))
+        return out
+
+    def profile_dbf(self, P, N, C, B, iters=20):
+        """HIP-event time of k_dbf alone on a [P, N, C] cube into B beams (rsp_profile_dbf):
+        {'stage', 'ms', 'bytes'}, bytes = element bytes x P N x (C + B)."""
+        ms, by = ct.c_float(), ct.c_int64()
+        check(lib().rsp_profile_dbf(self.h, int(P), int(N), int(C), int(B), int(iters), ct.byref(ms), ct.byref(by)))
+        return {'stage': 'k_dbf', 'ms': float(ms.value), 'bytes': int(by.value)}
+
+    def _raw_weights(self, W):
+        """(array kept alive, pointer) of the weights of a raw-cube call; None: the plan's own."""
+        if W is None:
+            return None, None
+        W = np.asarray(W, np.complex128)
+        if W.shape != (self.B, self.C):
+            raise ValueError('W shape %r != (B, C) = %r' % (W.shape, (self.B, self.C)))
+        Wcm = np.asfortranarray(W).ravel(order='F').view(np.float64)
+        return Wcm, _dptr(Wcm)
+
+    def process_raw_stage2(self, cube, W=None, conj=True, gate_cols=None):
+        """``process_stage2(dbf(cube, W, conj))`` in one call, bit for bit (rsp_process_raw_stage2):
+        the DBF runs inside the corner turn and the beams never reach device memory in PRT order.
+        ``cube[m, n, c]`` is the raw frame [P, N, C] (or gated, with ``gate_cols`` as
+        ``process_stage2``); ``W`` [B, C], None: the plan's DBF_coeffs_data_C.  Returns (MTD [P,G,B],
+        PC [P,G,B])."""
+        cube = np.asarray(cube)
+        a, ap, dt = _complex_arg(cube)
+        keep, wp = self._raw_weights(W)
+        mtd = np.empty((self.P, self.G, self.B), np.complex128, order='F')
+        pc = np.empty((self.P, self.G, self.B), np.complex128, order='F')
+        mo, po = mtd.ctypes.data_as(ct.POINTER(ct.c_double)), pc.ctypes.data_as(ct.POINTER(ct.c_double))
+        if gate_cols is None:
+            if cube.shape != (self.P, self.N, self.C):
+                raise ValueError('cube shape %r != (P, N, C) = %r' % (cube.shape, (self.P, self.N, self.C)))
+            ng, cols = 0, None
+        else:
+            if cube.ndim != 3 or cube.shape[0] != self.P or cube.shape[2] != self.C:
+                raise ValueError('cube shape %r: expected (P, n, C) with P=%d C=%d' % (cube.shape, self.P, self.C))
+            ng, cols = cube.shape[1], _gate_cols_arg(gate_cols)
+        check(lib().rsp_process_raw_stage2(self.h, ap, dt, ng, cols, wp, 1 if conj else 0, mo, po))
+        return mtd, pc
+
+    def process_raw_stage2_cfar(self, cube, cfar, W=None, conj=True, gate_cols=None, want=STAGE3_WANT, hits_cap=None):
+        """``process_stage2_cfar`` on the raw cube (rsp_process_raw_stage2_cfar): ``cube``, ``W``, ``conj``
+        and ``gate_cols`` as ``process_raw_stage2``, the rest as ``process_stage2_cfar``."""
+        keep, wp = self._raw_weights(W)
+        return self._stage2_detect(cube, self.C, gate_cols, _stage3_params(cfar), want, hits_cap,
+                                   lib().rsp_process_raw_stage2_cfar, raw=(wp, 1 if conj else 0))
+
+    def process_raw_stage2_vcfar(self, cube, cfar, method='ca', W=None, conj=True, gate_cols=None, want=STAGE3_WANT,
+                                 hits_cap=None):
+        """``process_stage2_vcfar`` on the raw cube (rsp_process_raw_stage2_vcfar): ``cube``, ``W``,
+        ``conj`` and ``gate_cols`` as ``process_raw_stage2``, the rest as ``process_stage2_vcfar``."""
+        keep, wp = self._raw_weights(W)
+        return self._stage2_detect(cube, self.C, gate_cols, _vcfar_params(cfar, method), want, hits_cap,
+                                   lib().rsp_process_raw_stage2_vcfar, raw=(wp, 1 if conj else 0))
 
     # ---- device-resident queue -------------------------------------------------------------
     def device_alloc(self, nbytes):
