@@ -651,6 +651,78 @@ int32_t rsp_process_raw_stage2_vcfar(rsp_plan* plan, const void* cube, int32_t d
 int32_t rsp_profile_dbf(rsp_plan* plan, int32_t P, int32_t N, int32_t C, int32_t B, int32_t iters, float* ms_out,
                         int64_t* bytes_out);
 
+/* ---- cross GOCA-CFAR as a map detector ----
+ * fun_run_goca_cfar_8 (fun_process_single_frame.m:172-223) on any real amplitude map: the only CFAR
+ * of the reference that tests along range and Doppler together, and the test K3 applies to the
+ * frame chain's pair sums.  Here it returns a dense flag map and the threshold every cell was
+ * tested against, like the two one-axis detectors above.  Per map A [P x G] (P Doppler rows,
+ * 1-based row v; G range columns, 1-based column r) and rsp_cfar_params with
+ *   rR = refCells_R >= 1, gR = guardCells_R >= 0, rV = refCells_V >= 1, gV = guardCells_V >= 0,
+ *   T_CFAR finite and > 0, hR = rR + gR, hV = rV + gV:
+ * the cells under test are r = hR + 1 .. G - hR, v = hV + 1 .. P - hV (:192-193).  For each:
+ *   lr = A(v, r - hR) + .. + A(v, r - gR - 1)      tr = A(v, r + gR + 1) + .. + A(v, r + hR)
+ *   lv = A(v - hV, r) + .. + A(v - gV - 1, r)      tv = A(v + gV + 1, r) + .. + A(v + hV, r)
+ *   each sum one rounded add per cell in ascending index order starting from +0 (k3_map_sums); no
+ *   sliding-sum updates;
+ *   complex-double plans: nR = RN(max(lr, tr) / rR), nV = RN(max(lv, tv) / rV), the correctly
+ *     rounded quotients (k3_quot's FMA form gives exactly that);
+ *   complex-single plans: nR = RN(max(lr, tr) RN(1 / rR)), nV likewise: K3's float form, part of the
+ *     definition and not an approximation of the double one;
+ *   noise = max(nR, nV); threshold = RN(T_CFAR noise); flag = A > threshold (strict, :209).
+ * T_CFAR and the amplitudes are rounded to the plan's precision first; thresholds and amplitudes
+ * leave the device widened to double.  Every other cell is never tested by the reference: its flag
+ * is 0 and its threshold +Inf (a threshold of 0 would read as "everything detects").  A map with
+ * no cell under test (G <= 2 hR or P <= 2 hV) gives all flags 0, all thresholds +Inf and no hits,
+ * whatever the halos.  The arithmetic is k3_cfar's (rsp_k3_arith.h), so on the pair-sum maps of a
+ * frame the flagged cells are the frame's detections. */
+
+/* What the detector does with a map of P rows and G columns (rsp_xcfar_describe). */
+typedef struct rsp_xcfar_info {
+    int32_t P, G;
+    int32_t hR, hV;           /* rR + gR, rV + gV: cells a window reaches along range / Doppler      */
+    int32_t max_hR, max_hV;   /* the largest halos the kernel's tile holds                           */
+    int32_t rows, cols;       /* Doppler rows and range columns one workgroup of k_xcfar resolves     */
+    int32_t row_tiles, col_tiles;   /* workgroups per map along either axis                          */
+    int32_t r0, r1, v0, v1;   /* 1-based cells under test r0..r1 x v0..v1; r0 > r1 and v0 > v1: none */
+} rsp_xcfar_info;
+
+/* The checks of the calls below, with the same refusals and messages, and the tiling they use.
+ * RSP_ERR_INVALID: refCells_R or refCells_V < 1, a negative guard, T_CFAR not finite or <= 0, P < 1
+ * or G < 1, hR beyond max_hR or hV beyond max_hV while the map has cells under test.  `info` may
+ * be NULL.  No HIP call is made. */
+int32_t rsp_xcfar_describe(int32_t P, int32_t G, const rsp_cfar_params* params, rsp_xcfar_info* info);
+
+/* The detector on host maps of any shape, with the conventions of rsp_vcfar: amp real double
+ * [P x G x n_maps] column-major, flags (uint8) and threshold (double) of the same shape, hits
+ * ordered by map, then as find() on [P x G], beam_idx = the map; every output optional.
+ * Synchronous; drains the queue first.  Refusals come before any device work. */
+int32_t rsp_xcfar(rsp_plan* plan, int32_t P, int32_t G, const double* amp, int32_t n_maps, const rsp_cfar_params* params,
+                  uint8_t* flags, double* threshold, rsp_stage3_hit* hits, int64_t hits_cap, int64_t* n_hits);
+/* rsp_process_stage2 (or its gated / raw-cube form), then the detector on |MTD_results| of all B
+ * beams without leaving the device (arguments and outputs as the _vcfar forms, every output optional). */
+int32_t rsp_process_stage2_xcfar(rsp_plan* plan, const void* iq_beams, int32_t dtype, const rsp_cfar_params* params,
+                                 double* mtd_out, double* amp_out, uint8_t* flags, double* threshold,
+                                 rsp_stage3_hit* hits, int64_t hits_cap, int64_t* n_hits);
+int32_t rsp_process_stage2_gated_xcfar(rsp_plan* plan, const void* iq_gated, int32_t dtype, int32_t n_gated,
+                                       const int32_t* cols, const rsp_cfar_params* params, double* mtd_out,
+                                       double* amp_out, uint8_t* flags, double* threshold, rsp_stage3_hit* hits,
+                                       int64_t hits_cap, int64_t* n_hits);
+int32_t rsp_process_raw_stage2_xcfar(rsp_plan* plan, const void* cube, int32_t dtype, int32_t n_gated, const int32_t* cols,
+                                     const double* W, int32_t conj, const rsp_cfar_params* params, double* mtd_out,
+                                     double* amp_out, uint8_t* flags, double* threshold, rsp_stage3_hit* hits,
+                                     int64_t hits_cap, int64_t* n_hits);
+/* The detector with the plan's own cfar_params on the pair-sum maps of the plan's last synchronous
+ * frame that asked for rsp_frame_out.cfar_maps: the maps K3 thresholded, [P x G x (B - 1)], still
+ * on the device.  flags / threshold [P x G x (B - 1)], beam_idx of a hit = the pair; every output
+ * optional.  RSP_ERR_INVALID when the plan's last synchronous frame did not ask for the maps (or
+ * there has been none), or when the plan has one beam. */
+int32_t rsp_last_cfar_threshold(rsp_plan* plan, uint8_t* flags, double* threshold, rsp_stage3_hit* hits, int64_t hits_cap,
+                                int64_t* n_hits);
+/* Device time of k_xcfar over the plan's B beams of [P x G], in the three forms and with the
+ * algorithmic bytes of rsp_profile_stage3 (the same maps, the same bytes per form). */
+int32_t rsp_profile_xcfar(rsp_plan* plan, const rsp_cfar_params* params, int32_t iters, float* ms_out,
+                          int64_t* bytes_out);
+
 /* ---- measurement ----
  * Time each device stage `iters` times on the plan's stream with HIP events.  Each launch
  * batches nf = min(n_cubes, frames_per_launch) frames taken from the device-resident

@@ -955,6 +955,61 @@ extern "C" int32_t rsp_vcfar_describe(int32_t P, int32_t G, const rsp_vcfar_para
     return RSP_OK;
 }
 
+// ---- cross GOCA-CFAR as a map detector (fsf:192-213) ----
+int rsp_xcfar_derive(int P, int G, const rsp_cfar_params* prm, XcDesc* out) {
+    if (!prm || !out) return fail(RSP_ERR_INVALID, "null argument");
+    if (P < 1 || G < 1) return fail(RSP_ERR_INVALID, "bad map shape P=%d G=%d", P, G);
+    const int rR = prm->refCells_R, gR = prm->guardCells_R, rV = prm->refCells_V, gV = prm->guardCells_V;
+    if (rR < 1) return fail(RSP_ERR_INVALID, "refCells_R must be >= 1, got %d", rR);
+    if (rV < 1) return fail(RSP_ERR_INVALID, "refCells_V must be >= 1, got %d", rV);
+    if (gR < 0) return fail(RSP_ERR_INVALID, "guardCells_R must be >= 0, got %d", gR);
+    if (gV < 0) return fail(RSP_ERR_INVALID, "guardCells_V must be >= 0, got %d", gV);
+    if (!std::isfinite(prm->T_CFAR) || prm->T_CFAR <= 0) return fail(RSP_ERR_INVALID, "T_CFAR must be finite and > 0, got %g", prm->T_CFAR);
+    const int64_t hR = (int64_t)rR + gR, hV = (int64_t)rV + gV;
+    XcDesc d{};
+    d.P = P;
+    d.G = G;
+    d.rR = rR; d.gR = gR; d.rV = rV; d.gV = gV;
+    d.T = prm->T_CFAR;
+    if (G > 2 * hR && P > 2 * hV) {   // cells under test (fsf:192-193); otherwise no tile needs a halo
+        if (hR > RSP_XC_HMAX_R)
+            return fail(RSP_ERR_INVALID, "CFAR window refCells_R + guardCells_R = %lld exceeds the kernel's tile halo %d",
+                        (long long)hR, RSP_XC_HMAX_R);
+        if (hV > RSP_XC_HMAX_V)
+            return fail(RSP_ERR_INVALID, "CFAR window refCells_V + guardCells_V = %lld exceeds the kernel's tile halo %d",
+                        (long long)hV, RSP_XC_HMAX_V);
+        d.hR = (int)hR; d.hV = (int)hV;
+        d.r0 = (int)hR; d.r1 = G - (int)hR;
+        d.v0 = (int)hV; d.v1 = P - (int)hV;
+    }
+    *out = d;
+    return RSP_OK;
+}
+
+extern "C" int32_t rsp_xcfar_describe(int32_t P, int32_t G, const rsp_cfar_params* params, rsp_xcfar_info* info) {
+    XcDesc d;
+    if (!params) return fail(RSP_ERR_INVALID, "null argument");
+    int rc = rsp_xcfar_derive(P, G, params, &d);
+    if (rc || !info) return rc;
+    const int64_t hR = (int64_t)d.rR + d.gR, hV = (int64_t)d.rV + d.gV;
+    info->P = d.P;
+    info->G = d.G;
+    info->hR = (int32_t)std::min<int64_t>(hR, INT32_MAX);
+    info->hV = (int32_t)std::min<int64_t>(hV, INT32_MAX);
+    info->max_hR = RSP_XC_HMAX_R;
+    info->max_hV = RSP_XC_HMAX_V;
+    info->rows = RSP_XC_ROWS;
+    info->cols = RSP_XC_COLS;
+    info->row_tiles = (d.P + RSP_XC_ROWS - 1) / RSP_XC_ROWS;
+    info->col_tiles = (d.G + RSP_XC_COLS - 1) / RSP_XC_COLS;
+    const bool any = d.r1 > d.r0;
+    info->r0 = any ? d.r0 + 1 : 1;   // 1-based, inclusive; first > last: none
+    info->r1 = any ? d.r1 : 0;
+    info->v0 = any ? d.v0 + 1 : 1;
+    info->v1 = any ? d.v1 : 0;
+    return RSP_OK;
+}
+
 extern "C" int32_t rsp_dbf_describe(int32_t P, int32_t N, int32_t C, int32_t B, int32_t precision, rsp_dbf_info* info) {
     int rc = rsp_dbf_check_sizes(P, N, C, B, precision);
     if (rc || !info) return rc;

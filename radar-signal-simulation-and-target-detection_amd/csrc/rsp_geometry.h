@@ -399,6 +399,33 @@ RSP_HD constexpr size_t vc_lds_bytes(int halo, size_t rs) { return (size_t)(RSP_
 // RSP_OK, or RSP_ERR_INVALID with the message set.
 int rsp_vcfar_derive(int P, int G, const rsp_vcfar_params* prm, VcDesc* out);
 
+// Cross GOCA-CFAR as a map detector (k_xcfar, rsp_xcfar.hip).  A workgroup resolves RSP_XC_ROWS
+// Doppler rows of RSP_XC_COLS range columns (4 waves, lanes across columns) from the cross its cells
+// read, held in LDS: ROWS x (COLS + 2 hR') cells, hR' = hR rounded up to 4 cells so that tile rows
+// start on a 16-byte unit of the map row, and 2 hV x COLS cells above and below.  hR <= RSP_XC_HMAX_R
+// and hV <= RSP_XC_HMAX_V is the envelope (RSP_S3_HMAX and RSP_VC_HMAX).  The tile is sized by the
+// halos in use (xc_lds_bytes): the reference's 15 / 15 takes 39 KiB in double (three workgroups per
+// CU with the hit queue), the envelope's corner 80 KiB.
+#define RSP_XC_COLS 64
+#define RSP_XC_ROWS 32
+#define RSP_XC_HMAX_R 64
+#define RSP_XC_HMAX_V 32
+struct XcDesc {          // kernel argument
+    int P, G;
+    int rR, gR, rV, gV;  // reference and guard cells along range and Doppler
+    int hR, hV;          // the tile's halos: rR + gR and rV + gV, or 0 and 0 when no cell is under test
+    int r0, r1, v0, v1;  // 0-based cells under test [r0, r1) x [v0, v1); all 0 when there are none
+    double T;            // T_CFAR
+};
+RSP_HD constexpr int xc_tile_width(int hR) { return RSP_XC_COLS + 2 * ((hR + 3) & ~3); }
+// Dynamic LDS bytes of k_xcfar's amplitude tile for reals of rs bytes
+RSP_HD constexpr size_t xc_lds_bytes(int hR, int hV, size_t rs) {
+    return ((size_t)RSP_XC_ROWS * xc_tile_width(hR) + (size_t)2 * hV * RSP_XC_COLS) * rs;
+}
+// The checks of the cross CFAR calls and the descriptor for a map of P rows and G columns.
+// RSP_OK, or RSP_ERR_INVALID with the message set.
+int rsp_xcfar_derive(int P, int G, const rsp_cfar_params* prm, XcDesc* out);
+
 // The checks of rsp_plan_create_ex that need no device and come before its device checks.
 int rsp_plan_check_args(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params* cluster,
                         const rsp_precomputed* pre, const rsp_plan_options* opt);

@@ -105,6 +105,10 @@ hipError_t launch_s3(const S3Desc& d, int prec, bool cplx, const void* in, int n
 // Doppler CA-CFAR (rsp_vcfar.hip) of n_maps maps [n_maps][P][G]: inputs and outputs as launch_s3's.
 hipError_t launch_vcfar(const VcDesc& d, int prec, bool cplx, const void* in, int n_maps, double* amp, double* thr,
                         uint8_t* flags, rsp_stage3_hit* hits, int* count, int hits_cap, hipStream_t s);
+// Cross GOCA-CFAR (rsp_xcfar.hip) of n_maps maps [n_maps][P][G]: inputs and outputs as launch_s3's;
+// `in` starts on a 16-byte boundary.
+hipError_t launch_xcfar(const XcDesc& d, int prec, bool cplx, const void* in, int n_maps, double* amp, double* thr,
+                        uint8_t* flags, rsp_stage3_hit* hits, int* count, int hits_cap, hipStream_t s);
 // Stand-alone DBF (rsp_dbf.hip): d.C channel planes x at d.pitch -> d.B beam planes y at d.opitch, both
 // complex of the precision, 16-B aligned; At = rsp_dbf_atab's table in the precision's row layout
 // (double DBF_ROWS_SPLIT, float DBF_ROWS_PAIR) as reals of the precision.

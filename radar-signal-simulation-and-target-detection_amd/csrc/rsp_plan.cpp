@@ -164,6 +164,7 @@ struct rsp_plan {
     bool band_ok = false;
     rsp_band_counters ctr{};
     bool aux_valid = false;
+    bool smap_valid = false;      // d_smap holds the pair-sum maps of the plan's last synchronous frame
     struct DevBuf {
         void* p = nullptr;
         size_t cap = 0;
@@ -654,6 +655,7 @@ int run_sync_frame(rsp_plan* p, const void* d_in, int frame_idx, rsp_frame_out* 
     int ids[1] = {frame_idx};
     std::vector<std::vector<rsp_detection>> dets;
     void* smap = nullptr;
+    p->smap_valid = false;   // rsp_last_cfar_threshold reads the maps of the last synchronous frame, if it asked for them
     if (out && out->cfar_maps && p->g.B > 1) {
         if (!p->d_smap && (rc = p->dalloc_bytes(&p->d_smap, (size_t)(p->g.B - 1) * p->g.P * p->g.G * p->rsz))) return rc;
         smap = p->d_smap;
@@ -661,6 +663,7 @@ int run_sync_frame(rsp_plan* p, const void* d_in, int frame_idx, rsp_frame_out* 
     void* rdm[1] = {L.rdm};
     if ((rc = launch_batch(p, L, in, ids, 1, smap, nullptr, out && out->rdm ? rdm : nullptr))) return rc;
     if ((rc = harvest(p, L, &dets))) return rc;
+    p->smap_valid = smap != nullptr;
     FrameResult fr = p->results.back();
     p->results.resize(nres);   // synchronous frames do not enter the queue's result list
     p->last_dets = std::move(dets[0]);
@@ -827,6 +830,14 @@ int vc_run(rsp_plan* p, const VcDesc& d, bool cplx, const void* d_in, int n_maps
                     });
 }
 
+// ... and k_xcfar
+int xc_run(rsp_plan* p, const XcDesc& d, bool cplx, const void* d_in, int n_maps, const S3Out& o) {
+    return cfar_run(p, d.P, d.G, n_maps, o,
+                    [&](double* amp, double* thr, uint8_t* flags, rsp_stage3_hit* hits, int* count, int cap, hipStream_t s) {
+                        return launch_xcfar(d, p->g.prec, cplx, d_in, n_maps, amp, thr, flags, hits, count, cap, s);
+                    });
+}
+
 int s3_fused(rsp_plan* p, const Stage2In& in, const rsp_stage3_cfar_params* prm, double* mtd_out, const S3Out& o) {
     S3Desc d;
     int rc = rsp_stage3_derive(p->g.P, p->gates, prm, &d);   // refusals before any device work
@@ -841,6 +852,14 @@ int vc_fused(rsp_plan* p, const Stage2In& in, const rsp_vcfar_params* prm, doubl
     if (rc || (rc = rsp_s3_check_cells(d.P, d.G, p->g.B)) || (rc = stage2_device(p, in))) return rc;
     if (mtd_out && (rc = rdm_out(p, p->d_aux, mtd_out))) return rc;
     return vc_run(p, d, true, p->d_aux, p->g.B, o);
+}
+
+int xc_fused(rsp_plan* p, const Stage2In& in, const rsp_cfar_params* prm, double* mtd_out, const S3Out& o) {
+    XcDesc d;
+    int rc = rsp_xcfar_derive(p->g.P, p->g.G, prm, &d);   // refusals before any device work
+    if (rc || (rc = rsp_s3_check_cells(d.P, d.G, p->g.B)) || (rc = stage2_device(p, in))) return rc;
+    if (mtd_out && (rc = rdm_out(p, p->d_aux, mtd_out))) return rc;
+    return xc_run(p, d, true, p->d_aux, p->g.B, o);
 }
 
 // The profile entries' measurement: run() once to warm up, then iters times between two events on
@@ -867,6 +886,51 @@ int time_launches(hipStream_t s, int iters, F run, float* ms_per_iter) {
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
     *ms_per_iter = ms / iters;
+    return RSP_OK;
+}
+
+// The three timed forms of a CFAR kernel over the B beams of the plan's last stage-2 result (what
+// rsp_profile_stage3 documents).  launch(cplx, in, amp, thr, flags, hits, count, cap, stream) starts the kernel.
+template <class Launch>
+int cfar_profile(rsp_plan* p, int P, int G, int iters, float* ms_out, int64_t* bytes_out, Launch launch) {
+    if (!p->aux_valid) return fail(RSP_ERR_INVALID, "no stage-2 result on the device: call rsp_process_stage2 first");
+    HIPCHK(hipSetDevice(p->device));
+    int rc;
+    if ((rc = drain_all(p))) return rc;
+    Lane& L = p->lanes[0];
+    const int B = p->g.B;
+    const size_t cells = (size_t)B * P * G, rs = p->rsz;
+    if ((rc = s3_reserve(p->s3_amp, cells * 8)) || (rc = s3_reserve(p->s3_thr, cells * 8)) ||
+        (rc = s3_reserve(p->s3_flags, cells)) || (rc = s3_reserve(p->s3_count, 16)) || (rc = s3_reserve(p->s3_in, cells * rs)) ||
+        (rc = s3_reserve(p->s3_hits, sizeof(rsp_stage3_hit) * std::min<size_t>(cells, 65536))))
+        return rc;
+    double* amp = (double*)p->s3_amp.p;
+    double* thr = (double*)p->s3_thr.p;
+    uint8_t* fl = (uint8_t*)p->s3_flags.p;
+    rsp_stage3_hit* hits = (rsp_stage3_hit*)p->s3_hits.p;
+    int* cnt = (int*)p->s3_count.p;
+    const int cap = (int)std::min<size_t>(p->s3_hits.cap / sizeof(rsp_stage3_hit), (size_t)INT32_MAX);
+    {   // the real form's input: the magnitudes the complex form writes, in the plan's precision
+        HIPCHK(hipMemsetAsync(cnt, 0, 4, L.stream));
+        HIPCHK(launch(true, p->d_aux, amp, nullptr, nullptr, nullptr, cnt, 0, L.stream));
+        HIPCHK(hipStreamSynchronize(L.stream));
+        std::vector<double> a(cells);
+        HIPCHK(hipMemcpy(a.data(), amp, cells * 8, hipMemcpyDeviceToHost));
+        if ((rc = p->put_reals(p->s3_in.p, a.data(), cells))) return rc;
+    }
+    for (int s = 0; s < 3; ++s) {
+        auto run = [&]() -> hipError_t {
+            hipError_t e = hipMemsetAsync(cnt, 0, 4, L.stream);
+            if (e != hipSuccess) return e;
+            if (s == 0) return launch(false, p->s3_in.p, nullptr, thr, fl, nullptr, cnt, 0, L.stream);
+            if (s == 1) return launch(true, p->d_aux, amp, thr, fl, nullptr, cnt, 0, L.stream);
+            return launch(true, p->d_aux, nullptr, nullptr, nullptr, hits, cnt, cap, L.stream);
+        };
+        float ms = 0;
+        if ((rc = time_launches(L.stream, iters, [&]() -> int { HIPCHK(run()); return RSP_OK; }, &ms))) return rc;
+        if (ms_out) ms_out[s] = ms;
+    }
+    if (bytes_out) rsp_stage3_bytes((int64_t)cells, (int)p->esz, bytes_out);
     return RSP_OK;
 }
 
@@ -1345,44 +1409,10 @@ int32_t rsp_profile_stage3(rsp_plan* p, const rsp_stage3_cfar_params* prm, int32
     S3Desc d;
     int rc = rsp_stage3_derive(p->g.P, p->gates, prm, &d);
     if (rc || (rc = rsp_s3_check_cells(d.P, d.G, p->g.B))) return rc;
-    if (!p->aux_valid) return fail(RSP_ERR_INVALID, "no stage-2 result on the device: call rsp_process_stage2 first");
-    HIPCHK(hipSetDevice(p->device));
-    if ((rc = drain_all(p))) return rc;
-    Lane& L = p->lanes[0];
     const int B = p->g.B;
-    const size_t cells = (size_t)B * d.P * d.G, rs = p->rsz;
-    if ((rc = s3_reserve(p->s3_amp, cells * 8)) || (rc = s3_reserve(p->s3_thr, cells * 8)) ||
-        (rc = s3_reserve(p->s3_flags, cells)) || (rc = s3_reserve(p->s3_count, 16)) || (rc = s3_reserve(p->s3_in, cells * rs)) ||
-        (rc = s3_reserve(p->s3_hits, sizeof(rsp_stage3_hit) * std::min<size_t>(cells, 65536))))
-        return rc;
-    double* amp = (double*)p->s3_amp.p;
-    double* thr = (double*)p->s3_thr.p;
-    uint8_t* fl = (uint8_t*)p->s3_flags.p;
-    rsp_stage3_hit* hits = (rsp_stage3_hit*)p->s3_hits.p;
-    int* cnt = (int*)p->s3_count.p;
-    const int cap = (int)std::min<size_t>(p->s3_hits.cap / sizeof(rsp_stage3_hit), (size_t)INT32_MAX);
-    {   // the real form's input: the magnitudes the complex form writes, in the plan's precision
-        HIPCHK(hipMemsetAsync(cnt, 0, 4, L.stream));
-        HIPCHK(launch_s3(d, p->g.prec, true, p->d_aux, B, amp, nullptr, nullptr, nullptr, cnt, 0, L.stream));
-        HIPCHK(hipStreamSynchronize(L.stream));
-        std::vector<double> a(cells);
-        HIPCHK(hipMemcpy(a.data(), amp, cells * 8, hipMemcpyDeviceToHost));
-        if ((rc = p->put_reals(p->s3_in.p, a.data(), cells))) return rc;
-    }
-    for (int s = 0; s < 3; ++s) {
-        auto run = [&]() -> hipError_t {
-            hipError_t e = hipMemsetAsync(cnt, 0, 4, L.stream);
-            if (e != hipSuccess) return e;
-            if (s == 0) return launch_s3(d, p->g.prec, false, p->s3_in.p, B, nullptr, thr, fl, nullptr, cnt, 0, L.stream);
-            if (s == 1) return launch_s3(d, p->g.prec, true, p->d_aux, B, amp, thr, fl, nullptr, cnt, 0, L.stream);
-            return launch_s3(d, p->g.prec, true, p->d_aux, B, nullptr, nullptr, nullptr, hits, cnt, cap, L.stream);
-        };
-        float ms = 0;
-        if ((rc = time_launches(L.stream, iters, [&]() -> int { HIPCHK(run()); return RSP_OK; }, &ms))) return rc;
-        if (ms_out) ms_out[s] = ms;
-    }
-    if (bytes_out) rsp_stage3_bytes((int64_t)cells, (int)p->esz, bytes_out);
-    return RSP_OK;
+    return cfar_profile(p, d.P, d.G, iters, ms_out, bytes_out,
+                        [&](bool cplx, const void* in, double* amp, double* thr, uint8_t* fl, rsp_stage3_hit* hits, int* cnt,
+                            int cap, hipStream_t st) { return launch_s3(d, p->g.prec, cplx, in, B, amp, thr, fl, hits, cnt, cap, st); });
 }
 
 int32_t rsp_vcfar(rsp_plan* p, int32_t P, int32_t G, const double* amp, int32_t n_maps, const rsp_vcfar_params* prm,
@@ -1428,44 +1458,10 @@ int32_t rsp_profile_vcfar(rsp_plan* p, const rsp_vcfar_params* prm, int32_t iter
     VcDesc d;
     int rc = rsp_vcfar_derive(p->g.P, p->g.G, prm, &d);
     if (rc || (rc = rsp_s3_check_cells(d.P, d.G, p->g.B))) return rc;
-    if (!p->aux_valid) return fail(RSP_ERR_INVALID, "no stage-2 result on the device: call rsp_process_stage2 first");
-    HIPCHK(hipSetDevice(p->device));
-    if ((rc = drain_all(p))) return rc;
-    Lane& L = p->lanes[0];
     const int B = p->g.B;
-    const size_t cells = (size_t)B * d.P * d.G, rs = p->rsz;
-    if ((rc = s3_reserve(p->s3_amp, cells * 8)) || (rc = s3_reserve(p->s3_thr, cells * 8)) ||
-        (rc = s3_reserve(p->s3_flags, cells)) || (rc = s3_reserve(p->s3_count, 16)) || (rc = s3_reserve(p->s3_in, cells * rs)) ||
-        (rc = s3_reserve(p->s3_hits, sizeof(rsp_stage3_hit) * std::min<size_t>(cells, 65536))))
-        return rc;
-    double* amp = (double*)p->s3_amp.p;
-    double* thr = (double*)p->s3_thr.p;
-    uint8_t* fl = (uint8_t*)p->s3_flags.p;
-    rsp_stage3_hit* hits = (rsp_stage3_hit*)p->s3_hits.p;
-    int* cnt = (int*)p->s3_count.p;
-    const int cap = (int)std::min<size_t>(p->s3_hits.cap / sizeof(rsp_stage3_hit), (size_t)INT32_MAX);
-    {   // the real form's input: the magnitudes the complex form writes, in the plan's precision
-        HIPCHK(hipMemsetAsync(cnt, 0, 4, L.stream));
-        HIPCHK(launch_vcfar(d, p->g.prec, true, p->d_aux, B, amp, nullptr, nullptr, nullptr, cnt, 0, L.stream));
-        HIPCHK(hipStreamSynchronize(L.stream));
-        std::vector<double> a(cells);
-        HIPCHK(hipMemcpy(a.data(), amp, cells * 8, hipMemcpyDeviceToHost));
-        if ((rc = p->put_reals(p->s3_in.p, a.data(), cells))) return rc;
-    }
-    for (int s = 0; s < 3; ++s) {
-        auto run = [&]() -> hipError_t {
-            hipError_t e = hipMemsetAsync(cnt, 0, 4, L.stream);
-            if (e != hipSuccess) return e;
-            if (s == 0) return launch_vcfar(d, p->g.prec, false, p->s3_in.p, B, nullptr, thr, fl, nullptr, cnt, 0, L.stream);
-            if (s == 1) return launch_vcfar(d, p->g.prec, true, p->d_aux, B, amp, thr, fl, nullptr, cnt, 0, L.stream);
-            return launch_vcfar(d, p->g.prec, true, p->d_aux, B, nullptr, nullptr, nullptr, hits, cnt, cap, L.stream);
-        };
-        float ms = 0;
-        if ((rc = time_launches(L.stream, iters, [&]() -> int { HIPCHK(run()); return RSP_OK; }, &ms))) return rc;
-        if (ms_out) ms_out[s] = ms;
-    }
-    if (bytes_out) rsp_stage3_bytes((int64_t)cells, (int)p->esz, bytes_out);
-    return RSP_OK;
+    return cfar_profile(p, d.P, d.G, iters, ms_out, bytes_out,
+                        [&](bool cplx, const void* in, double* amp, double* thr, uint8_t* fl, rsp_stage3_hit* hits, int* cnt,
+                            int cap, hipStream_t st) { return launch_vcfar(d, p->g.prec, cplx, in, B, amp, thr, fl, hits, cnt, cap, st); });
 }
 
 // The raw cube of a raw-cube stage-2 call as the full-PRT [P x N x C] the device takes: the caller's, or
@@ -1515,6 +1511,85 @@ int32_t rsp_process_raw_stage2_vcfar(rsp_plan* p, const void* cube, int32_t dtyp
     const void* src;
     if ((rc = raw_full_prt(p, cube, dtype, n_gated, cols, full, &src))) return rc;
     return vc_fused(p, Stage2In{src, dtype, true, W, conj}, prm, mtd_out, S3Out{amp_out, flags, threshold, hits, hits_cap, n_hits});
+}
+
+// ---- cross GOCA-CFAR as a map detector ----
+int32_t rsp_xcfar(rsp_plan* p, int32_t P, int32_t G, const double* amp, int32_t n_maps, const rsp_cfar_params* prm,
+                  uint8_t* flags, double* threshold, rsp_stage3_hit* hits, int64_t hits_cap, int64_t* n_hits) {
+    XcDesc d;
+    int rc = s3_args(p, amp, prm, hits_cap);
+    if (rc || (rc = rsp_xcfar_derive(P, G, prm, &d))) return rc;   // refusals before any device work
+    if ((rc = rsp_s3_check_cells(d.P, d.G, n_maps))) return rc;
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    // MATLAB column-major [P x G x n] -> [n][P][G] in the plan's precision
+    const size_t cells = (size_t)n_maps * d.P * d.G, rs = p->rsz;
+    std::vector<unsigned char> host(cells * rs);
+    if (rs == 8) rsp_transpose_planes(amp, d.G, d.P, n_maps, reinterpret_cast<double*>(host.data()));
+    else rsp_transpose_planes(amp, d.G, d.P, n_maps, reinterpret_cast<float*>(host.data()));
+    if ((rc = s3_reserve(p->s3_in, cells * rs))) return rc;
+    HIPCHK(hipMemcpy(p->s3_in.p, host.data(), cells * rs, hipMemcpyHostToDevice));
+    const S3Out o{nullptr, flags, threshold, hits, hits_cap, n_hits};
+    return xc_run(p, d, false, p->s3_in.p, n_maps, o);
+}
+
+int32_t rsp_process_stage2_xcfar(rsp_plan* p, const void* iq, int32_t dtype, const rsp_cfar_params* prm, double* mtd_out,
+                                 double* amp_out, uint8_t* flags, double* threshold, rsp_stage3_hit* hits, int64_t hits_cap,
+                                 int64_t* n_hits) {
+    const int rc = s3_args(p, iq, prm, hits_cap);
+    return rc ? rc : xc_fused(p, Stage2In{iq, dtype, false, nullptr, 1}, prm, mtd_out, S3Out{amp_out, flags, threshold, hits, hits_cap, n_hits});
+}
+
+int32_t rsp_process_stage2_gated_xcfar(rsp_plan* p, const void* iq, int32_t dtype, int32_t n_gated, const int32_t* cols,
+                                       const rsp_cfar_params* prm, double* mtd_out, double* amp_out, uint8_t* flags,
+                                       double* threshold, rsp_stage3_hit* hits, int64_t hits_cap, int64_t* n_hits) {
+    XcDesc d;
+    int rc = s3_args(p, iq, prm, hits_cap);
+    if (rc || (rc = rsp_xcfar_derive(p->g.P, p->g.G, prm, &d))) return rc;   // before the re-insertion's work too
+    std::vector<unsigned char> full;
+    if ((rc = rsp_stage2_regate(p->g.P, p->g.N, p->g.B, iq, dtype, n_gated, cols, full))) return rc;
+    const S3Out o{amp_out, flags, threshold, hits, hits_cap, n_hits};
+    return xc_fused(p, Stage2In{full.data(), dtype, false, nullptr, 1}, prm, mtd_out, o);
+}
+
+int32_t rsp_process_raw_stage2_xcfar(rsp_plan* p, const void* cube, int32_t dtype, int32_t n_gated, const int32_t* cols,
+                                     const double* W, int32_t conj, const rsp_cfar_params* prm, double* mtd_out,
+                                     double* amp_out, uint8_t* flags, double* threshold, rsp_stage3_hit* hits,
+                                     int64_t hits_cap, int64_t* n_hits) {
+    XcDesc d;
+    int rc = s3_args(p, cube, prm, hits_cap);
+    if (rc || (rc = rsp_xcfar_derive(p->g.P, p->g.G, prm, &d))) return rc;   // before the re-insertion's work too
+    std::vector<unsigned char> full;
+    const void* src;
+    if ((rc = raw_full_prt(p, cube, dtype, n_gated, cols, full, &src))) return rc;
+    return xc_fused(p, Stage2In{src, dtype, true, W, conj}, prm, mtd_out, S3Out{amp_out, flags, threshold, hits, hits_cap, n_hits});
+}
+
+int32_t rsp_last_cfar_threshold(rsp_plan* p, uint8_t* flags, double* threshold, rsp_stage3_hit* hits, int64_t hits_cap,
+                                int64_t* n_hits) {
+    if (!p) return fail(RSP_ERR_INVALID, "null argument");
+    if (hits_cap < 0) return fail(RSP_ERR_INVALID, "negative hits_cap");
+    if (p->g.B < 2) return fail(RSP_ERR_INVALID, "a plan with one beam has no pair-sum maps");
+    if (!p->smap_valid || !p->d_smap)
+        return fail(RSP_ERR_INVALID, "no pair-sum maps on the device: the plan's last synchronous frame did not ask for cfar_maps");
+    const rsp_cfar_params prm{p->g.refV, p->g.guardV, p->g.refR, p->g.guardR, p->g.T};
+    XcDesc d;
+    int rc = rsp_xcfar_derive(p->g.P, p->g.G, &prm, &d);
+    if (rc || (rc = rsp_s3_check_cells(d.P, d.G, p->g.B - 1))) return rc;
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    return xc_run(p, d, false, p->d_smap, p->g.B - 1, S3Out{nullptr, flags, threshold, hits, hits_cap, n_hits});
+}
+
+int32_t rsp_profile_xcfar(rsp_plan* p, const rsp_cfar_params* prm, int32_t iters, float* ms_out, int64_t* bytes_out) {
+    if (!p || !prm || iters < 1) return fail(RSP_ERR_INVALID, "bad argument");
+    XcDesc d;
+    int rc = rsp_xcfar_derive(p->g.P, p->g.G, prm, &d);
+    if (rc || (rc = rsp_s3_check_cells(d.P, d.G, p->g.B))) return rc;
+    const int B = p->g.B;
+    return cfar_profile(p, d.P, d.G, iters, ms_out, bytes_out,
+                        [&](bool cplx, const void* in, double* amp, double* thr, uint8_t* fl, rsp_stage3_hit* hits, int* cnt,
+                            int cap, hipStream_t st) { return launch_xcfar(d, p->g.prec, cplx, in, B, amp, thr, fl, hits, cnt, cap, st); });
 }
 
 // The device buffers and the kernel argument of a k_dbf launch of these sizes (already checked)

@@ -25,7 +25,7 @@ from .config import (named_config, make_config, default_cfar_params, default_clu
                      v8_2_targets, evolve_targets, V8_FIR, stage2_config, debug_v3_config,
                      debug_v2_cfar_config, v3_cfar_params)
 from .precompute import precompute
-from .plan import Plan, process_targets_multi, describe_vcfar, describe_dbf
+from .plan import Plan, process_targets_multi, describe_vcfar, describe_dbf, describe_xcfar
 from ._abi import RspError
 from .matio import load_frame, save_frame
 from .music import MusicPlan, MUSIC_1D, MusicPlan2D, MUSIC_2D
@@ -201,4 +201,22 @@ def local_cfar_detector(rdm_abs, params, device=0, precision='c128'):
     cfg, cfar, cluster, W, ang, k = named_config('plumbing')   # the plan gives the device and the precision only
     p = _plan_for(cfg, cfar, cluster, precompute(cfg, W, ang, k, V8_FIR), device, precision)
     r = p.doppler_cfar(rdm_abs, params, method='ca', want_hits=False)
+    return r['flags'].astype(bool), r['threshold']
+
+
+def goca_cfar_maps(amp, cfar_params, device=0, precision='c128'):
+    """fun_run_goca_cfar_8's cross GOCA-CFAR test (fun_process_single_frame.m:192-213) on any real
+    amplitude map: ``[detection_map, threshold_map] = goca_cfar_maps(amp, cfar_params)``.  Every cell
+    r = hR + 1 .. G - hR, v = hV + 1 .. P - hV (hR = refCells_R + guardCells_R, hV likewise) is tested
+    against T_CFAR times the greatest of its four slice means, two along range and two along Doppler,
+    with the strict ``>`` (include/rsp.h restates it); the cells the reference never tests have no
+    detection and threshold +Inf.
+
+    ``amp`` is real [P, G] (or [P, G, n]) of any shape; ``cfar_params`` has the reference's fields
+    refCells_R, guardCells_R, refCells_V, guardCells_V and T_CFAR (``default_cfar_params``).  Returns
+    (detection_map bool, threshold_map float64) of the input's shape.  'c128' computes in double like
+    MATLAB, 'c64' in K3's single-precision form (thresholds widened to double)."""
+    cfg, cfar, cluster, W, ang, k = named_config('plumbing')   # the plan gives the device and the precision only
+    p = _plan_for(cfg, cfar, cluster, precompute(cfg, W, ang, k, V8_FIR), device, precision)
+    r = p.cross_cfar(amp, cfar_params, want_hits=False)
     return r['flags'].astype(bool), r['threshold']

@@ -134,6 +134,11 @@ class VcfarInfo(ct.Structure):
                 ('rows', ct.c_int32), ('cols', ct.c_int32), ('row_tiles', ct.c_int32), ('col_tiles', ct.c_int32)]
 
 
+class XcfarInfo(ct.Structure):
+    _fields_ = [(n, ct.c_int32) for n in ('P', 'G', 'hR', 'hV', 'max_hR', 'max_hV', 'rows', 'cols', 'row_tiles',
+                                          'col_tiles', 'r0', 'r1', 'v0', 'v1')]
+
+
 class DbfInfo(ct.Structure):
     _fields_ = [(n, ct.c_int32) for n in ('positions', 'CP', 'BMAX', 'sub_tile', 'tiles_per_wave', 'waves', 'rounds',
                                           'wg_positions', 'workgroups', 'tail_positions', 'row_layout', 'pitch')]
@@ -301,6 +306,20 @@ PROTOTYPES = {
                                                     ct.POINTER(VcfarParams), _dp, _dp, _U8, _dp,
                                                     ct.POINTER(Stage3Hit), ct.c_int64, ct.POINTER(ct.c_int64)]),
     'rsp_profile_vcfar': (ct.c_int32, [_P, ct.POINTER(VcfarParams), ct.c_int32, ct.POINTER(ct.c_float),
+                                       ct.POINTER(ct.c_int64)]),
+    'rsp_xcfar_describe': (ct.c_int32, [ct.c_int32, ct.c_int32, ct.POINTER(CfarParams), ct.POINTER(XcfarInfo)]),
+    'rsp_xcfar': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, _dp, ct.c_int32, ct.POINTER(CfarParams), _U8, _dp,
+                               ct.POINTER(Stage3Hit), ct.c_int64, ct.POINTER(ct.c_int64)]),
+    'rsp_process_stage2_xcfar': (ct.c_int32, [_P, _P, ct.c_int32, ct.POINTER(CfarParams), _dp, _dp, _U8, _dp,
+                                              ct.POINTER(Stage3Hit), ct.c_int64, ct.POINTER(ct.c_int64)]),
+    'rsp_process_stage2_gated_xcfar': (ct.c_int32, [_P, _P, ct.c_int32, ct.c_int32, ct.POINTER(ct.c_int32),
+                                                    ct.POINTER(CfarParams), _dp, _dp, _U8, _dp,
+                                                    ct.POINTER(Stage3Hit), ct.c_int64, ct.POINTER(ct.c_int64)]),
+    'rsp_process_raw_stage2_xcfar': (ct.c_int32, [_P, _P, ct.c_int32, ct.c_int32, ct.POINTER(ct.c_int32), _dp, ct.c_int32,
+                                                  ct.POINTER(CfarParams), _dp, _dp, _U8, _dp,
+                                                  ct.POINTER(Stage3Hit), ct.c_int64, ct.POINTER(ct.c_int64)]),
+    'rsp_last_cfar_threshold': (ct.c_int32, [_P, _U8, _dp, ct.POINTER(Stage3Hit), ct.c_int64, ct.POINTER(ct.c_int64)]),
+    'rsp_profile_xcfar': (ct.c_int32, [_P, ct.POINTER(CfarParams), ct.c_int32, ct.POINTER(ct.c_float),
                                        ct.POINTER(ct.c_int64)]),
     'rsp_dbf_describe': (ct.c_int32, [ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, ct.POINTER(DbfInfo)]),
     'rsp_dbf_table': (ct.c_int32, [_dp, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, _dp, ct.c_int32,

@@ -268,6 +268,26 @@ def describe_vcfar(P, G, cfar, method='ca'):
     return {k: getattr(info, k) for k, _ in _abi.VcfarInfo._fields_}
 
 
+def _xcfar_params(cfar):
+    """rsp_cfar_params from the reference's cfar_params field names (v8:45-47; ``method`` is not read:
+    fun_process_single_frame has only 'GOCA')."""
+    return _abi.CfarParams(refCells_V=int(cfar['refCells_V']), guardCells_V=int(cfar['guardCells_V']),
+                           refCells_R=int(cfar['refCells_R']), guardCells_R=int(cfar['guardCells_R']),
+                           T_CFAR=float(cfar['T_CFAR']))
+
+
+def describe_xcfar(P, G, cfar):
+    """What the cross GOCA-CFAR map detector does with a map of ``P`` Doppler rows and ``G`` range
+    columns, without a device (rsp_xcfar_describe): the window's halos ``hR`` = refCells_R +
+    guardCells_R and ``hV``, the kernel's ``max_hR`` and ``max_hV``, the ``rows`` and ``cols`` of a
+    workgroup's tile, ``row_tiles``, ``col_tiles`` and the 1-based inclusive bounds ``r0``..``r1``,
+    ``v0``..``v1`` of the cells under test (r0 > r1 and v0 > v1: none).  Refusals raise RspError with
+    the code and message the CFAR calls give."""
+    prm, info = _xcfar_params(cfar), _abi.XcfarInfo()
+    check(lib().rsp_xcfar_describe(int(P), int(G), ct.byref(prm), ct.byref(info)))
+    return {k: getattr(info, k) for k, _ in _abi.XcfarInfo._fields_}
+
+
 DBF_ROW_LAYOUTS = {'split': _abi.RSP_DBF_ROWS_SPLIT, 'pair': _abi.RSP_DBF_ROWS_PAIR}
 
 
@@ -443,33 +463,40 @@ class Plan:
         check(lib().rsp_last_targets(self.h, tg, n.value, ct.byref(n)))
         return [_tgt_dict(tg[i]) for i in range(n.value)]
 
-    def _collect(self, o, bufs, dets, tg):
+    def _collect(self, o, bufs, dets, tg, want_threshold=False):
         res = {'final_targets': self.last_targets(), 'detections': self.last_detections()}
         assert len(res['detections']) == o.n_dets and len(res['final_targets']) == o.n_targets
         if 'rdm' in bufs:
             res['rdm'] = bufs['rdm']
         if 'cfar' in bufs:
             res['cfar_maps'] = bufs['cfar']
+        if want_threshold:
+            t = self.last_cfar_threshold(want_hits=False)
+            res['cfar_threshold'], res['cfar_flags'] = t['threshold'], t['flags']
         return res
 
-    def process_cube(self, cube, frame_idx=1, want_rdm=False, want_cfar=False):
+    def process_cube(self, cube, frame_idx=1, want_rdm=False, want_cfar=False, want_threshold=False):
         """S5..S11 on a noisy echo cube ``cube[m, n, c]`` (MATLAB [P x N x C]).  ``cfar_maps``
-        (want_cfar) is rdm_for_cfar_all as the device's K3 thresholds it (fsf:184-187)."""
+        (want_cfar) is rdm_for_cfar_all as the device's K3 thresholds it (fsf:184-187).
+        ``want_threshold`` implies ``want_cfar`` and adds ``cfar_threshold`` and ``cfar_flags``
+        [P, G, B - 1]: ``last_cfar_threshold`` on those maps."""
         cube = np.asarray(cube)
         if cube.shape != (self.P, self.N, self.C):
             raise ValueError('cube shape %r != (P, N, C) = %r' % (cube.shape, (self.P, self.N, self.C)))
         a, ap, dt = _complex_arg(cube)
-        o, bufs, dets, tg = self._frame_out(want_rdm, want_cfar)
+        o, bufs, dets, tg = self._frame_out(want_rdm, want_cfar or want_threshold)
         check(lib().rsp_process_cube(self.h, ap, dt, _abi.RSP_LAYOUT_PNC, int(frame_idx), ct.byref(o)))
-        return self._collect(o, bufs, dets, tg)
+        return self._collect(o, bufs, dets, tg, want_threshold)
 
-    def process_targets(self, targets, frame_idx=1, seed=20250101, p_noise=1.0, want_rdm=False, want_cfar=False):
-        """fsf:13 path: device S4 synthesis + S4.1 Philox noise + S5..S11."""
+    def process_targets(self, targets, frame_idx=1, seed=20250101, p_noise=1.0, want_rdm=False, want_cfar=False,
+                        want_threshold=False):
+        """fsf:13 path: device S4 synthesis + S4.1 Philox noise + S5..S11.  ``want_threshold`` as
+        ``process_cube``."""
         tin = self._targets_in(targets)
-        o, bufs, dets, tg = self._frame_out(want_rdm, want_cfar)
+        o, bufs, dets, tg = self._frame_out(want_rdm, want_cfar or want_threshold)
         check(lib().rsp_process_targets(self.h, tin, len(targets), int(frame_idx), int(seed), float(p_noise),
                                         ct.byref(o)))
-        return self._collect(o, bufs, dets, tg)
+        return self._collect(o, bufs, dets, tg, want_threshold)
 
     @staticmethod
     def _targets_in(targets):
@@ -650,6 +677,70 @@ class Plan:
         check(lib().rsp_profile_vcfar(self.h, ct.byref(prm), int(iters), ms, by))
         return {k: (ms[i], by[i]) for i, k in enumerate(('real', 'fused_all', 'fused_hits'))}
 
+    # ---- cross GOCA-CFAR as a map detector ------------------------------------------------------
+    def cross_cfar(self, amp, cfar, hits_cap=None, want_hits=True):
+        """fun_run_goca_cfar_8's test (fsf:192-213) on real amplitude maps ``amp`` [P, G] or [P, G, n]
+        of any shape (rsp_xcfar; include/rsp.h restates the semantics): the plan gives the device and
+        the precision.  ``cfar``: refCells_R, guardCells_R, refCells_V, guardCells_V, T_CFAR.  Returns
+        ``flags`` (uint8) and ``threshold`` (float64, +Inf where the reference tests no cell) shaped
+        like ``amp``, ``n_hits`` and ``hits``: a HIT_DTYPE array in map-then-find() order, all of them,
+        or the first ``hits_cap``."""
+        a = np.asarray(amp, np.float64)
+        shape = a.shape
+        if a.ndim == 2:
+            a = a[:, :, None]
+        if a.ndim != 3:
+            raise ValueError('amp must be [P, G] or [P, G, n], got shape %r' % (shape,))
+        P, G, n = a.shape
+        a = np.asfortranarray(a)
+        prm = _xcfar_params(cfar)
+        flags = np.empty((P, G, n), np.uint8, order='F')
+        thr = np.empty((P, G, n), np.float64, order='F')
+        fp_, tp = flags.ctypes.data_as(ct.POINTER(ct.c_uint8)), _dptr(thr)
+        total = ct.c_int64()
+
+        def call(cap, hp, maps):
+            check(lib().rsp_xcfar(self.h, P, G, _dptr(a), n, ct.byref(prm), fp_ if maps else None, tp if maps else None,
+                                  hp, cap, ct.byref(total)))
+            return total.value
+
+        n_hits, hits = _with_hits(call, max(4096, a.size // 8), hits_cap, want_hits)
+        return dict(flags=flags.reshape(shape, order='F'), threshold=thr.reshape(shape, order='F'),
+                    n_hits=n_hits, hits=hits)
+
+    def process_stage2_xcfar(self, iq_beams, cfar, gate_cols=None, want=STAGE3_WANT, hits_cap=None):
+        """process_stage2_mtd followed by the cross GOCA-CFAR on |MTD_results| of every beam, without
+        leaving the device (rsp_process_stage2_xcfar / _gated_xcfar).  ``iq_beams``, ``gate_cols``,
+        ``want`` and ``hits_cap`` as ``process_stage2_cfar``; ``cfar`` as ``cross_cfar``."""
+        return self._stage2_detect(iq_beams, self.B, gate_cols, _xcfar_params(cfar), want, hits_cap,
+                                   lib().rsp_process_stage2_xcfar, lib().rsp_process_stage2_gated_xcfar)
+
+    def last_cfar_threshold(self, hits_cap=None, want_hits=True):
+        """The threshold K3 tested every cell of the last synchronous frame against
+        (rsp_last_cfar_threshold): the cross GOCA-CFAR with the plan's own cfar_params on the pair-sum
+        maps of that frame, which must have asked for them (``want_cfar``).  Returns ``flags`` and
+        ``threshold`` [P, G, B - 1], ``n_hits`` and ``hits`` as ``cross_cfar``, beam_idx = the pair."""
+        shp = (self.P, self.G, max(self.B - 1, 1))
+        flags, thr = np.empty(shp, np.uint8, order='F'), np.empty(shp, np.float64, order='F')
+        fp_, tp = flags.ctypes.data_as(ct.POINTER(ct.c_uint8)), _dptr(thr)
+        total = ct.c_int64()
+
+        def call(cap, hp, maps):
+            check(lib().rsp_last_cfar_threshold(self.h, fp_ if maps else None, tp if maps else None, hp, cap,
+                                                ct.byref(total)))
+            return total.value
+
+        n_hits, hits = _with_hits(call, max(4096, flags.size // 8), hits_cap, want_hits)
+        return dict(flags=flags, threshold=thr, n_hits=n_hits, hits=hits)
+
+    def profile_xcfar(self, cfar, iters=20):
+        """HIP-event time of k_xcfar over the B beams of the plan's last stage-2 result
+        (rsp_profile_xcfar), in the three forms of ``profile_stage3``."""
+        prm = _xcfar_params(cfar)
+        ms, by = (ct.c_float * 3)(), (ct.c_int64 * 3)()
+        check(lib().rsp_profile_xcfar(self.h, ct.byref(prm), int(iters), ms, by))
+        return {k: (ms[i], by[i]) for i, k in enumerate(('real', 'fused_all', 'fused_hits'))}
+
     # ---- stage-1 DBF of the stage-2 path, and stage 2 on the raw cube ----------------------------
     def dbf(self, cube, W, conj=True, out=None):
         """The stage-2 scripts' DBF loop (rsp_dbf; include/rsp.h restates the semantics): raw
@@ -729,6 +820,13 @@ class Plan:
         keep, wp = self._raw_weights(W)
         return self._stage2_detect(cube, self.C, gate_cols, _vcfar_params(cfar, method), want, hits_cap,
                                    lib().rsp_process_raw_stage2_vcfar, raw=(wp, 1 if conj else 0))
+
+    def process_raw_stage2_xcfar(self, cube, cfar, W=None, conj=True, gate_cols=None, want=STAGE3_WANT, hits_cap=None):
+        """``process_stage2_xcfar`` on the raw cube (rsp_process_raw_stage2_xcfar): ``cube``, ``W``,
+        ``conj`` and ``gate_cols`` as ``process_raw_stage2``, the rest as ``process_stage2_xcfar``."""
+        keep, wp = self._raw_weights(W)
+        return self._stage2_detect(cube, self.C, gate_cols, _xcfar_params(cfar), want, hits_cap,
+                                   lib().rsp_process_raw_stage2_xcfar, raw=(wp, 1 if conj else 0))
 
     # ---- device-resident queue -------------------------------------------------------------
     def device_alloc(self, nbytes):
