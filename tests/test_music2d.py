@@ -11,7 +11,8 @@ reference).  Complex double; the tolerances are tests/test_music.py's for c128:
                  count -- exactly.  Exactness is asserted only after a precondition on the reference
                  map alone: no pixel equals its largest neighbour, and every pixel differs from its
                  largest neighbour by >= 1e-5 dB (100 x the spectrum tolerance), so that no
-                 regional-maximum decision can flip within the tolerance.
+                 regional-maximum decision can flip within the tolerance; and the M + 1 highest
+                 regional maxima differ pairwise by as much, so that neither can the top-M order.
 
 The reference (Q_n form, LAPACK eigenvectors) is computed once per case in a module fixture.
 """
@@ -21,6 +22,7 @@ import numpy as np
 import pytest
 
 import _music2d_ref as ref
+from _music2d_shapes import height_gap
 
 SEED = 20250101
 TOL = dict(X=1e-12, R=1e-12, eig=1e-11, db=1e-7)
@@ -80,12 +82,17 @@ def _expected_map(c, i):
     return m[THETA_MAP][:, PHI_MAP] if c['name'] == 'dup' else m
 
 
-def _assert_margin(m, where):
-    """The precondition of every exact peak comparison, on a reference map alone."""
+def _assert_margin(m, where, mask, M):
+    """The preconditions of every exact peak comparison, on a reference map alone: the pixel-to-
+    neighbour margin (the set of regional maxima) and the gap between the heights of the M + 1
+    highest maxima (which of them are the top M, and in what order)."""
     gap = np.abs(m - ref.largest_neighbour(m))
     print('%s: min |P_dB - largest neighbour| = %.3e dB' % (where, gap.min()))
     assert gap.min() > 0.0, '%s: a pixel equals its largest neighbour' % where
     assert gap.min() >= MARGIN_DB, '%s: margin %.3e dB' % (where, gap.min())
+    hg = height_gap(m, mask, M)
+    print('%s: min gap between the %d highest regional maxima = %.3e dB' % (where, min(M, mask.sum()) + 1, hg))
+    assert hg >= MARGIN_DB, '%s: height gap %.3e dB' % (where, hg)
 
 
 @pytest.mark.gpu
@@ -137,7 +144,7 @@ def test_peaks(case):
             assert ang == [(-60.0, 45.0), (30.0, 20.0)]
             assert c['out']['n_peaks'][i] >= M
             continue
-        _assert_margin(c['ref'][i]['spectrum_db'], '%s[%d]' % (c['name'], i))
+        _assert_margin(c['ref'][i]['spectrum_db'], '%s[%d]' % (c['name'], i), c['ref'][i]['mask'], M)
         want = _expected_map(c, i)
         mask = ref.regional_max(want)
         top = ref.top_peaks(want, mask, M)
