@@ -412,11 +412,11 @@ def det_key_set(dets):
     return {(int(d[0]), int(d[1]), int(d[2])) for d in dets}
 
 
-def device_cube(plan, targets, frame_idx=1, seed=SEED):
+def device_cube(plan, targets, frame_idx=1, seed=SEED, p_noise=1.0):
     """S4 + S4.1 synthesised on the device in the plan's precision, downloaded as [P, N, C]."""
     ptr = plan.device_alloc(plan.cube_bytes)
     try:
-        plan.synthesize_device(ptr, targets, frame_idx=frame_idx, seed=seed)
+        plan.synthesize_device(ptr, targets, frame_idx=frame_idx, seed=seed, p_noise=p_noise)
         plan.sync()
         flat = plan.device_download(ptr, plan.sizes.cube_elems, plan.cdtype)
     finally:
