@@ -651,6 +651,59 @@ int32_t rsp_process_raw_stage2_vcfar(rsp_plan* plan, const void* cube, int32_t d
 int32_t rsp_profile_dbf(rsp_plan* plan, int32_t P, int32_t N, int32_t C, int32_t B, int32_t iters, float* ms_out,
                         int64_t* bytes_out);
 
+/* ---- the MTD as a stand-alone stage: a slow-time transform of any length ----
+ * `fftshift(fft(pc .* MTD_win, nfft, 1), 1)` (main_simulate_echoes_with_array_v7_7.m:501-503 with
+ * FFTnum_MTD = 512 on 332 pulses; fun_process_single_frame.m:131-135 with nfft = prtNum) on a cube in
+ * MATLAB's own layout.  For every column (g, map) of pc [P x G x n_maps], pulse index fastest:
+ *   out[:, g, map] = shift( DFT_nfft( [pc[:, g, map] .* win ; zeros(nfft - P)] ) ),
+ * shift = MATLAB's fftshift (output row v holds frequency (v - floor(nfft / 2)) mod nfft, odd nfft
+ * included) or, shift = 0, natural order.  out is [nfft x G x n_maps].  Any 1 <= P <= nfft <=
+ * RSP_MTD_MAX_NFFT, G, n_maps >= 1; nfft = 0 means P.  The work is O(nfft log nfft) per column at
+ * every length: Stockham passes in LDS for nfft = 2^m, Bluestein's chirp-z transform over the least
+ * power of two M >= 2 nfft - 1 for every other length. */
+#define RSP_MTD_MAX_NFFT 2048
+#define RSP_MTD_ROUTE_POW2 0     /* nfft = 2^m: zero fill, 2^m-point Stockham passes            */
+#define RSP_MTD_ROUTE_CHIRPZ 1   /* chirp, M-point FFT, filter spectrum, inverse FFT, chirp     */
+#define RSP_MTD_ROUTE_DIRECT 2   /* reserved: no length takes it                                */
+
+/* How k_mtd_any covers a cube (rsp_mtd_describe). */
+typedef struct rsp_mtd_info {
+    int32_t P, G, nfft;      /* nfft as resolved (0 on input = P)                         */
+    int32_t route;           /* RSP_MTD_ROUTE_*                                           */
+    int32_t M;               /* points of the LDS transform: nfft (POW2), chirp-z M, 0    */
+    int32_t cols;            /* columns one workgroup transforms                          */
+    int32_t col_tiles;       /* workgroups per map                                        */
+    int32_t lds_bytes;       /* dynamic LDS of a workgroup                                */
+    int32_t table_elems;     /* complex entries of rsp_mtd_table: nfft + M, 0 if none     */
+} rsp_mtd_info;
+/* The size checks of rsp_mtd for one map, with the same refusals and messages, and the kernel's
+ * route and tiling, for a plan of `precision`.  RSP_ERR_INVALID: unknown precision, P < 1, G < 1,
+ * nfft < P (nfft = 0: P); RSP_ERR_UNSUPPORTED: nfft > RSP_MTD_MAX_NFFT, 2 GB or more of input or
+ * output.  `info` may be NULL.  No HIP call is made. */
+int32_t rsp_mtd_describe(int32_t P, int32_t G, int32_t nfft, int32_t precision, rsp_mtd_info* info);
+/* The chirp-z tables of length nfft as the kernel reads them: w[0 .. nfft) = exp(-i pi (m^2 mod
+ * 2 nfft) / nfft), then Bf[0 .. M), the M-point DFT of conj(w) wrapped round M (entry j and entry
+ * M - j hold conj(w[j]), j < nfft) with 1 / M folded in -- interleaved (re, im) doubles that hold the
+ * values rounded once to `precision` from a long double evaluation.  A power-of-two nfft has no
+ * tables: *n = 0.  *n = the complex entries; the first min(cap, *n) go to out.  No HIP call is made. */
+int32_t rsp_mtd_table(int32_t nfft, int32_t precision, double* out, int32_t cap, int32_t* n);
+/* pc [P x G x n_maps] (dtype RSP_C64 / RSP_C128, converted to the plan's precision as rsp_process_cube
+ * converts) -> out, complex double [nfft x G x n_maps].  win: P reals, NULL = none.  The plan gives
+ * only the device, the stream and the precision; its tables of a length are built and uploaded once.
+ * Synchronous; drains the queue first.  Refusals (sizes, dtype, null pointers, in that order) come
+ * before any device work. */
+int32_t rsp_mtd(rsp_plan* plan, int32_t P, int32_t G, int32_t n_maps, int32_t nfft, const void* pc, int32_t dtype,
+                const double* win, int32_t shift, double* out);
+/* The same on device memory in the plan's precision: d_pc [P x G x n_maps] -> d_out [nfft x G x
+ * n_maps], which must not overlap and are aligned to a complex element of the precision.  Nothing outside
+ * those nfft G n_maps elements is written. */
+int32_t rsp_mtd_device(rsp_plan* plan, int32_t P, int32_t G, int32_t n_maps, int32_t nfft, const void* d_pc,
+                       const double* win, int32_t shift, void* d_out);
+/* Device time of k_mtd_any alone on a cube of zeros, by HIP events on the plan's stream, averaged
+ * over `iters` launches; *bytes_out = element bytes x G n_maps (P + nfft). */
+int32_t rsp_profile_mtd(rsp_plan* plan, int32_t P, int32_t G, int32_t n_maps, int32_t nfft, int32_t iters,
+                        float* ms_out, int64_t* bytes_out);
+
 /* ---- cross GOCA-CFAR as a map detector ----
  * fun_run_goca_cfar_8 (fun_process_single_frame.m:172-223) on any real amplitude map: the only CFAR
  * of the reference that tests along range and Doppler together, and the test K3 applies to the

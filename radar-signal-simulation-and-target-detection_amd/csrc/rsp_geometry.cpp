@@ -607,6 +607,106 @@ DbfDesc dbf_desc(int S, int C, int B, int pitch, int opitch, int prec) {
     return DbfDesc{S, C, B, pitch, opitch, (unsigned)C * (unsigned)pitch * esz, (unsigned)B * (unsigned)opitch * esz};
 }
 
+// ---- the stand-alone MTD of any length (k_mtd_any) ----
+int rsp_mtd_check_sizes(int64_t P, int64_t G, int64_t n_maps, int64_t nfft, int precision, int* nfft_out) {
+    if (precision != RSP_C64 && precision != RSP_C128)
+        return fail(RSP_ERR_INVALID, "precision must be RSP_C128 or RSP_C64, got %d", precision);
+    if (nfft == 0) nfft = P;
+    if (P < 1 || G < 1 || n_maps < 1 || nfft < P)
+        return fail(RSP_ERR_INVALID, "bad sizes P=%lld G=%lld n_maps=%lld nfft=%lld (P, G, n_maps >= 1, nfft >= P or 0)",
+                    (long long)P, (long long)G, (long long)n_maps, (long long)nfft);
+    if (nfft > RSP_MTD_MAX_NFFT)
+        return fail(RSP_ERR_UNSUPPORTED, "nfft=%lld: a transform holds at most RSP_MTD_MAX_NFFT = %d points", (long long)nfft,
+                    RSP_MTD_MAX_NFFT);
+    // nfft >= P: the output is the larger side
+    const int64_t esz = precision == RSP_C128 ? 16 : 8, lim = (int64_t)1 << 31;
+    if (G >= lim || n_maps >= lim || G * n_maps >= lim || G * n_maps * nfft * esz >= lim)
+        return fail(RSP_ERR_UNSUPPORTED, "%lld x %lld columns of %lld points: the kernel addresses a cube of less than 2 GB",
+                    (long long)G, (long long)n_maps, (long long)nfft);
+    if (nfft_out) *nfft_out = (int)nfft;
+    return RSP_OK;
+}
+
+MtdDesc mtd_desc(int P, int G, int n_maps, int nfft, int shift, bool has_win, int prec) {
+    MtdDesc d{};
+    d.P = P;
+    d.G = G;
+    d.n_maps = n_maps;
+    d.nfft = nfft;
+    d.chirp = is_pow2(nfft) ? 0 : 1;
+    d.L = d.chirp ? mtd_chirp_len(nfft) : nfft;
+    d.lgL = ilog2i(d.L);
+    d.cols = mtd_cols(d.L, prec);
+    d.col_tiles = (G + d.cols - 1) / d.cols;
+    d.shift = shift ? 1 : 0;
+    d.has_win = has_win ? 1 : 0;
+    return d;
+}
+
+namespace {
+const long double kPiL = 3.141592653589793238462643383279502884L;
+// one rounding from the long double value to the precision, held in a double
+double round_prec(long double x, int prec) { return prec == RSP_PREC_F64 ? (double)x : (double)(float)x; }
+// In-place forward FFT of n = 2^k points in long double (radix 2, roots from one table)
+void fft_ld(std::vector<long double>& re, std::vector<long double>& im) {
+    const int n = (int)re.size();
+    std::vector<long double> rc(n / 2 + 1), rs(n / 2 + 1);
+    for (int k = 0; k < n / 2; ++k) {
+        rc[k] = cosl(-2.0L * kPiL * (long double)k / (long double)n);
+        rs[k] = sinl(-2.0L * kPiL * (long double)k / (long double)n);
+    }
+    for (int i = 1, j = 0; i < n; ++i) {
+        int bit = n >> 1;
+        for (; j & bit; bit >>= 1) j ^= bit;
+        j ^= bit;
+        if (i < j) {
+            std::swap(re[i], re[j]);
+            std::swap(im[i], im[j]);
+        }
+    }
+    for (int len = 2; len <= n; len <<= 1)
+        for (int i = 0; i < n; i += len)
+            for (int k = 0; k < len / 2; ++k) {
+                const long double wr = rc[k * (n / len)], wi = rs[k * (n / len)];
+                const int a = i + k, b = i + k + len / 2;
+                const long double vr = re[b] * wr - im[b] * wi, vi = re[b] * wi + im[b] * wr;
+                re[b] = re[a] - vr;
+                im[b] = im[a] - vi;
+                re[a] += vr;
+                im[a] += vi;
+            }
+}
+}  // namespace
+
+void rsp_mtd_tables(int nfft, int prec, std::vector<cd>& out) {
+    out.clear();
+    if (is_pow2(nfft)) return;
+    const int M = mtd_chirp_len(nfft);
+    std::vector<long double> wr(nfft), wi(nfft), br(M, 0.0L), bi(M, 0.0L);
+    for (int m = 0; m < nfft; ++m) {   // the phase as an integer mod 2 nfft before any floating point
+        const int64_t e = ((int64_t)m * m) % (2 * (int64_t)nfft);
+        const long double a = -kPiL * (long double)e / (long double)nfft;
+        wr[m] = cosl(a);
+        wi[m] = sinl(a);
+        br[m] = wr[m];   // conj(w) wrapped round M: entries m and M - m
+        bi[m] = -wi[m];
+        if (m) {
+            br[M - m] = wr[m];
+            bi[M - m] = -wi[m];
+        }
+    }
+    fft_ld(br, bi);
+    out.reserve((size_t)nfft + M);
+    for (int m = 0; m < nfft; ++m) out.push_back(cd(round_prec(wr[m], prec), round_prec(wi[m], prec)));
+    for (int k = 0; k < M; ++k) out.push_back(cd(round_prec(br[k] / (long double)M, prec), round_prec(bi[k] / (long double)M, prec)));
+}
+
+void rsp_mtd_twiddles(int lgL, std::vector<cd>& out) {
+    out.clear();
+    build_plan_twiddles(plan_pow2(lgL), out, true);
+    build_plan_twiddles(plan_rev(plan_pow2(lgL)), out, true);
+}
+
 size_t k1_tiled_lds(const Geometry& g, bool rq) {
     return ((size_t)g.B * g.NT * g.Ppad + (rq ? rq_table_elems(g.twq_elems, g.P) : g.P)) * cplx_bytes(g);
 }
@@ -1040,6 +1140,38 @@ extern "C" int32_t rsp_dbf_table(const double* W, int32_t B, int32_t C, int32_t 
     rsp_dbf_atab(W, B, C, conj, row_layout, t);
     *n = (int32_t)t.size();
     for (int i = 0; i < cap && i < (int)t.size(); ++i) out[i] = t[i];
+    return RSP_OK;
+}
+
+extern "C" int32_t rsp_mtd_describe(int32_t P, int32_t G, int32_t nfft, int32_t precision, rsp_mtd_info* info) {
+    int n = 0;
+    int rc = rsp_mtd_check_sizes(P, G, 1, nfft, precision, &n);
+    if (rc || !info) return rc;
+    const int prec = precision == RSP_C128 ? RSP_PREC_F64 : RSP_PREC_F32;
+    const MtdDesc d = mtd_desc(P, G, 1, n, 1, false, prec);
+    info->P = P;
+    info->G = G;
+    info->nfft = n;
+    info->route = d.chirp ? RSP_MTD_ROUTE_CHIRPZ : RSP_MTD_ROUTE_POW2;
+    info->M = d.L;
+    info->cols = d.cols;
+    info->col_tiles = d.col_tiles;
+    info->lds_bytes = (int32_t)mtd_lds_bytes(d.L, prec);
+    info->table_elems = d.chirp ? n + d.L : 0;
+    return RSP_OK;
+}
+
+extern "C" int32_t rsp_mtd_table(int32_t nfft, int32_t precision, double* out, int32_t cap, int32_t* n) {
+    if (!n || cap < 0 || (cap > 0 && !out)) return fail(RSP_ERR_INVALID, "null argument");
+    int rc = rsp_mtd_check_sizes(nfft, 1, 1, nfft, precision, nullptr);
+    if (rc) return rc;
+    std::vector<cd> t;
+    rsp_mtd_tables(nfft, precision == RSP_C128 ? RSP_PREC_F64 : RSP_PREC_F32, t);
+    *n = (int32_t)t.size();
+    for (int i = 0; i < cap && i < (int)t.size(); ++i) {
+        out[2 * i] = t[i].real();
+        out[2 * i + 1] = t[i].imag();
+    }
     return RSP_OK;
 }
 

@@ -305,6 +305,55 @@ int rsp_dbf_check_args(const void* plan, const void* cube, int dtype, const void
 // The kernel argument for planes at `pitch` / `opitch` elements (sizes already checked)
 DbfDesc dbf_desc(int S, int C, int B, int pitch, int opitch, int prec);
 
+// ---- the stand-alone MTD of any length (k_mtd_any, rsp_mtd.hip) ----
+// A workgroup holds `cols` columns of L points in LDS, L = nfft (a power of two) or the chirp-z
+// length M = the least power of two >= 2 nfft - 1, and transforms them with the Stockham passes of
+// PlanPow2<log2 L>, 16 points per thread.  Complex double: 1024 points, 16 KB and one wave per
+// workgroup, so that a pass's barrier costs nothing and nine workgroups share a CU's LDS; complex
+// single: 4096 points, 32 KB and four waves (measured against 2048 points in either precision,
+// profiles/mtd_prof.json and DESIGN.md section 3h).  Never more than RSP_MTD_MAX_COLS columns, so that
+// short transforms do not turn a narrow map into one workgroup; a row longer than a workgroup's points is
+// one column, up to the 4096 complex doubles (64 KB + pads) of nfft = 2047.  Rows carry K2's pad, one
+// element per 32 (RSP_K2_SH).
+#define RSP_MTD_MAX_COLS 16
+#define RSP_MTD_MAX_LG 12   // M of nfft = 2047
+RSP_HD constexpr int mtd_wg_points(int prec) { return prec == RSP_PREC_F64 ? 1024 : 4096; }
+RSP_HD constexpr int mtd_cols(int L, int prec) {
+    return mtd_wg_points(prec) / L < 1 ? 1 : (mtd_wg_points(prec) / L > RSP_MTD_MAX_COLS ? RSP_MTD_MAX_COLS : mtd_wg_points(prec) / L);
+}
+RSP_HD constexpr int mtd_threads(int L, int prec) {
+    return mtd_cols(L, prec) * L / 16 < 64 ? 64 : (mtd_cols(L, prec) * L / 16 > 256 ? 256 : mtd_cols(L, prec) * L / 16);
+}
+RSP_HD constexpr int mtd_row_stride(int L) { return k2_lds_data(L, RSP_K2_SH); }
+RSP_HD constexpr size_t mtd_lds_bytes(int L, int prec) {
+    return (size_t)mtd_cols(L, prec) * mtd_row_stride(L) * (prec == RSP_PREC_F64 ? 16 : 8);
+}
+// The chirp-z length of nfft: the least power of two >= 2 nfft - 1
+RSP_HD constexpr int mtd_chirp_len(int nfft) {
+    int M = 1;
+    while (M < 2 * nfft - 1) M *= 2;
+    return M;
+}
+struct MtdDesc {          // kernel argument
+    int P, G, n_maps, nfft;
+    int L, lgL, chirp;    // points of the LDS transform, its log2, 1 on the chirp-z route
+    int cols, col_tiles;  // columns per workgroup, workgroups per map
+    int shift, has_win;
+    int vec;              // complex single: bit 0 the loads, bit 1 the stores take element pairs (16 B)
+};
+// The checks of rsp_mtd / rsp_mtd_device / rsp_profile_mtd / rsp_mtd_describe that need no device:
+// precision, sizes (nfft = 0: P), the cap, and input and output under 2 GB.  RSP_OK and *nfft_out =
+// the resolved length, or the refusal with its message set.
+int rsp_mtd_check_sizes(int64_t P, int64_t G, int64_t n_maps, int64_t nfft, int precision, int* nfft_out);
+// The kernel argument of sizes already checked; vec is left 0 (the launcher's caller knows the pointers)
+MtdDesc mtd_desc(int P, int G, int n_maps, int nfft, int shift, bool has_win, int prec);
+// The chirp-z tables of nfft, w[0 .. nfft) | Bf[0 .. M), evaluated in long double and rounded once to
+// the precision (the doubles hold the rounded values); empty for a power of two
+void rsp_mtd_tables(int nfft, int prec, std::vector<std::complex<double>>& out);
+// The Stockham twiddles k_mtd_any reads for an L-point transform: the compact tables of
+// PlanPow2<log2 L> and then those of its reverse (the inverse passes of the chirp-z route)
+void rsp_mtd_twiddles(int lgL, std::vector<std::complex<double>>& out);
+
 // Which K1 slow-time FFTs run k1_fft_dif (the persistent and the tiled K1 agree, so their outputs
 // are bit-identical): P = 64, 128 always; P = 256 for plans of more than 8 channels (with 8, the
 // persistent K1's 8 sub-tiles of loads per wave and the DIF's registers spill: the Stockham passes)

@@ -113,6 +113,12 @@ hipError_t launch_xcfar(const XcDesc& d, int prec, bool cplx, const void* in, in
 // complex of the precision, 16-B aligned; At = rsp_dbf_atab's table in the precision's row layout
 // (double DBF_ROWS_SPLIT, float DBF_ROWS_PAIR) as reals of the precision.
 hipError_t launch_dbf(const DbfDesc& d, int prec, const void* x, const void* At, void* y, hipStream_t s);
+// Stand-alone MTD of any length (rsp_mtd.hip): pc [P x G x n_maps] -> out [nfft x G x n_maps], complex of
+// the precision; win = P reals of the precision (d.has_win), tab = rsp_mtd_tables' w | Bf (chirp-z route)
+// and tw = rsp_mtd_twiddles' tables of d.lgL, complex of the precision.  d.vec says which sides of a
+// complex-single launch are 16-byte aligned.
+hipError_t launch_mtd(const MtdDesc& d, int prec, const void* pc, const void* win, const void* tab, const void* tw,
+                      void* out, hipStream_t s);
 // Queue read-back: count record + the detections of nf frames (device stride dcap + 1 records) into
 // mapped pinned host memory (stride hcap + 1), only the records that exist.
 hipError_t launch_dets_to_host(const void* dets, int dcap, void* host, int hcap, int nf, hipStream_t s);

@@ -16,6 +16,7 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -172,6 +173,10 @@ struct rsp_plan {
     DevBuf s3_in, s3_amp, s3_thr, s3_flags, s3_hits, s3_count;
     // stand-alone DBF (rsp_dbf, rsp_profile_dbf): channel planes, beam planes and the A operands of the call
     DevBuf dbf_in, dbf_out, dbf_tab;
+    // stand-alone MTD (rsp_mtd, rsp_profile_mtd): the call's cube, result and window, and what a length
+    // needs once: the chirp-z tables w | Bf by nfft and the Stockham twiddles by log2 of the LDS transform
+    DevBuf mtd_in, mtd_out, mtd_win;
+    std::map<int, void*> mtd_tab, mtd_tw;
     // raw-cube stage 2 (rsp_process_raw_stage2*): the plan's own weights, and the A operands of the last
     // call whose W / conj were not the plan's (K1's layout; uploaded again only when they change)
     std::vector<double> h_W;
@@ -273,8 +278,11 @@ rsp_plan::~rsp_plan() {
     for (auto e : slot_free) if (e) (void)hipEventDestroy(e);
     if (up_stream) (void)hipStreamDestroy(up_stream);
     if (h_stage) (void)hipHostFree(h_stage);
-    for (DevBuf* b : {&s3_in, &s3_amp, &s3_thr, &s3_flags, &s3_hits, &s3_count, &dbf_in, &dbf_out, &dbf_tab, &raw_tab})
+    for (DevBuf* b : {&s3_in, &s3_amp, &s3_thr, &s3_flags, &s3_hits, &s3_count, &dbf_in, &dbf_out, &dbf_tab, &raw_tab, &mtd_in, &mtd_out,
+                      &mtd_win})
         if (b->p) (void)hipFree(b->p);
+    for (auto* m : {&mtd_tab, &mtd_tw})
+        for (auto& kv : *m) (void)hipFree(kv.second);
     for (void* p : dev_allocs) (void)hipFree(p);
 }
 
@@ -1652,6 +1660,137 @@ int32_t rsp_profile_dbf(rsp_plan* p, int32_t P, int32_t N, int32_t C, int32_t B,
     };
     if ((rc = time_launches(s, iters, run, ms_out))) return rc;
     if (bytes_out) *bytes_out = (int64_t)p->esz * S * (C + B);
+    return RSP_OK;
+}
+
+// The device tables of a k_mtd_any launch, built and uploaded the first time a length is seen
+static int mtd_tables(rsp_plan* p, const MtdDesc& d, const void** tab, const void** tw) {
+    typedef std::complex<double> cd;
+    *tab = *tw = nullptr;
+    auto put = [&](std::map<int, void*>& m, int key, const std::vector<cd>& h, const void** out) -> int {
+        void* q = nullptr;
+        if (hipMalloc(&q, h.size() * p->esz) != hipSuccess) return fail(RSP_ERR_NOMEM, "hipMalloc of the MTD tables failed");
+        const int rc = p->put_reals(q, reinterpret_cast<const double*>(h.data()), 2 * h.size());
+        if (rc) {
+            (void)hipFree(q);
+            return rc;
+        }
+        m[key] = q;
+        *out = q;
+        return RSP_OK;
+    };
+    int rc;
+    std::vector<cd> h;
+    if (d.chirp) {
+        auto it = p->mtd_tab.find(d.nfft);
+        if (it != p->mtd_tab.end())
+            *tab = it->second;
+        else {
+            rsp_mtd_tables(d.nfft, p->g.prec, h);
+            if ((rc = put(p->mtd_tab, d.nfft, h, tab))) return rc;
+        }
+    }
+    if (d.lgL >= 5) {   // one pass (L <= 16): no twiddles
+        auto it = p->mtd_tw.find(d.lgL);
+        if (it != p->mtd_tw.end())
+            *tw = it->second;
+        else {
+            rsp_mtd_twiddles(d.lgL, h);
+            if ((rc = put(p->mtd_tw, d.lgL, h, tw))) return rc;
+        }
+    }
+    return RSP_OK;
+}
+
+// One k_mtd_any launch on device memory of the plan's precision (sizes checked, queue drained)
+static int mtd_run(rsp_plan* p, MtdDesc d, const void* d_pc, const double* win, void* d_out, hipStream_t s) {
+    const void *tab, *tw;
+    int rc = mtd_tables(p, d, &tab, &tw);
+    if (rc) return rc;
+    if (win) {
+        if ((rc = s3_reserve(p->mtd_win, (size_t)d.P * p->rsz)) || (rc = p->put_reals(p->mtd_win.p, win, d.P))) return rc;
+    }
+    // complex single: element pairs where a column starts on 16 bytes (even length, aligned base)
+    if (p->g.prec != RSP_PREC_F64)
+        d.vec = ((d.P % 2 == 0 && (uintptr_t)d_pc % 16 == 0) ? 1 : 0) | ((d.nfft % 2 == 0 && (uintptr_t)d_out % 16 == 0) ? 2 : 0);
+    HIPCHK(launch_mtd(d, p->g.prec, d_pc, win ? p->mtd_win.p : nullptr, tab, tw, d_out, s));
+    return RSP_OK;
+}
+
+static int mtd_prec(const rsp_plan* p) { return p ? (p->g.prec == RSP_PREC_F64 ? RSP_C128 : RSP_C64) : RSP_C128; }
+
+int32_t rsp_mtd(rsp_plan* p, int32_t P, int32_t G, int32_t n_maps, int32_t nfft, const void* pc, int32_t dtype,
+                const double* win, int32_t shift, double* out) {
+    int n = 0;
+    int rc = rsp_mtd_check_sizes(P, G, n_maps, nfft, mtd_prec(p), &n);
+    if (rc) return rc;   // refusals before any device work
+    if (dtype != RSP_C64 && dtype != RSP_C128) return fail(RSP_ERR_INVALID, "unknown dtype %d", dtype);
+    if (!p || !pc || !out) return fail(RSP_ERR_INVALID, "null argument");
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    const bool f64 = p->g.prec == RSP_PREC_F64;
+    const size_t cols = (size_t)G * n_maps, nin = cols * P, nout = cols * n, esz = p->esz;
+    if ((rc = s3_reserve(p->mtd_in, nin * esz)) || (rc = s3_reserve(p->mtd_out, nout * esz))) return rc;
+    hipStream_t s = p->lanes[0].stream;
+    const void* src = pc;
+    if ((dtype == RSP_C128) != f64) {   // as upload_cube: a converting copy only when the dtypes differ
+        if ((rc = ensure_stage(p, nin * esz))) return rc;
+        rsp_convert_reals(pc, dtype, 2 * nin, p->h_stage);
+        src = p->h_stage;
+    }
+    HIPCHK(hipMemcpyAsync(p->mtd_in.p, src, nin * esz, hipMemcpyHostToDevice, s));
+    if ((rc = mtd_run(p, mtd_desc(P, G, n_maps, n, shift, win != nullptr, p->g.prec), p->mtd_in.p, win, p->mtd_out.p, s)))
+        return rc;
+    std::vector<float> nar(f64 ? 0 : 2 * nout);   // widened to double for a complex-single plan
+    HIPCHK(hipMemcpyAsync(f64 ? (void*)out : (void*)nar.data(), p->mtd_out.p, nout * esz, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));   // the caller's cube (or the staging buffer) is borrowed for the call
+    if (!f64) rsp_convert_reals(nar.data(), RSP_C64, 2 * nout, out);
+    return RSP_OK;
+}
+
+int32_t rsp_mtd_device(rsp_plan* p, int32_t P, int32_t G, int32_t n_maps, int32_t nfft, const void* d_pc,
+                       const double* win, int32_t shift, void* d_out) {
+    int n = 0;
+    int rc = rsp_mtd_check_sizes(P, G, n_maps, nfft, mtd_prec(p), &n);
+    if (rc) return rc;
+    if (!p || !d_pc || !d_out) return fail(RSP_ERR_INVALID, "null argument");
+    const size_t cols = (size_t)G * n_maps;
+    const char *a = static_cast<const char*>(d_pc), *b = static_cast<const char*>(d_out);
+    if (a < b + cols * n * p->esz && b < a + cols * P * p->esz) return fail(RSP_ERR_INVALID, "d_pc and d_out overlap");
+    if ((uintptr_t)d_pc % p->esz || (uintptr_t)d_out % p->esz)
+        return fail(RSP_ERR_INVALID, "d_pc and d_out must be aligned to a complex element (%zu bytes)", p->esz);
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    hipStream_t s = p->lanes[0].stream;
+    if ((rc = mtd_run(p, mtd_desc(P, G, n_maps, n, shift, win != nullptr, p->g.prec), d_pc, win, d_out, s))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    return RSP_OK;
+}
+
+int32_t rsp_profile_mtd(rsp_plan* p, int32_t P, int32_t G, int32_t n_maps, int32_t nfft, int32_t iters, float* ms_out,
+                        int64_t* bytes_out) {
+    if (!p || iters < 1 || !ms_out) return fail(RSP_ERR_INVALID, "bad argument");
+    int n = 0;
+    int rc = rsp_mtd_check_sizes(P, G, n_maps, nfft, mtd_prec(p), &n);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    const size_t cols = (size_t)G * n_maps;
+    if ((rc = s3_reserve(p->mtd_in, cols * P * p->esz)) || (rc = s3_reserve(p->mtd_out, cols * n * p->esz))) return rc;
+    hipStream_t s = p->lanes[0].stream;
+    HIPCHK(hipMemsetAsync(p->mtd_in.p, 0, cols * P * p->esz, s));   // zeros: the time does not depend on the values
+    const std::vector<double> win(P, 1.0);
+    MtdDesc d = mtd_desc(P, G, n_maps, n, 1, true, p->g.prec);
+    if ((rc = mtd_run(p, d, p->mtd_in.p, win.data(), p->mtd_out.p, s))) return rc;   // tables and window up, once
+    const void *tab, *tw;
+    if ((rc = mtd_tables(p, d, &tab, &tw))) return rc;
+    if (p->g.prec != RSP_PREC_F64) d.vec = (P % 2 == 0 ? 1 : 0) | (n % 2 == 0 ? 2 : 0);
+    auto run = [&]() -> int {
+        HIPCHK(launch_mtd(d, p->g.prec, p->mtd_in.p, p->mtd_win.p, tab, tw, p->mtd_out.p, s));
+        return RSP_OK;
+    };
+    if ((rc = time_launches(s, iters, run, ms_out))) return rc;
+    if (bytes_out) *bytes_out = (int64_t)p->esz * (int64_t)cols * (P + n);
     return RSP_OK;
 }
 

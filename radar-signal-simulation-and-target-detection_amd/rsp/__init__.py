@@ -9,6 +9,9 @@ Drop-in for the MATLAB reference's per-frame chain
 * ``dbf_beams(raw_iq_data, DBF_coeffs_data_C)`` / ``process_frame_stage2(raw_iq_data, angle, config,
   DBF_coeffs_data_C)`` -- the DBF loop every stage-2 script runs first
   (debug_simulated_data_processing.m:166-175), alone or fused with process_stage2_mtd
+* ``mtd_doppler(pc_results, MTD_win, nfft)`` / ``mtd_velocity_axis(v_max, nfft)`` -- the windowed,
+  zero-padded slow-time FFT of any length and its velocity axis
+  (main_simulate_echoes_with_array_v7_7.m:501-503, :190; fsf:134-135)
 * ``precompute(...)`` -- the driver's "%% 3" section (v8:79-155)
 * ``load_frame`` / ``save_frame`` -- the ``frame_sim_array_%d.mat`` load/save pair
   (main_simulate_echoes_with_array_v2.m:285, debug_simulated_data_processing_v3.m:20-22)
@@ -25,7 +28,7 @@ from .config import (named_config, make_config, default_cfar_params, default_clu
                      v8_2_targets, evolve_targets, V8_FIR, stage2_config, debug_v3_config,
                      debug_v2_cfar_config, v3_cfar_params)
 from .precompute import precompute
-from .plan import Plan, process_targets_multi, describe_vcfar, describe_dbf, describe_xcfar
+from .plan import Plan, process_targets_multi, describe_vcfar, describe_dbf, describe_xcfar, describe_mtd, mtd_table
 from ._abi import RspError
 from .matio import load_frame, save_frame
 from .music import MusicPlan, MUSIC_1D, MusicPlan2D, MUSIC_2D
@@ -137,6 +140,24 @@ def dbf_beams(raw_iq_data, DBF_coeffs_data_C, conj=True, device=0, precision='c1
     cfg, cfar, cluster, W, ang, k = named_config('plumbing')   # the plan gives the device and the precision only
     p = _plan_for(cfg, cfar, cluster, precompute(cfg, W, ang, k, V8_FIR), device, precision)
     return p.dbf(raw_iq_data, DBF_coeffs_data_C, conj=conj)
+
+
+def mtd_doppler(pc_results, MTD_win, nfft=None, device=0, precision='c128'):
+    """``rdm(:, :, b) = fftshift(fft(pc_results(:, :, b) .* MTD_win, nfft, 1), 1)`` for every beam b
+    (main_simulate_echoes_with_array_v7_7.m:501-503 with FFTnum_MTD = 512; fun_process_single_frame.m:
+    134-135 with ``nfft=None``, MATLAB's ``[]``).  ``pc_results`` is [prtNum, gates] or [prtNum, gates,
+    beam_num] of any shape, ``MTD_win`` prtNum reals (a column, as kaiser's; None: no window), ``nfft``
+    any length from prtNum to 2048, a power of two or not.  Returns complex128 [nfft, gates(,
+    beam_num)]."""
+    cfg, cfar, cluster, W, ang, k = named_config('plumbing')   # the plan gives the device and the precision only
+    p = _plan_for(cfg, cfar, cluster, precompute(cfg, W, ang, k, V8_FIR), device, precision)
+    return p.mtd(pc_results, MTD_win, nfft=nfft)
+
+
+def mtd_velocity_axis(v_max, nfft):
+    """``linspace(-v_max/2, v_max/2, nfft)`` (main_simulate_echoes_with_array_v7_7.m:190): the velocity
+    of every row of ``mtd_doppler``'s result as the reference labels them, v_max = wavelength / (2 prt)."""
+    return np.linspace(-v_max / 2.0, v_max / 2.0, int(nfft))
 
 
 def process_frame_stage2(raw_iq_data, angle, config, DBF_coeffs_data_C, conj=True, gate_cols=None,

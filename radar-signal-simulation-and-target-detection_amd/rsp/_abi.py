@@ -146,6 +146,14 @@ class DbfInfo(ct.Structure):
 
 RSP_DBF_ROWS_SPLIT, RSP_DBF_ROWS_PAIR = 0, 1
 
+
+class MtdInfo(ct.Structure):
+    _fields_ = [(n, ct.c_int32) for n in ('P', 'G', 'nfft', 'route', 'M', 'cols', 'col_tiles', 'lds_bytes', 'table_elems')]
+
+
+RSP_MTD_MAX_NFFT = 2048
+RSP_MTD_ROUTE_POW2, RSP_MTD_ROUTE_CHIRPZ, RSP_MTD_ROUTE_DIRECT = 0, 1, 2
+
 RSP_PLAN_K1_TILED = 1
 RSP_PLAN_MONOPULSE_COMPLEX = 2
 RSP_PLAN_K2_ALL_ROWS = 4
@@ -351,6 +359,12 @@ PROTOTYPES = {
                                      ct.POINTER(ct.c_int64)]),
     'rsp_cluster_detections': (ct.c_int32, [ct.POINTER(Detection), ct.c_int32, ct.POINTER(ClusterParams),
                                             ct.POINTER(Target), ct.c_int32, ct.POINTER(ct.c_int32)]),
+    'rsp_mtd_describe': (ct.c_int32, [ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, ct.POINTER(MtdInfo)]),
+    'rsp_mtd_table': (ct.c_int32, [ct.c_int32, ct.c_int32, _dp, ct.c_int32, ct.POINTER(ct.c_int32)]),
+    'rsp_mtd': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, _P, ct.c_int32, _dp, ct.c_int32, _dp]),
+    'rsp_mtd_device': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, _P, _dp, ct.c_int32, _P]),
+    'rsp_profile_mtd': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32,
+                                     ct.POINTER(ct.c_float), ct.POINTER(ct.c_int64)]),
     'rsp_device_alloc': (ct.c_int32, [_P, ct.c_int64, ct.POINTER(_P)]),
     'rsp_device_free': (ct.c_int32, [_P, _P]),
     'rsp_device_upload': (ct.c_int32, [_P, _P, _P, ct.c_int64]),

@@ -327,6 +327,42 @@ def dbf_table(W, conj=True, row_layout='split'):
                                                           out, cap, n))
 
 
+MTD_ROUTES = {_abi.RSP_MTD_ROUTE_POW2: 'pow2', _abi.RSP_MTD_ROUTE_CHIRPZ: 'chirpz', _abi.RSP_MTD_ROUTE_DIRECT: 'direct'}
+
+
+def _prec_code(precision):
+    if precision not in ('c128', 'c64'):
+        raise ValueError("precision must be 'c128' or 'c64'")
+    return _abi.RSP_C128 if precision == 'c128' else _abi.RSP_C64
+
+
+def describe_mtd(P, G, nfft=None, precision='c128'):
+    """How k_mtd_any transforms a [P, G] map to ``nfft`` rows (None: P) in a plan of ``precision``,
+    without a device (rsp_mtd_describe): ``P``, ``G``, ``nfft`` as resolved, ``route`` ('pow2' /
+    'chirpz'), ``M`` (points of the transform in LDS: nfft, or the chirp-z length), ``cols`` (columns
+    per workgroup), ``col_tiles``, ``lds_bytes`` and ``table_elems``.  Refusals raise RspError with the
+    code and message ``Plan.mtd`` gives."""
+    info = _abi.MtdInfo()
+    check(lib().rsp_mtd_describe(int(P), int(G), int(nfft or 0), _prec_code(precision), ct.byref(info)))
+    d = {k: getattr(info, k) for k, _ in _abi.MtdInfo._fields_}
+    d['route'] = MTD_ROUTES[d['route']]
+    return d
+
+
+def mtd_table(nfft, precision='c128'):
+    """The chirp-z tables of length ``nfft`` as the kernel reads them (rsp_mtd_table): ``(w, Bf)``,
+    complex128 arrays that hold the values rounded to ``precision``: w[m] = exp(-i pi (m^2 mod 2 nfft) /
+    nfft), m < nfft, and Bf, the M-point DFT of conj(w) wrapped round M, divided by M.  A power-of-two
+    ``nfft`` has none: two empty arrays."""
+    code, n = _prec_code(precision), ct.c_int32(0)
+    check(lib().rsp_mtd_table(int(nfft), code, None, 0, ct.byref(n)))
+    t = np.empty(2 * max(n.value, 1), np.float64)
+    check(lib().rsp_mtd_table(int(nfft), code, _dptr(t), n.value, ct.byref(n)))
+    t = t[:2 * n.value].view(np.complex128)
+    k = int(nfft) if n.value else 0
+    return t[:k].copy(), t[k:].copy()
+
+
 def describe_dbf_table(config, cfar_params, cluster_params, precomputed_data, precision='c128', ncu=256):
     """The A operands a plan of these arguments uploads for K1, without a device
     (rsp_plan_describe_dbf_table): as ``dbf_table(W, True, 'split')``."""
@@ -772,6 +808,53 @@ class Plan:
         ms, by = ct.c_float(), ct.c_int64()
         check(lib().rsp_profile_dbf(self.h, int(P), int(N), int(C), int(B), int(iters), ct.byref(ms), ct.byref(by)))
         return {'stage': 'k_dbf', 'ms': float(ms.value), 'bytes': int(by.value)}
+
+    # ---- the MTD as a stand-alone stage: a slow-time transform of any length ----------------------
+    @staticmethod
+    def _mtd_win(win, P):
+        if win is None:
+            return None, None
+        w = np.ascontiguousarray(np.asarray(win, np.float64).ravel())
+        if w.size != P:
+            raise ValueError('win has %d entries, the cube %d pulses' % (w.size, P))
+        return w, _dptr(w)
+
+    def mtd(self, pc, win=None, nfft=None, shift=True, out=None):
+        """``fftshift(fft(pc .* win, nfft, 1), 1)`` (rsp_mtd; v7_7:501-503, fsf:131-135): ``pc`` [P, G]
+        or [P, G, n_maps] of any shape, ``win`` P reals (None: none), ``nfft`` any length P ..
+        RSP_MTD_MAX_NFFT (None: P), ``shift`` False for natural order -> complex128 [nfft, G(, n_maps)].
+        The plan gives the device and the precision only.  ``out``: a Fortran-contiguous complex128
+        array of the result's shape to write into."""
+        pc = np.asarray(pc)
+        if pc.ndim not in (2, 3):
+            raise ValueError('pc %r: expected [P, G] or [P, G, n_maps]' % (pc.shape,))
+        a, ap, dt = _complex_arg(pc)
+        P, G = pc.shape[:2]
+        n_maps = pc.shape[2] if pc.ndim == 3 else 1
+        n = int(nfft) if nfft else P
+        wk, wp = self._mtd_win(win, P)
+        shp = (n,) + pc.shape[1:]
+        if out is None:
+            out = np.empty(shp, np.complex128, order='F')
+        elif out.shape != shp or out.dtype != np.complex128 or not out.flags.f_contiguous:
+            raise ValueError('out must be a Fortran-contiguous complex128 array of shape %r' % (shp,))
+        check(lib().rsp_mtd(self.h, P, G, n_maps, n, ap, dt, wp, 1 if shift else 0, _dptr(out)))
+        return out
+
+    def mtd_device(self, d_pc, d_out, P, G, n_maps=1, win=None, nfft=None, shift=True):
+        """The same on device memory in the plan's precision (rsp_mtd_device): ``d_pc`` [P, G, n_maps]
+        -> ``d_out`` [nfft, G, n_maps], pulse index fastest; the two must not overlap."""
+        wk, wp = self._mtd_win(win, int(P))
+        check(lib().rsp_mtd_device(self.h, int(P), int(G), int(n_maps), int(nfft or 0), ct.c_void_p(d_pc), wp,
+                                   1 if shift else 0, ct.c_void_p(d_out)))
+
+    def profile_mtd(self, P, G, n_maps=1, nfft=None, iters=20):
+        """HIP-event time of k_mtd_any alone on a [P, G, n_maps] cube of zeros (rsp_profile_mtd):
+        {'stage', 'ms', 'bytes'}, bytes = element bytes x G n_maps x (P + nfft)."""
+        ms, by = ct.c_float(), ct.c_int64()
+        check(lib().rsp_profile_mtd(self.h, int(P), int(G), int(n_maps), int(nfft or 0), int(iters), ct.byref(ms),
+                                    ct.byref(by)))
+        return {'stage': 'k_mtd_any', 'ms': float(ms.value), 'bytes': int(by.value)}
 
     def _raw_weights(self, W):
         """(array kept alive, pointer) of the weights of a raw-cube call; None: the plan's own."""
