@@ -776,6 +776,88 @@ int32_t rsp_last_cfar_threshold(rsp_plan* plan, uint8_t* flags, double* threshol
 int32_t rsp_profile_xcfar(rsp_plan* plan, const rsp_cfar_params* params, int32_t iters, float* ms_out,
                           int64_t* bytes_out);
 
+/* ---- detection on any range-Doppler cube ----
+ * fun_run_goca_cfar_8 + fun_parameter_estimation_9 + fun_cluster_stage1_10 + fun_cluster_stage2_11
+ * (fun_process_single_frame.m:172-407) as a call of their own on a complex RD cube x [V x G x B] of any
+ * shape (V Doppler rows, 1-based row v; G range cells, 1-based r; B >= 2 beams) with the caller's axes:
+ * the back end main_simulate_echoes_with_array_v7_7.m runs on its zero-padded 512-row cube (:509-...).
+ *   1. pair sums (fsf:184-187): S(v, r, pair) = RN(|x(v, r, pair)| + |x(v, r, pair + 1)|), pair = 1 .. B - 1,
+ *      magnitudes by the library's one routine (k2_pc's), one rounded add, in the plan's precision
+ *      (k_pairsum): K3's bits on K3's maps;
+ *   2. the cross GOCA-CFAR of the section above on every S(:, :, pair) with params->cfar (fsf:192-221;
+ *      k_xcfar itself);
+ *   3. S9 of every hit (fsf:237-297; k_s9, K3's arithmetic): the 5-cell windows r - 2 .. r + 2 and
+ *      v - 2 .. v + 2 clipped to the map, the not-a-knot spline sampled at 1/8 (range) and 1/4 (velocity)
+ *      cell, first maximum; Range = range_axis(r) + (rCellMax - r) deltaR, Velocity = velocity_axis(v) +
+ *      (vCellMax - v) deltaV (fsf:262, :278), Angle = (beam_angles_deg(pair) + beam_angles_deg(pair + 1)) / 2
+ *      + k_slopes_LUT(pair) ratio, ratio = (S_A - S_B) / (S_A + S_B + eps) of the two magnitudes at the
+ *      integer cell (fsf:282-290), or with monopulse = 1 real((x_A - x_B) / (x_A + x_B + eps)) of the complex
+ *      values, as RSP_PLAN_MONOPULSE_COMPLEX.  main_simulate_echoes_with_array_v7_7.m:677's variant
+ *      velocity_axis(fix(vCellMax)) is not built;
+ *   4. the detections in the reference's order (pair, then r, then v) and S10 / S11 on the host
+ *      (fsf:302-407; rsp_cluster_detections' code) with params->cluster.
+ * The plan gives only the device, the stream and the precision (rsp_process_stage2_detect excepted). */
+typedef struct rsp_detect_params {
+    rsp_cfar_params cfar;
+    rsp_cluster_params cluster;
+    const double* range_axis;      /* G                                                                */
+    const double* velocity_axis;   /* V                                                                */
+    double deltaR, deltaV;
+    const double* beam_angles_deg; /* B                                                                */
+    const double* k_slopes_LUT;    /* B - 1                                                            */
+    int32_t monopulse;             /* 0: amplitude ratio (fsf:282-290); 1: complex ratio, as
+                                      RSP_PLAN_MONOPULSE_COMPLEX                                       */
+    int32_t reserved;
+} rsp_detect_params;
+
+/* What the detector does with a cube of V x G x B (rsp_detect_describe). */
+typedef struct rsp_detect_info {
+    int32_t V, G, B;
+    int32_t n_pairs;                 /* B - 1 pair-sum maps of V x G                                    */
+    int32_t rows, cols;              /* Doppler rows and range cells of k_pairsum's tile (cube in MATLAB's
+                                        layout: the tile is transposed through LDS)                    */
+    int32_t row_tiles, col_tiles;    /* workgroups along either axis; each walks all B beams           */
+    int32_t lds_bytes;               /* LDS of a workgroup, padding included                           */
+    int32_t r0, r1, v0, v1;          /* 1-based cells under test r0..r1 x v0..v1; r0 > r1, v0 > v1: none */
+    int32_t reserved;
+    int64_t cells_under_test;        /* per pair-sum map                                               */
+    int64_t max_detections;          /* (B - 1) x cells_under_test                                     */
+} rsp_detect_info;
+
+/* The size checks of the calls below, with the same refusals and messages, for a plan of `precision`
+ * (RSP_C128 / RSP_C64).  RSP_ERR_INVALID: unknown precision, B < 2, V < 1, G < 1, every refusal of
+ * rsp_xcfar_describe for a V x G map with its message; RSP_ERR_UNSUPPORTED: 2 GB or more of cube or of
+ * pair-sum maps.  `info` may be NULL.  No HIP call is made. */
+int32_t rsp_detect_describe(int32_t V, int32_t G, int32_t B, int32_t precision, const rsp_cfar_params* params,
+                            rsp_detect_info* info);
+/* The detector on a host cube rdm [V x G x B] in MATLAB's layout (Doppler index fastest; dtype RSP_C64 /
+ * RSP_C128, converted to the plan's precision as rsp_process_cube converts).  out->cfar_maps (optional) is
+ * S, [V x G x (B - 1)]; out->dets / targets, their caps and counts behave as in rsp_process_cube, overflow
+ * rule included (every detection and target: rsp_last_detections / rsp_last_targets); out->rdm must be NULL
+ * (RSP_ERR_INVALID otherwise: the cube is the caller's).  Synchronous; drains the queue first.  Refusals
+ * (sizes, dtype, null pointers, in that order) come before any device work. */
+int32_t rsp_detect(rsp_plan* plan, int32_t V, int32_t G, int32_t B, const void* rdm, int32_t dtype,
+                   const rsp_detect_params* params, rsp_frame_out* out);
+/* The same on a device cube in the plan's precision and MATLAB's layout (rsp_mtd_device's output), aligned
+ * to a complex element.  The cube is only read. */
+int32_t rsp_detect_device(rsp_plan* plan, int32_t V, int32_t G, int32_t B, const void* d_rdm,
+                          const rsp_detect_params* params, rsp_frame_out* out);
+/* v7_7 sections 7-10: rsp_mtd (shift = 1) of pc [P x G x B] to nfft rows into a device cube, and the
+ * detector on that cube in place (V = nfft; velocity_axis has nfft entries).  out->rdm (optional) is the
+ * cube, complex double [nfft x G x B]; nothing but the requested outputs crosses to the host. */
+int32_t rsp_mtd_detect(rsp_plan* plan, int32_t P, int32_t G, int32_t B, int32_t nfft, const void* pc, int32_t dtype,
+                       const double* win, const rsp_detect_params* params, rsp_frame_out* out);
+/* rsp_process_stage2, then the detector on MTD_results without leaving the device, with the plan's own
+ * cfar_params, cluster_params, axes, angles, K-LUT and monopulse option, at nfft = P (the device's
+ * range-contiguous layout [B][P][G], read in place).  out->rdm (optional) is MTD_results [P x G x B]. */
+int32_t rsp_process_stage2_detect(rsp_plan* plan, const void* iq_beams, int32_t dtype, rsp_frame_out* out);
+/* Device times of the three stages on a deterministic test cube of V x G x B (uniform noise in the unit
+ * square, a peak of amplitude 100 in every beam at each 37th row and 101st range cell), by HIP events
+ * on the plan's stream, averaged over `iters` launches: ms_out[0] k_pairsum (MATLAB layout), [1] k_xcfar
+ * (hits only), [2] k_s9.  bytes_out[0] = cube + maps, [1] = maps, [2] = 48 x the cube's hits. */
+int32_t rsp_profile_detect(rsp_plan* plan, int32_t V, int32_t G, int32_t B, const rsp_cfar_params* params, int32_t iters,
+                           float* ms_out, int64_t* bytes_out);
+
 /* ---- measurement ----
  * Time each device stage `iters` times on the plan's stream with HIP events.  Each launch
  * batches nf = min(n_cubes, frames_per_launch) frames taken from the device-resident

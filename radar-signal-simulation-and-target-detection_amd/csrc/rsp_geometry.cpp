@@ -1100,13 +1100,60 @@ extern "C" int32_t rsp_xcfar_describe(int32_t P, int32_t G, const rsp_cfar_param
     info->max_hV = RSP_XC_HMAX_V;
     info->rows = RSP_XC_ROWS;
     info->cols = RSP_XC_COLS;
-    info->row_tiles = (d.P + RSP_XC_ROWS - 1) / RSP_XC_ROWS;
-    info->col_tiles = (d.G + RSP_XC_COLS - 1) / RSP_XC_COLS;
+    info->row_tiles = (int32_t)(((int64_t)d.P + RSP_XC_ROWS - 1) / RSP_XC_ROWS);   // 64-bit: P up to INT32_MAX
+    info->col_tiles = (int32_t)(((int64_t)d.G + RSP_XC_COLS - 1) / RSP_XC_COLS);
     const bool any = d.r1 > d.r0;
     info->r0 = any ? d.r0 + 1 : 1;   // 1-based, inclusive; first > last: none
     info->r1 = any ? d.r1 : 0;
     info->v0 = any ? d.v0 + 1 : 1;
     info->v1 = any ? d.v1 : 0;
+    return RSP_OK;
+}
+
+// ---- detection on any RD cube (k_pairsum, k_xcfar, k_s9) ----
+int rsp_detect_check_sizes(int64_t V, int64_t G, int64_t B, int precision, const rsp_cfar_params* prm, XcDesc* out) {
+    if (precision != RSP_C64 && precision != RSP_C128)
+        return fail(RSP_ERR_INVALID, "precision must be RSP_C128 or RSP_C64, got %d", precision);
+    if (B < 2) return fail(RSP_ERR_INVALID, "B=%lld: a pair sum needs at least 2 beams", (long long)B);
+    if (V < 1 || G < 1) return fail(RSP_ERR_INVALID, "bad cube shape V=%lld G=%lld B=%lld", (long long)V, (long long)G, (long long)B);
+    const int64_t lim = (int64_t)1 << 31;
+    XcDesc d;
+    int rc = rsp_xcfar_derive((int)std::min(V, lim - 1), (int)std::min(G, lim - 1), prm, &d);
+    if (rc) return rc;
+    // the cube is the larger side (B complex planes against B - 1 real ones)
+    const int64_t esz = precision == RSP_C128 ? 16 : 8;
+    if (V >= lim || G >= lim || B >= lim || V * G >= lim || V * G * B >= lim || V * G * B * esz >= lim)
+        return fail(RSP_ERR_UNSUPPORTED, "%lld x %lld x %lld cube: the kernels address a cube and its pair-sum maps of less than 2 GB each",
+                    (long long)V, (long long)G, (long long)B);
+    if ((V + RSP_XC_ROWS - 1) / RSP_XC_ROWS > 65535 || B - 1 > 65535)
+        return fail(RSP_ERR_UNSUPPORTED, "%lld Doppler rows, %lld maps: the CFAR kernel's grid holds 65535 x %d rows and 65535 maps",
+                    (long long)V, (long long)(B - 1), RSP_XC_ROWS);
+    if (out) *out = d;
+    return RSP_OK;
+}
+
+extern "C" int32_t rsp_detect_describe(int32_t V, int32_t G, int32_t B, int32_t precision, const rsp_cfar_params* params,
+                                       rsp_detect_info* info) {
+    XcDesc d;
+    int rc = rsp_detect_check_sizes(V, G, B, precision, params, &d);
+    if (rc || !info) return rc;
+    *info = rsp_detect_info{};
+    info->V = V;
+    info->G = G;
+    info->B = B;
+    info->n_pairs = B - 1;
+    info->rows = RSP_PS_ROWS;
+    info->cols = RSP_PS_COLS;
+    info->row_tiles = (V + RSP_PS_ROWS - 1) / RSP_PS_ROWS;
+    info->col_tiles = (G + RSP_PS_COLS - 1) / RSP_PS_COLS;
+    info->lds_bytes = (int32_t)ps_lds_bytes(precision == RSP_C128 ? 8 : 4);
+    const bool any = d.r1 > d.r0;
+    info->r0 = any ? d.r0 + 1 : 1;   // 1-based, inclusive; first > last: none (as rsp_xcfar_describe)
+    info->r1 = any ? d.r1 : 0;
+    info->v0 = any ? d.v0 + 1 : 1;
+    info->v1 = any ? d.v1 : 0;
+    info->cells_under_test = (int64_t)(d.r1 - d.r0) * (d.v1 - d.v0);
+    info->max_detections = (int64_t)(B - 1) * info->cells_under_test;
     return RSP_OK;
 }
 

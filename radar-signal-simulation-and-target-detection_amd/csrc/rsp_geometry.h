@@ -475,6 +475,23 @@ RSP_HD constexpr size_t xc_lds_bytes(int hR, int hV, size_t rs) {
 // RSP_OK, or RSP_ERR_INVALID with the message set.
 int rsp_xcfar_derive(int P, int G, const rsp_cfar_params* prm, XcDesc* out);
 
+// Detection on any RD cube (k_pairsum, k_s9, rsp_detect.hip).  k_pairsum on a cube in MATLAB's layout
+// [V x G x B]: a workgroup takes RSP_PS_ROWS Doppler rows of RSP_PS_COLS range cells, walks the B beams
+// and turns each beam's magnitudes through an LDS tile of ROWS rows of COLS + RSP_PS_PAD elements.
+#define RSP_PS_ROWS 64
+#define RSP_PS_COLS 64
+#define RSP_PS_PAD 1
+RSP_HD constexpr size_t ps_lds_bytes(size_t rs) { return (size_t)RSP_PS_ROWS * (RSP_PS_COLS + RSP_PS_PAD) * rs; }
+enum { DET_LAYOUT_MATLAB = 0, DET_LAYOUT_DEVICE = 1 };   // [V x G x B], Doppler index fastest | [B][V][G]
+struct DetDesc {         // kernel argument of k_pairsum and k_s9
+    int V, G, B;
+    int vec;             // k_pairsum: 1 when its 16-byte units are aligned (complex single; see the kernel)
+    int cplx;            // k_s9: 1 = the complex monopulse ratio
+};
+// The size checks of the detect calls (rsp_detect_describe's) and the CFAR descriptor of a V x G map.
+// RSP_OK, or the refusal with its message set.
+int rsp_detect_check_sizes(int64_t V, int64_t G, int64_t B, int precision, const rsp_cfar_params* prm, XcDesc* out);
+
 // The checks of rsp_plan_create_ex that need no device and come before its device checks.
 int rsp_plan_check_args(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params* cluster,
                         const rsp_precomputed* pre, const rsp_plan_options* opt);

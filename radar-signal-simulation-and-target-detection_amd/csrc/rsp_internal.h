@@ -119,6 +119,13 @@ hipError_t launch_dbf(const DbfDesc& d, int prec, const void* x, const void* At,
 // complex-single launch are 16-byte aligned.
 hipError_t launch_mtd(const MtdDesc& d, int prec, const void* pc, const void* win, const void* tab, const void* tw,
                       void* out, hipStream_t s);
+// Detection on any RD cube (rsp_detect.hip).  launch_pairsum: the complex cube x of d.V x d.G x d.B in
+// `layout` (DET_LAYOUT_*) -> the pair-sum maps S [B - 1][V][G], reals of the precision; d.vec is set here from
+// the pointers.  launch_s9: S9 of the n records `hits` of launch_xcfar on S (beam_idx = the pair) into dets[0 .. n),
+// in the list's order; k gives the axes, angles, K-LUT and cell sizes (device pointers), d.cplx the monopulse form.
+hipError_t launch_pairsum(DetDesc d, int prec, int layout, const void* x, void* S, hipStream_t s);
+hipError_t launch_s9(const DetDesc& d, int prec, int layout, const DevConsts& k, const void* x, const void* S,
+                     const rsp_stage3_hit* hits, int n, DevDet* dets, hipStream_t s);
 // Queue read-back: count record + the detections of nf frames (device stride dcap + 1 records) into
 // mapped pinned host memory (stride hcap + 1), only the records that exist.
 hipError_t launch_dets_to_host(const void* dets, int dcap, void* host, int hcap, int nf, hipStream_t s);

@@ -177,6 +177,10 @@ struct rsp_plan {
     // needs once: the chirp-z tables w | Bf by nfft and the Stockham twiddles by log2 of the LDS transform
     DevBuf mtd_in, mtd_out, mtd_win;
     std::map<int, void*> mtd_tab, mtd_tw;
+    // detection on any RD cube (rsp_detect and its compositions): the call's cube, its pair-sum maps, the
+    // S9 records of its hits, and the caller's axes, angles and K-LUT (doubles); the plan's own
+    // cluster parameters are `cl`
+    DevBuf det_in, det_smap, det_dets, det_axes;
     // raw-cube stage 2 (rsp_process_raw_stage2*): the plan's own weights, and the A operands of the last
     // call whose W / conj were not the plan's (K1's layout; uploaded again only when they change)
     std::vector<double> h_W;
@@ -279,7 +283,7 @@ rsp_plan::~rsp_plan() {
     if (up_stream) (void)hipStreamDestroy(up_stream);
     if (h_stage) (void)hipHostFree(h_stage);
     for (DevBuf* b : {&s3_in, &s3_amp, &s3_thr, &s3_flags, &s3_hits, &s3_count, &dbf_in, &dbf_out, &dbf_tab, &raw_tab, &mtd_in, &mtd_out,
-                      &mtd_win})
+                      &mtd_win, &det_in, &det_smap, &det_dets, &det_axes})
         if (b->p) (void)hipFree(b->p);
     for (auto* m : {&mtd_tab, &mtd_tw})
         for (auto& kv : *m) (void)hipFree(kv.second);
@@ -783,26 +787,24 @@ int s3_args(const rsp_plan* p, const void* in, const void* prm, int64_t hits_cap
     return RSP_OK;
 }
 
-// A CFAR kernel over n_maps device maps of P x G on lane 0's stream, then the requested outputs to
-// the host.  launch(amp, thr, flags, hits, count, cap, stream) starts the kernel with the device
-// outputs of this run (launch_s3's / launch_vcfar's trailing arguments).
+// A CFAR kernel on lane 0's stream over `cells` cells in all, with the device outputs the caller asks for
+// (amp / thr / flags: the plan's s3 buffers, already reserved) and, with `list`, the device hit list
+// p->s3_hits: count, then grow -- a run that counts more hits than the list holds grows the list to the
+// count and runs once more.  launch(amp, thr, flags, hits, count, cap, stream) starts the kernel with the
+// device outputs of this run (launch_s3's / launch_vcfar's trailing arguments).  Returns with the stream
+// idle, *total = the hits, all of them on the device when `list`.
 template <class Launch>
-int cfar_run(rsp_plan* p, int P, int G, int n_maps, const S3Out& o, Launch launch) {
+int cfar_launch_grow(rsp_plan* p, size_t cells, bool amp, bool thr, bool flags, bool list, Launch launch, int* total_out) {
     Lane& L = p->lanes[0];
-    const size_t cells = (size_t)n_maps * P * G;
     int rc;
-    if (o.amp && (rc = s3_reserve(p->s3_amp, cells * 8))) return rc;
-    if (o.thr && (rc = s3_reserve(p->s3_thr, cells * 8))) return rc;
-    if (o.flags && (rc = s3_reserve(p->s3_flags, cells))) return rc;
     if ((rc = s3_reserve(p->s3_count, 16))) return rc;
-    const bool list = o.hits && o.hits_cap > 0;
     if (list && (rc = s3_reserve(p->s3_hits, sizeof(rsp_stage3_hit) * std::min<size_t>(cells, 65536)))) return rc;
     int total = 0;
     for (int pass = 0;; ++pass) {
         const int cap = list ? (int)std::min<size_t>(p->s3_hits.cap / sizeof(rsp_stage3_hit), (size_t)INT32_MAX) : 0;
         HIPCHK(hipMemsetAsync(p->s3_count.p, 0, 4, L.stream));
-        HIPCHK(launch(o.amp ? (double*)p->s3_amp.p : nullptr, o.thr ? (double*)p->s3_thr.p : nullptr,
-                      o.flags ? (uint8_t*)p->s3_flags.p : nullptr, list ? (rsp_stage3_hit*)p->s3_hits.p : nullptr,
+        HIPCHK(launch(amp ? (double*)p->s3_amp.p : nullptr, thr ? (double*)p->s3_thr.p : nullptr,
+                      flags ? (uint8_t*)p->s3_flags.p : nullptr, list ? (rsp_stage3_hit*)p->s3_hits.p : nullptr,
                       (int*)p->s3_count.p, cap, L.stream));
         HIPCHK(hipStreamSynchronize(L.stream));
         HIPCHK(hipMemcpy(&total, p->s3_count.p, 4, hipMemcpyDeviceToHost));
@@ -810,6 +812,22 @@ int cfar_run(rsp_plan* p, int P, int G, int n_maps, const S3Out& o, Launch launc
         if (pass > 0) return fail(RSP_ERR_DEVICE, "CFAR hit count changed between two runs on the same map");
         if ((rc = s3_reserve(p->s3_hits, sizeof(rsp_stage3_hit) * (size_t)total))) return rc;   // every hit, then again
     }
+    *total_out = total;
+    return RSP_OK;
+}
+
+// A CFAR kernel over n_maps device maps of P x G on lane 0's stream (cfar_launch_grow), then the requested
+// outputs to the host.
+template <class Launch>
+int cfar_run(rsp_plan* p, int P, int G, int n_maps, const S3Out& o, Launch launch) {
+    const size_t cells = (size_t)n_maps * P * G;
+    int rc;
+    if (o.amp && (rc = s3_reserve(p->s3_amp, cells * 8))) return rc;
+    if (o.thr && (rc = s3_reserve(p->s3_thr, cells * 8))) return rc;
+    if (o.flags && (rc = s3_reserve(p->s3_flags, cells))) return rc;
+    const bool list = o.hits && o.hits_cap > 0;
+    int total = 0;
+    if ((rc = cfar_launch_grow(p, cells, o.amp != nullptr, o.thr != nullptr, o.flags != nullptr, list, launch, &total))) return rc;
     if (o.n_hits) *o.n_hits = total;
     if (o.amp && (rc = maps_to_matlab<double>(p->s3_amp.p, P, G, n_maps, o.amp))) return rc;
     if (o.thr && (rc = maps_to_matlab<double>(p->s3_thr.p, P, G, n_maps, o.thr))) return rc;
@@ -1791,6 +1809,228 @@ int32_t rsp_profile_mtd(rsp_plan* p, int32_t P, int32_t G, int32_t n_maps, int32
     };
     if ((rc = time_launches(s, iters, run, ms_out))) return rc;
     if (bytes_out) *bytes_out = (int64_t)p->esz * (int64_t)cols * (P + n);
+    return RSP_OK;
+}
+
+// ---- detection on any RD cube: k_pairsum -> k_xcfar -> k_s9 -> S10 / S11 ----
+static int det_prec(const rsp_plan* p) { return p ? (p->g.prec == RSP_PREC_F64 ? RSP_C128 : RSP_C64) : RSP_C128; }
+
+// The checks of the detect entries after the sizes: the parameter block and the outputs
+static int det_args(const rsp_plan* p, const void* in, const rsp_detect_params* prm, const rsp_frame_out* out, bool rdm_ok) {
+    if (!p || !in || !prm) return fail(RSP_ERR_INVALID, "null argument");
+    if (!prm->range_axis || !prm->velocity_axis || !prm->beam_angles_deg || !prm->k_slopes_LUT)
+        return fail(RSP_ERR_INVALID, "null argument: range_axis, velocity_axis, beam_angles_deg and k_slopes_LUT are needed");
+    if (prm->monopulse != 0 && prm->monopulse != 1) return fail(RSP_ERR_INVALID, "monopulse must be 0 or 1, got %d", prm->monopulse);
+    if (out && out->rdm && !rdm_ok) return fail(RSP_ERR_INVALID, "out->rdm must be NULL: the cube is the caller's");
+    return RSP_OK;
+}
+
+// The caller's axes (G, V), angles (B) and K-LUT (B - 1) on the device, as the DevConsts fields S9 reads
+static int det_consts(rsp_plan* p, int V, int G, int B, const rsp_detect_params* prm, DevConsts* k) {
+    std::vector<double> h;
+    h.reserve((size_t)G + V + 2 * B);
+    h.insert(h.end(), prm->range_axis, prm->range_axis + G);
+    h.insert(h.end(), prm->velocity_axis, prm->velocity_axis + V);
+    h.insert(h.end(), prm->beam_angles_deg, prm->beam_angles_deg + B);
+    h.insert(h.end(), prm->k_slopes_LUT, prm->k_slopes_LUT + (B - 1));
+    int rc = s3_reserve(p->det_axes, h.size() * sizeof(double));
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(p->det_axes.p, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    const double* d = static_cast<const double*>(p->det_axes.p);
+    *k = DevConsts{};
+    k->range_axis = d;
+    k->velocity_axis = d + G;
+    k->beam_angles = d + G + V;
+    k->klut = d + G + V + B;
+    k->deltaR = prm->deltaR;
+    k->deltaV = prm->deltaV;
+    return RSP_OK;
+}
+
+// The device half on a cube of xd.P x xd.G x B in `layout` on lane 0's stream: the pair-sum maps into
+// p->det_smap, k_xcfar's hit list (cfar_launch_grow) in p->s3_hits, their S9 records in p->det_dets, in
+// the list's order.  Returns with the stream idle and *n_hits set.
+static int det_device(rsp_plan* p, const XcDesc& xd, int B, int layout, const void* d_x, const DevConsts& k, int cplx,
+                      int* n_hits) {
+    Lane& L = p->lanes[0];
+    const int V = xd.P, G = xd.G, np = B - 1, prec = p->g.prec;
+    const size_t cells = (size_t)np * V * G;
+    int rc;
+    if ((rc = s3_reserve(p->det_smap, cells * p->rsz))) return rc;
+    const DetDesc dd{V, G, B, 0, cplx};
+    HIPCHK(launch_pairsum(dd, prec, layout, d_x, p->det_smap.p, L.stream));
+    const void* smap = p->det_smap.p;
+    rc = cfar_launch_grow(p, cells, false, false, false, true,
+                          [&](double* amp, double* thr, uint8_t* flags, rsp_stage3_hit* hits, int* count, int cap, hipStream_t s) {
+                              return launch_xcfar(xd, prec, false, smap, np, amp, thr, flags, hits, count, cap, s);
+                          }, n_hits);
+    if (rc || *n_hits == 0) return rc;
+    if ((rc = s3_reserve(p->det_dets, sizeof(DevDet) * (size_t)*n_hits))) return rc;
+    HIPCHK(launch_s9(dd, prec, layout, k, d_x, smap, (const rsp_stage3_hit*)p->s3_hits.p, *n_hits, (DevDet*)p->det_dets.p, L.stream));
+    HIPCHK(hipStreamSynchronize(L.stream));
+    return RSP_OK;
+}
+
+// ... and the host half: the records in the reference's order, S10 / S11, the caller's outputs as
+// run_sync_frame fills them (rdm excepted: the entry's)
+static int det_run(rsp_plan* p, const XcDesc& xd, int B, int layout, const void* d_x, const DevConsts& k, int cplx,
+                   const rsp_cluster_params& cl, rsp_frame_out* out) {
+    int n = 0;
+    int rc = det_device(p, xd, B, layout, d_x, k, cplx, &n);
+    if (rc) return rc;
+    static_assert(sizeof(DevDet) == sizeof(rsp_detection), "layout");
+    std::vector<rsp_detection> dets((size_t)n);
+    if (n) HIPCHK(hipMemcpy(dets.data(), p->det_dets.p, sizeof(DevDet) * (size_t)n, hipMemcpyDeviceToHost));
+    std::vector<rsp_target> tg;
+    rsp_cluster_frame(cl, dets, tg);   // sorts into fsf's find order (pair, r, v) first
+    p->last_dets = std::move(dets);
+    p->last_targets = tg;
+    if (!out) return RSP_OK;
+    const int nt = (int)tg.size(), nd = (int)p->last_dets.size();
+    const int rt = rsp_capped_copy(out->targets, tg.data(), nt, out->targets_cap, &out->n_targets,
+                                   "%d targets exceed targets_cap %d (all of them: rsp_last_targets)", nt, out->targets_cap);
+    const int rd = rsp_capped_copy(out->dets, p->last_dets.data(), nd, out->dets_cap, &out->n_dets,
+                                   "%d detections exceed dets_cap %d (all of them: rsp_last_detections)", nd, out->dets_cap);
+    if (out->cfar_maps) {
+        rc = p->g.prec == RSP_PREC_F64 ? maps_to_matlab<double>(p->det_smap.p, xd.P, xd.G, B - 1, out->cfar_maps)
+                                       : maps_to_matlab<float>(p->det_smap.p, xd.P, xd.G, B - 1, out->cfar_maps);
+        if (rc) return rc;
+    }
+    return rd ? rd : rt;
+}
+
+// A host cube of `elems` complex values into buf in the plan's precision, on stream s (borrowed until the sync)
+static int det_upload(rsp_plan* p, rsp_plan::DevBuf& buf, const void* src, int dtype, size_t elems, hipStream_t s) {
+    int rc = s3_reserve(buf, elems * p->esz);
+    if (rc) return rc;
+    if ((dtype == RSP_C128) != (p->g.prec == RSP_PREC_F64)) {   // as upload_cube: a converting copy only when the dtypes differ
+        if ((rc = ensure_stage(p, elems * p->esz))) return rc;
+        rsp_convert_reals(src, dtype, 2 * elems, p->h_stage);
+        src = p->h_stage;
+    }
+    HIPCHK(hipMemcpyAsync(buf.p, src, elems * p->esz, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return RSP_OK;
+}
+
+int32_t rsp_detect(rsp_plan* p, int32_t V, int32_t G, int32_t B, const void* rdm, int32_t dtype,
+                   const rsp_detect_params* prm, rsp_frame_out* out) {
+    XcDesc xd;
+    int rc = rsp_detect_check_sizes(V, G, B, det_prec(p), prm ? &prm->cfar : nullptr, &xd);
+    if (rc) return rc;   // refusals before any device work
+    if (dtype != RSP_C64 && dtype != RSP_C128) return fail(RSP_ERR_INVALID, "unknown dtype %d", dtype);
+    if ((rc = det_args(p, rdm, prm, out, false))) return rc;
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    DevConsts k;
+    if ((rc = det_consts(p, V, G, B, prm, &k))) return rc;
+    if ((rc = det_upload(p, p->det_in, rdm, dtype, (size_t)V * G * B, p->lanes[0].stream))) return rc;
+    return det_run(p, xd, B, DET_LAYOUT_MATLAB, p->det_in.p, k, prm->monopulse, prm->cluster, out);
+}
+
+int32_t rsp_detect_device(rsp_plan* p, int32_t V, int32_t G, int32_t B, const void* d_rdm, const rsp_detect_params* prm,
+                          rsp_frame_out* out) {
+    XcDesc xd;
+    int rc = rsp_detect_check_sizes(V, G, B, det_prec(p), prm ? &prm->cfar : nullptr, &xd);
+    if (rc || (rc = det_args(p, d_rdm, prm, out, false))) return rc;
+    if ((uintptr_t)d_rdm % p->esz) return fail(RSP_ERR_INVALID, "d_rdm must be aligned to a complex element (%zu bytes)", p->esz);
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    DevConsts k;
+    if ((rc = det_consts(p, V, G, B, prm, &k))) return rc;
+    return det_run(p, xd, B, DET_LAYOUT_MATLAB, d_rdm, k, prm->monopulse, prm->cluster, out);
+}
+
+int32_t rsp_mtd_detect(rsp_plan* p, int32_t P, int32_t G, int32_t B, int32_t nfft, const void* pc, int32_t dtype,
+                       const double* win, const rsp_detect_params* prm, rsp_frame_out* out) {
+    int n = 0;
+    XcDesc xd;
+    int rc = rsp_mtd_check_sizes(P, G, B, nfft, det_prec(p), &n);
+    if (rc || (rc = rsp_detect_check_sizes(n, G, B, det_prec(p), prm ? &prm->cfar : nullptr, &xd))) return rc;
+    if (dtype != RSP_C64 && dtype != RSP_C128) return fail(RSP_ERR_INVALID, "unknown dtype %d", dtype);
+    if ((rc = det_args(p, pc, prm, out, true))) return rc;
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    hipStream_t s = p->lanes[0].stream;
+    const size_t nout = (size_t)G * B * n;
+    DevConsts k;
+    if ((rc = det_consts(p, n, G, B, prm, &k)) || (rc = s3_reserve(p->mtd_out, nout * p->esz))) return rc;
+    if ((rc = det_upload(p, p->mtd_in, pc, dtype, (size_t)G * B * P, s))) return rc;
+    if ((rc = mtd_run(p, mtd_desc(P, G, B, n, 1, win != nullptr, p->g.prec), p->mtd_in.p, win, p->mtd_out.p, s))) return rc;
+    const int rr = det_run(p, xd, B, DET_LAYOUT_MATLAB, p->mtd_out.p, k, prm->monopulse, prm->cluster, out);
+    if (rr && rr != RSP_ERR_OVERFLOW) return rr;
+    if (out && out->rdm) {   // the cube, widened to double for a complex-single plan
+        const bool f64 = p->g.prec == RSP_PREC_F64;
+        std::vector<float> nar(f64 ? 0 : 2 * nout);
+        HIPCHK(hipMemcpy(f64 ? (void*)out->rdm : (void*)nar.data(), p->mtd_out.p, nout * p->esz, hipMemcpyDeviceToHost));
+        if (!f64) rsp_convert_reals(nar.data(), RSP_C64, 2 * nout, out->rdm);
+    }
+    return rr;
+}
+
+int32_t rsp_process_stage2_detect(rsp_plan* p, const void* iq, int32_t dtype, rsp_frame_out* out) {
+    if (!p || !iq) return fail(RSP_ERR_INVALID, "null argument");
+    const rsp_cfar_params prm{p->g.refV, p->g.guardV, p->g.refR, p->g.guardR, p->g.T};
+    XcDesc xd;
+    int rc = rsp_detect_check_sizes(p->g.P, p->g.G, p->g.B, det_prec(p), &prm, &xd);   // refusals before any device work
+    if (rc || (rc = stage2_device(p, iq, dtype))) return rc;
+    const int rr = det_run(p, xd, p->g.B, DET_LAYOUT_DEVICE, p->d_aux, p->k, p->g.mono_c ? 1 : 0, p->cl, out);
+    if (rr && rr != RSP_ERR_OVERFLOW) return rr;
+    if (out && out->rdm && (rc = rdm_out(p, p->d_aux, out->rdm))) return rc;
+    return rr;
+}
+
+int32_t rsp_profile_detect(rsp_plan* p, int32_t V, int32_t G, int32_t B, const rsp_cfar_params* prm, int32_t iters,
+                           float* ms_out, int64_t* bytes_out) {
+    if (!p || !prm || iters < 1 || !ms_out) return fail(RSP_ERR_INVALID, "bad argument");
+    XcDesc xd;
+    int rc = rsp_detect_check_sizes(V, G, B, det_prec(p), prm, &xd);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    Lane& L = p->lanes[0];
+    const size_t elems = (size_t)V * G * B, cells = (size_t)V * G * (B - 1);
+    {   // the test cube rsp.h describes, in the plan's precision
+        std::vector<float> h(2 * elems);
+        uint32_t st = 0x9E3779B9u;
+        for (size_t i = 0; i < 2 * elems; ++i) {
+            st = st * 1664525u + 1013904223u;   // Numerical Recipes' LCG
+            h[i] = (float)(st >> 8) * (1.0f / 16777216.0f);
+        }
+        for (int b = 0; b < B; ++b)
+            for (int g = 50; g < G; g += 101)
+                for (int v = 18; v < V; v += 37) h[2 * ((size_t)v + (size_t)V * (g + (size_t)G * b))] = 100.0f;
+        if ((rc = det_upload(p, p->det_in, h.data(), RSP_C64, elems, L.stream))) return rc;
+    }
+    const std::vector<double> ax((size_t)std::max(std::max(V, G), B), 0.0);
+    rsp_detect_params dp{};
+    dp.range_axis = dp.velocity_axis = dp.beam_angles_deg = dp.k_slopes_LUT = ax.data();
+    DevConsts k;
+    if ((rc = det_consts(p, V, G, B, &dp, &k))) return rc;
+    int n = 0;
+    if ((rc = det_device(p, xd, B, DET_LAYOUT_MATLAB, p->det_in.p, k, 0, &n))) return rc;   // buffers sized, hits on the device
+    const DetDesc dd{V, G, B, 0, 0};
+    const int prec = p->g.prec, cap = (int)std::min<size_t>(p->s3_hits.cap / sizeof(rsp_stage3_hit), (size_t)INT32_MAX);
+    for (int s = 0; s < 3; ++s) {
+        auto run = [&]() -> int {
+            if (s == 0) HIPCHK(launch_pairsum(dd, prec, DET_LAYOUT_MATLAB, p->det_in.p, p->det_smap.p, L.stream));
+            if (s == 1) {
+                HIPCHK(hipMemsetAsync(p->s3_count.p, 0, 4, L.stream));
+                HIPCHK(launch_xcfar(xd, prec, false, p->det_smap.p, B - 1, nullptr, nullptr, nullptr, (rsp_stage3_hit*)p->s3_hits.p,
+                                    (int*)p->s3_count.p, cap, L.stream));
+            }
+            if (s == 2)
+                HIPCHK(launch_s9(dd, prec, DET_LAYOUT_MATLAB, k, p->det_in.p, p->det_smap.p, (const rsp_stage3_hit*)p->s3_hits.p, n,
+                                 (DevDet*)p->det_dets.p, L.stream));
+            return RSP_OK;
+        };
+        if ((rc = time_launches(L.stream, iters, run, &ms_out[s]))) return rc;
+    }
+    if (bytes_out) {
+        bytes_out[0] = (int64_t)(elems * p->esz + cells * p->rsz);
+        bytes_out[1] = (int64_t)(cells * p->rsz);
+        bytes_out[2] = (int64_t)sizeof(DevDet) * n;
+    }
     return RSP_OK;
 }
 

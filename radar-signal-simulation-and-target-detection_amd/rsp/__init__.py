@@ -12,6 +12,10 @@ Drop-in for the MATLAB reference's per-frame chain
 * ``mtd_doppler(pc_results, MTD_win, nfft)`` / ``mtd_velocity_axis(v_max, nfft)`` -- the windowed,
   zero-padded slow-time FFT of any length and its velocity axis
   (main_simulate_echoes_with_array_v7_7.m:501-503, :190; fsf:134-135)
+* ``detect_rdm(rdm_13beam, cfar_params, cluster_params, precomputed_data)`` / ``mtd_detect(pc_results,
+  MTD_win, nfft, ...)`` -- fun_run_goca_cfar_8, fun_parameter_estimation_9 and the two clustering stages
+  (fsf:172-407) on a range-Doppler cube of any shape, alone or behind the zero-padded MTD
+  (main_simulate_echoes_with_array_v7_7.m:501-...)
 * ``precompute(...)`` -- the driver's "%% 3" section (v8:79-155)
 * ``load_frame`` / ``save_frame`` -- the ``frame_sim_array_%d.mat`` load/save pair
   (main_simulate_echoes_with_array_v2.m:285, debug_simulated_data_processing_v3.m:20-22)
@@ -28,7 +32,8 @@ from .config import (named_config, make_config, default_cfar_params, default_clu
                      v8_2_targets, evolve_targets, V8_FIR, stage2_config, debug_v3_config,
                      debug_v2_cfar_config, v3_cfar_params)
 from .precompute import precompute
-from .plan import Plan, process_targets_multi, describe_vcfar, describe_dbf, describe_xcfar, describe_mtd, mtd_table
+from .plan import (Plan, process_targets_multi, describe_vcfar, describe_dbf, describe_xcfar, describe_mtd, mtd_table,
+                   describe_detect)
 from ._abi import RspError
 from .matio import load_frame, save_frame
 from .music import MusicPlan, MUSIC_1D, MusicPlan2D, MUSIC_2D
@@ -158,6 +163,54 @@ def mtd_velocity_axis(v_max, nfft):
     """``linspace(-v_max/2, v_max/2, nfft)`` (main_simulate_echoes_with_array_v7_7.m:190): the velocity
     of every row of ``mtd_doppler``'s result as the reference labels them, v_max = wavelength / (2 prt)."""
     return np.linspace(-v_max / 2.0, v_max / 2.0, int(nfft))
+
+
+def _plumbing_plan(device, precision, monopulse='amplitude'):
+    """A plan that gives the device and the precision only (and, for S9, the monopulse form)."""
+    cfg, cfar, cluster, W, ang, k = named_config('plumbing')
+    if monopulse == 'amplitude':
+        return _plan_for(cfg, cfar, cluster, precompute(cfg, W, ang, k, V8_FIR), device, precision)
+    key = ('plumbing', monopulse, device, precision)
+    p = _PLANS.pop(key, None)
+    if p is None:
+        p = Plan(cfg, cfar, cluster, precompute(cfg, W, ang, k, V8_FIR), device=device, precision=precision, monopulse=monopulse)
+        while len(_PLANS) >= _MAX_PLANS:
+            _PLANS.popitem(last=False)[1].close()
+    _PLANS[key] = p
+    return p
+
+
+def detect_rdm(rdm_13beam, cfar_params, cluster_params, precomputed_data, monopulse='amplitude', device=0, precision='c128',
+               want_cfar=False):
+    """fun_process_single_frame.m S8-S11 on a given range-Doppler cube: ``fun_run_goca_cfar_8(rdm_13beam,
+    cfar_params)``, ``fun_parameter_estimation_9``, ``fun_cluster_stage1_10`` and ``fun_cluster_stage2_11``
+    (fsf:172-407).  ``rdm_13beam`` is complex [V, G, B] of any shape, B >= 2; ``precomputed_data`` gives
+    ``range_axis`` (G), ``velocity_axis`` (V), ``deltaR``, ``deltaV``, ``beam_angles_deg`` (B) and
+    ``k_slopes_LUT`` (B - 1).  ``monopulse`` 'complex': the angle from the complex ratio
+    (main_plot_snr_vs_angle_error.m:455-462).  Returns a dict: ``final_targets``, ``detections`` (the
+    parameterised detections in the reference's order) and, with ``want_cfar``, ``cfar_maps``
+    (rdm_for_cfar_all, [V, G, B - 1])."""
+    pre = precomputed_data
+    p = _plumbing_plan(device, precision, monopulse)
+    return p.detect(rdm_13beam, cfar_params, cluster_params, pre['range_axis'], pre['velocity_axis'], pre['deltaR'],
+                    pre['deltaV'], pre['beam_angles_deg'], pre['k_slopes_LUT'], monopulse, want_cfar=want_cfar)
+
+
+def mtd_detect(pc_results, MTD_win, nfft, cfar_params, cluster_params, precomputed_data, velocity_axis=None, v_max=None,
+               monopulse='amplitude', device=0, precision='c128', want_rdm=False, want_cfar=False):
+    """main_simulate_echoes_with_array_v7_7.m sections 7-10 from the pulse-compression results on:
+    ``mtd_doppler(pc_results, MTD_win, nfft)`` and ``detect_rdm`` on its result, without the cube leaving
+    the device.  ``velocity_axis`` (nfft entries) defaults to ``mtd_velocity_axis(v_max, nfft)`` when
+    ``v_max`` is given (v7_7:190), else to ``precomputed_data['velocity_axis']``; the other axes and
+    parameters as ``detect_rdm``.  ``want_rdm`` adds the cube ``rdm`` [nfft, G, B]."""
+    pre = precomputed_data
+    n = int(nfft) if nfft else np.asarray(pc_results).shape[0]
+    if velocity_axis is None:
+        velocity_axis = mtd_velocity_axis(v_max, n) if v_max is not None else pre['velocity_axis']
+    p = _plumbing_plan(device, precision, monopulse)
+    return p.mtd_detect(pc_results, MTD_win, n, cfar_params, cluster_params, pre['range_axis'], velocity_axis,
+                        pre['deltaR'], pre['deltaV'], pre['beam_angles_deg'], pre['k_slopes_LUT'], monopulse,
+                        want_rdm=want_rdm, want_cfar=want_cfar)
 
 
 def process_frame_stage2(raw_iq_data, angle, config, DBF_coeffs_data_C, conj=True, gate_cols=None,

@@ -151,6 +151,18 @@ class MtdInfo(ct.Structure):
     _fields_ = [(n, ct.c_int32) for n in ('P', 'G', 'nfft', 'route', 'M', 'cols', 'col_tiles', 'lds_bytes', 'table_elems')]
 
 
+class DetectParams(ct.Structure):
+    _fields_ = [('cfar', CfarParams), ('cluster', ClusterParams), ('range_axis', _dp), ('velocity_axis', _dp),
+                ('deltaR', ct.c_double), ('deltaV', ct.c_double), ('beam_angles_deg', _dp), ('k_slopes_LUT', _dp),
+                ('monopulse', ct.c_int32), ('reserved', ct.c_int32)]
+
+
+class DetectInfo(ct.Structure):
+    _fields_ = [(n, ct.c_int32) for n in ('V', 'G', 'B', 'n_pairs', 'rows', 'cols', 'row_tiles', 'col_tiles', 'lds_bytes',
+                                          'r0', 'r1', 'v0', 'v1', 'reserved')] + \
+               [('cells_under_test', ct.c_int64), ('max_detections', ct.c_int64)]
+
+
 RSP_MTD_MAX_NFFT = 2048
 RSP_MTD_ROUTE_POW2, RSP_MTD_ROUTE_CHIRPZ, RSP_MTD_ROUTE_DIRECT = 0, 1, 2
 
@@ -365,6 +377,17 @@ PROTOTYPES = {
     'rsp_mtd_device': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, _P, _dp, ct.c_int32, _P]),
     'rsp_profile_mtd': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32,
                                      ct.POINTER(ct.c_float), ct.POINTER(ct.c_int64)]),
+    'rsp_detect_describe': (ct.c_int32, [ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, ct.POINTER(CfarParams),
+                                         ct.POINTER(DetectInfo)]),
+    'rsp_detect': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, _P, ct.c_int32, ct.POINTER(DetectParams),
+                                ct.POINTER(FrameOut)]),
+    'rsp_detect_device': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, _P, ct.POINTER(DetectParams),
+                                       ct.POINTER(FrameOut)]),
+    'rsp_mtd_detect': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, _P, ct.c_int32, _dp,
+                                    ct.POINTER(DetectParams), ct.POINTER(FrameOut)]),
+    'rsp_process_stage2_detect': (ct.c_int32, [_P, _P, ct.c_int32, ct.POINTER(FrameOut)]),
+    'rsp_profile_detect': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, ct.POINTER(CfarParams), ct.c_int32,
+                                        ct.POINTER(ct.c_float), ct.POINTER(ct.c_int64)]),
     'rsp_device_alloc': (ct.c_int32, [_P, ct.c_int64, ct.POINTER(_P)]),
     'rsp_device_free': (ct.c_int32, [_P, _P]),
     'rsp_device_upload': (ct.c_int32, [_P, _P, _P, ct.c_int64]),

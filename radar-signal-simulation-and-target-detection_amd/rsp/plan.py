@@ -288,6 +288,18 @@ def describe_xcfar(P, G, cfar):
     return {k: getattr(info, k) for k, _ in _abi.XcfarInfo._fields_}
 
 
+def describe_detect(V, G, B, cfar, precision='c128'):
+    """What the detector on an RD cube does with ``V`` Doppler rows, ``G`` range cells and ``B`` beams in
+    a plan of ``precision``, without a device (rsp_detect_describe): ``n_pairs`` = B - 1 pair-sum maps, the
+    ``rows`` x ``cols`` tile of k_pairsum (cube in MATLAB's layout), ``row_tiles``, ``col_tiles``, its
+    ``lds_bytes``, the 1-based inclusive bounds ``r0``..``r1``, ``v0``..``v1`` of the cells under test
+    (r0 > r1 and v0 > v1: none), ``cells_under_test`` per map and ``max_detections``.  Refusals raise
+    RspError with the code and message ``Plan.detect`` gives."""
+    prm, info = _xcfar_params(cfar), _abi.DetectInfo()
+    check(lib().rsp_detect_describe(int(V), int(G), int(B), _prec_code(precision), ct.byref(prm), ct.byref(info)))
+    return {k: getattr(info, k) for k, _ in _abi.DetectInfo._fields_ if k != 'reserved'}
+
+
 DBF_ROW_LAYOUTS = {'split': _abi.RSP_DBF_ROWS_SPLIT, 'pair': _abi.RSP_DBF_ROWS_PAIR}
 
 
@@ -391,6 +403,8 @@ class Plan:
     def __init__(self, config, cfar_params, cluster_params, precomputed_data, device=0, frames_per_launch=1,
                  precision='c128', k1_tiled=False, monopulse='amplitude', k2_all_rows=False):
         self.config = config
+        self.cfar_params, self.cluster_params, self.precomputed_data = cfar_params, cluster_params, precomputed_data
+        self.monopulse = monopulse
         self._keep = []
         self.cfg, self.cfar, self.cluster, self.pre = _marshal(config, cfar_params, cluster_params, precomputed_data,
                                                                self._keep)
@@ -855,6 +869,135 @@ class Plan:
         check(lib().rsp_profile_mtd(self.h, int(P), int(G), int(n_maps), int(nfft or 0), int(iters), ct.byref(ms),
                                     ct.byref(by)))
         return {'stage': 'k_mtd_any', 'ms': float(ms.value), 'bytes': int(by.value)}
+
+    # ---- detection on any RD cube: pair sums, cross CFAR, S9, clustering ---------------------------
+    def _detect_params(self, V, G, B, cfar, cluster, range_axis, velocity_axis, deltaR, deltaV, beam_angles_deg,
+                       k_slopes_LUT, monopulse):
+        """rsp_detect_params for a [V, G, B] cube; every None falls back to the plan's own where the
+        shape agrees (range_axis: G == plan.G, velocity_axis: V == plan.P, angles and K-LUT: B == plan.B).
+        Returns (struct, the arrays it borrows)."""
+        pre = self.precomputed_data
+
+        def pick(x, name, n, own_n):
+            if x is None:
+                if n != own_n:
+                    raise ValueError('%s is needed: the cube has %d entries along it, the plan %d' % (name, n, own_n))
+                x = pre[name]
+            a = np.ascontiguousarray(np.asarray(x, np.float64).ravel())
+            if a.size != n:
+                raise ValueError('%s has %d entries, expected %d' % (name, a.size, n))
+            return a if a.size else np.zeros(1)
+
+        cfar = self.cfar_params if cfar is None else cfar
+        cluster = self.cluster_params if cluster is None else cluster
+        monopulse = self.monopulse if monopulse is None else monopulse
+        if monopulse not in ('amplitude', 'complex'):
+            raise ValueError("monopulse must be 'amplitude' or 'complex', got %r" % (monopulse,))
+        keep = [pick(range_axis, 'range_axis', G, self.G), pick(velocity_axis, 'velocity_axis', V, self.P),
+                pick(beam_angles_deg, 'beam_angles_deg', B, self.B), pick(k_slopes_LUT, 'k_slopes_LUT', B - 1, self.B - 1)]
+        prm = _abi.DetectParams(
+            cfar=_xcfar_params(cfar),
+            cluster=_abi.ClusterParams(max_range_sep=cluster['max_range_sep'], max_vel_sep=cluster['max_vel_sep'],
+                                       max_angle_sep=cluster['max_angle_sep']),
+            range_axis=_dptr(keep[0]), velocity_axis=_dptr(keep[1]),
+            deltaR=float(pre['deltaR'] if deltaR is None else deltaR),
+            deltaV=float(pre['deltaV'] if deltaV is None else deltaV),
+            beam_angles_deg=_dptr(keep[2]), k_slopes_LUT=_dptr(keep[3]), monopulse=1 if monopulse == 'complex' else 0)
+        return prm, keep
+
+    def _detect_out(self, V, G, B, want_cfar, rdm_shape=None):
+        o, bufs = _abi.FrameOut(), {}
+        if rdm_shape is not None:
+            bufs['rdm'] = np.empty(rdm_shape, np.complex128, order='F')
+            o.rdm = bufs['rdm'].ctypes.data_as(ct.POINTER(ct.c_double))
+        if want_cfar:
+            bufs['cfar'] = np.empty((V, G, B - 1), np.float64, order='F')
+            o.cfar_maps = _dptr(bufs['cfar'])
+        o.dets, o.dets_cap, o.targets, o.targets_cap = None, 0, None, 0   # no fixed count: rsp_last_*
+        return o, bufs
+
+    @staticmethod
+    def _cube3(a, what):
+        a = np.asarray(a)
+        if a.ndim != 3 or a.shape[2] < 2:
+            raise ValueError('%s %r: expected [rows, G, B] with B >= 2' % (what, a.shape))
+        return a
+
+    def detect(self, rdm, cfar=None, cluster=None, range_axis=None, velocity_axis=None, deltaR=None, deltaV=None,
+               beam_angles_deg=None, k_slopes_LUT=None, monopulse=None, want_cfar=False):
+        """fsf S8-S11 (fun_run_goca_cfar_8, fun_parameter_estimation_9, the two clustering stages) on a
+        complex RD cube ``rdm`` [V, G, B] of any shape (rsp_detect; include/rsp.h restates the semantics):
+        the plan gives the device and the precision, and its own ``cfar`` / ``cluster`` parameters, axes,
+        cell sizes, angles, K-LUT and ``monopulse`` ('amplitude' / 'complex') wherever the argument is
+        None and the shape agrees.  Returns ``detections`` and ``final_targets`` as ``process_cube``, and
+        with ``want_cfar`` ``cfar_maps`` [V, G, B - 1]."""
+        rdm = self._cube3(rdm, 'rdm')
+        V, G, B = rdm.shape
+        prm, keep = self._detect_params(V, G, B, cfar, cluster, range_axis, velocity_axis, deltaR, deltaV,
+                                        beam_angles_deg, k_slopes_LUT, monopulse)
+        a, ap, dt = _complex_arg(rdm)
+        o, bufs = self._detect_out(V, G, B, want_cfar)
+        check(lib().rsp_detect(self.h, V, G, B, ap, dt, ct.byref(prm), ct.byref(o)))
+        return self._collect(o, bufs, None, None)
+
+    def detect_device(self, d_rdm, V, G, B, cfar=None, cluster=None, range_axis=None, velocity_axis=None, deltaR=None,
+                      deltaV=None, beam_angles_deg=None, k_slopes_LUT=None, monopulse=None, want_cfar=False):
+        """The same on a device cube [V, G, B] in the plan's precision and MATLAB's layout, Doppler index
+        fastest (rsp_detect_device): ``mtd_device``'s output."""
+        V, G, B = int(V), int(G), int(B)
+        prm, keep = self._detect_params(V, G, B, cfar, cluster, range_axis, velocity_axis, deltaR, deltaV,
+                                        beam_angles_deg, k_slopes_LUT, monopulse)
+        o, bufs = self._detect_out(V, G, B, want_cfar)
+        check(lib().rsp_detect_device(self.h, V, G, B, ct.c_void_p(d_rdm), ct.byref(prm), ct.byref(o)))
+        return self._collect(o, bufs, None, None)
+
+    def mtd_detect(self, pc, win=None, nfft=None, cfar=None, cluster=None, range_axis=None, velocity_axis=None,
+                   deltaR=None, deltaV=None, beam_angles_deg=None, k_slopes_LUT=None, monopulse=None, want_rdm=False,
+                   want_cfar=False):
+        """``mtd`` of ``pc`` [P, G, B] to ``nfft`` rows and ``detect`` on the result without leaving the
+        device (rsp_mtd_detect; v7_7 sections 7-10): ``velocity_axis`` has nfft entries.  ``want_rdm`` adds
+        the cube ``rdm`` [nfft, G, B]."""
+        pc = self._cube3(pc, 'pc')
+        P, G, B = pc.shape
+        n = int(nfft) if nfft else P
+        prm, keep = self._detect_params(n, G, B, cfar, cluster, range_axis, velocity_axis, deltaR, deltaV,
+                                        beam_angles_deg, k_slopes_LUT, monopulse)
+        wk, wp = self._mtd_win(win, P)
+        a, ap, dt = _complex_arg(pc)
+        o, bufs = self._detect_out(n, G, B, want_cfar, (n, G, B) if want_rdm else None)
+        check(lib().rsp_mtd_detect(self.h, P, G, B, n, ap, dt, wp, ct.byref(prm), ct.byref(o)))
+        return self._collect(o, bufs, None, None)
+
+    def process_stage2_detect(self, iq_beams, gate_cols=None, want_rdm=False, want_cfar=False):
+        """process_stage2_mtd followed by ``detect`` on MTD_results without leaving the device, with the
+        plan's own parameters (rsp_process_stage2_detect).  ``iq_beams`` and ``gate_cols`` as
+        ``process_stage2`` (a gated input is put back at its PRT columns here); ``want_rdm`` adds
+        MTD_results as ``rdm`` [P, G, B]."""
+        iq = np.asarray(iq_beams)
+        if gate_cols is not None:
+            if iq.ndim != 3 or iq.shape[0] != self.P or iq.shape[2] != self.B:
+                raise ValueError('iq shape %r: expected (P, n, B) with P=%d B=%d' % (iq.shape, self.P, self.B))
+            cols = np.concatenate([np.arange(f - 1, l) for f, l in gate_cols])
+            if cols.size != iq.shape[1] or cols.min() < 0 or cols.max() >= self.N:
+                raise ValueError('gate_cols cover %d columns of a %d-sample PRT, the input has %d' % (cols.size, self.N, iq.shape[1]))
+            full = np.zeros((self.P, self.N, self.B), iq.dtype if iq.dtype == np.complex64 else np.complex128, order='F')
+            full[:, cols, :] = iq
+            iq = full
+        if iq.shape != (self.P, self.N, self.B):
+            raise ValueError('iq shape %r != (P, N, B) = %r' % (iq.shape, (self.P, self.N, self.B)))
+        a, ap, dt = _complex_arg(iq)
+        o, bufs = self._detect_out(self.P, self.G, self.B, want_cfar and self.B > 1,
+                                   (self.P, self.G, self.B) if want_rdm else None)
+        check(lib().rsp_process_stage2_detect(self.h, ap, dt, ct.byref(o)))
+        return self._collect(o, bufs, None, None)
+
+    def profile_detect(self, V, G, B, cfar=None, iters=20):
+        """HIP-event times of the detector's three kernels on the library's test cube of [V, G, B]
+        (rsp_profile_detect): {'k_pairsum' | 'k_xcfar' | 'k_s9': (ms, bytes)}."""
+        prm = _xcfar_params(self.cfar_params if cfar is None else cfar)
+        ms, by = (ct.c_float * 3)(), (ct.c_int64 * 3)()
+        check(lib().rsp_profile_detect(self.h, int(V), int(G), int(B), ct.byref(prm), int(iters), ms, by))
+        return {k: (float(ms[i]), int(by[i])) for i, k in enumerate(('k_pairsum', 'k_xcfar', 'k_s9'))}
 
     def _raw_weights(self, W):
         """(array kept alive, pointer) of the weights of a raw-cube call; None: the plan's own."""

@@ -15,7 +15,7 @@ for a library or a single object file (build/rsp_k2.hip.o): two builds whose lis
 run the same machine code in every template instantiation.
 
 The frame chain's kernels are spread over one translation unit per stage (rsp_k1.hip, rsp_k2.hip,
-rsp_k3.hip, rsp_frame_aux.hip, rsp_stage3.hip, rsp_vcfar.hip, rsp_xcfar.hip, rsp_dbf.hip, rsp_mtd.hip) plus rsp_music.hip, so a library has
+rsp_k3.hip, rsp_frame_aux.hip, rsp_stage3.hip, rsp_vcfar.hip, rsp_xcfar.hip, rsp_dbf.hip, rsp_mtd.hip, rsp_detect.hip) plus rsp_music.hip, so a library has
 several code objects.  A kernel's mangled name found in two of them is an error (merge), and the
 Makefile's hash step fails.
 """
