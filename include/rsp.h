@@ -858,6 +858,62 @@ int32_t rsp_process_stage2_detect(rsp_plan* plan, const void* iq_beams, int32_t 
 int32_t rsp_profile_detect(rsp_plan* plan, int32_t V, int32_t G, int32_t B, const rsp_cfar_params* params, int32_t iters,
                            float* ms_out, int64_t* bytes_out);
 
+/* ---- pulse compression as a stand-alone stage: any pulse count, any beam count ----
+ * Section 6 of main_simulate_echoes_with_array_v7_7.m (:362-486; fun_process_single_frame.m:99-127): the
+ * three-segment pulse compression of every (pulse, beam) row of a beam cube iq_beams [P x N x B] in MATLAB's
+ * layout (pulse index fastest) into pc [P x G x B].  A row's arithmetic is k2_pc's, the kernel of
+ * rsp_process_stage2, and depends on that row's samples alone; what is new is the way in and out of it:
+ *   k_pc_pack    beams -> k2_pc's compacted sample rows (z) for the caller's P and B, no window, no transform;
+ *   k2_pc        on a record table built for B P rows, with the plan's segments, taps, spectra and twiddles;
+ *   k_pc_unpack  k2_pc's [B][P][G] result -> pc [P x G x B].
+ * The plan gives the device, the stream, the precision, N = point_PRT, the gate layout and the filter
+ * tables; its own prtNum and beam_num play no part, so P may be odd, prime or 1. */
+typedef struct rsp_pc_info {
+    int32_t P, B, N, G;
+    int32_t nU, n_intervals;             /* used fast-time samples, and the intervals they form            */
+    int32_t NZ, nzc;                     /* z: NZ compacted samples per (row, chunk) slab, nzc chunks       */
+    int64_t z_elems;                     /* B nzc P NZ complex elements                                    */
+    int32_t pack_rows, pack_cols;        /* k_pc_pack's tile: NZ samples x pulses                          */
+    int32_t unpack_rows, unpack_cols;    /* k_pc_unpack's tile: pulses x gates; a workgroup walks up to 8
+                                            such tiles along the pulse axis                                */
+    int32_t pack_wg, k2_wg, unpack_wg;   /* workgroups of the three launches                               */
+    int32_t k2_wg_per_cu;                /* the k2_pc instantiation (rsp_k2_layout.wg_per_cu)              */
+    int32_t pack_lds_bytes, unpack_lds_bytes;   /* LDS of a workgroup, padding included                    */
+    /* interval q < n_intervals: compacted samples ivl_start[q] .. are fast-time samples ivl_lo[q] .. (0-based) */
+    int32_t ivl_lo[4], ivl_start[4];
+} rsp_pc_info;
+/* The size checks of the calls below, with the same refusals and messages, and how the three launches cover
+ * P pulses of B beams.  RSP_ERR_INVALID: P < 1 or B < 1; RSP_ERR_UNSUPPORTED: 2 GB or more of beams, of z or
+ * of result (the kernels address each with 32-bit byte offsets).  `info` may be NULL. */
+int32_t rsp_query_pc(const rsp_plan* plan, int32_t P, int32_t B, rsp_pc_info* info);
+/* The same from the arguments of rsp_plan_create_ex, whose prtNum and beam_num are not read (a
+ * configuration that a plan refuses for its prtNum alone is accepted).  No HIP call is made. */
+int32_t rsp_plan_describe_pc(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params* cluster,
+                             const rsp_precomputed* pre, const rsp_plan_options* opt, int32_t ncu, int32_t P, int32_t B,
+                             rsp_pc_info* info);
+/* iq_beams [P x N x B] (dtype RSP_C64 / RSP_C128, converted to the plan's precision as rsp_process_cube
+ * converts) -> pc_out, complex double [P x G x B].  Synchronous; drains the queue first.  Refusals (sizes,
+ * dtype, null pointers, in that order) come before any device work.  Scratch buffers are the plan's, grow on
+ * demand and are kept; the record table is rebuilt only when (P, B) changes. */
+int32_t rsp_pc(rsp_plan* plan, int32_t P, int32_t B, const void* iq_beams, int32_t dtype, double* pc_out);
+/* The same on device memory in the plan's precision, MATLAB's layout on both sides: d_beams [P x N x B] ->
+ * d_pc [P x G x B] (what rsp_mtd_device reads), which must not overlap and are aligned to a complex element.
+ * Nothing outside those P G B elements is written. */
+int32_t rsp_pc_device(rsp_plan* plan, int32_t P, int32_t B, const void* d_beams, void* d_pc);
+/* v7_7 sections 6-10: rsp_pc_device, rsp_mtd_device (shift = 1, nfft rows; 0 = P) and rsp_detect_device on
+ * the plan's scratch; the arguments and outputs are rsp_mtd_detect's, out->rdm the [nfft x G x B] cube. */
+int32_t rsp_pc_mtd_detect(rsp_plan* plan, int32_t P, int32_t B, int32_t nfft, const void* iq_beams, int32_t dtype,
+                          const double* win, const rsp_detect_params* params, rsp_frame_out* out);
+/* v7_7 sections 5-10 from the raw cube [P x N x C]: k_dbf first, with rsp_dbf's W (B x C) and conj; W = NULL
+ * takes the plan's own weights, whose shape B x C must then be the plan's. */
+int32_t rsp_raw_detect(rsp_plan* plan, int32_t P, int32_t C, int32_t B, int32_t nfft, const void* cube, int32_t dtype,
+                       const double* W, int32_t conj, const double* win, const rsp_detect_params* params,
+                       rsp_frame_out* out);
+/* Device times by HIP events on the plan's stream, averaged over `iters` launches each, on zeros: ms_out[0]
+ * k_pc_pack, [1] the k2_pc launch, [2] k_pc_unpack.  bytes_out[0] = element bytes x (P nU B read + z written),
+ * [1] = z + the result + the scratch magnitude map, [2] = 2 x element bytes x P G B. */
+int32_t rsp_profile_pc(rsp_plan* plan, int32_t P, int32_t B, int32_t iters, float* ms_out, int64_t* bytes_out);
+
 /* ---- measurement ----
  * Time each device stage `iters` times on the plan's stream with HIP events.  Each launch
  * batches nf = min(n_cubes, frames_per_launch) frames taken from the device-resident

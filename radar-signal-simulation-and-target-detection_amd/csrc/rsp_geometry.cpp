@@ -1234,3 +1234,91 @@ extern "C" int32_t rsp_plan_describe_dbf_table(const rsp_sig_config* cfg, const 
     for (int i = 0; i < cap && i < (int)h.atab.size(); ++i) out[i] = h.atab[i];
     return RSP_OK;
 }
+
+// ---- pulse compression for any pulse and beam count (k_pc_pack, k2_pc, k_pc_unpack) ----
+int rsp_pc_derive(const Geometry& base, int64_t P, int64_t B, PcDesc* out, std::vector<K2Rec>* rec) {
+    if (P < 1 || B < 1) return fail(RSP_ERR_INVALID, "bad sizes P=%lld B=%lld (P, B >= 1)", (long long)P, (long long)B);
+    // beams, z and the result each under 2 GB: the kernels and k2_pc's buffer resources take 32-bit byte
+    // offsets (rsp_plan_check_args' limit for a frame)
+    const int64_t esz = base.prec == RSP_PREC_F64 ? 16 : 8, lim = (int64_t)1 << 31;
+    const int64_t nzc = (base.nU + RSP_PC_NZ - 1) / RSP_PC_NZ, row = std::max<int64_t>(std::max<int64_t>(base.N, base.G), nzc * RSP_PC_NZ);
+    if (P >= lim || B >= lim || P * B >= lim || P * B * row >= lim || P * B * row * esz >= lim)
+        return fail(RSP_ERR_UNSUPPORTED,
+                    "%lld pulses x %lld beams of %d samples, %d gates: the kernels address the beams, the compacted rows and the result with 32-bit offsets (< 2 GB each)",
+                    (long long)P, (long long)B, base.N, base.G);
+    PcDesc d{};
+    Geometry& g = d.g;
+    g = base;
+    g.P = (int)P;
+    g.B = g.C = (int)B;
+    g.cpitch = g.N * g.P;
+    g.NZ = RSP_PC_NZ;
+    g.nzc = (int)nzc;
+    std::vector<SegDesc> segs(g.segs, g.segs + g.nseg);
+    std::vector<K2Job> jobs;
+    std::vector<K2Rec> local;
+    std::vector<K2Rec>& r = rec ? *rec : local;
+    int rc = k2_build_records(g, segs, g.B * g.P, &jobs, nullptr, &r);
+    if (rc) return rc;
+    g.njobs = (int)jobs.size();   // segments x blocks: the base's count
+    for (int q = 0; q < g.njobs && q < RSP_MAX_JOBS; ++q) g.jobs[q] = jobs[q];
+    g.nwg_k2 = (int)r.size();
+    d.rows = K2Rows{g.P, 0, g.P, 0, g.B * g.P};
+    d.pack_tiles = (g.P + RSP_PCK_COLS - 1) / RSP_PCK_COLS;
+    d.pack_wg = g.nzc * d.pack_tiles * g.B;
+    d.unpack_row_tiles = (g.P + RSP_PCU_ROWS - 1) / RSP_PCU_ROWS;
+    d.unpack_col_tiles = (g.G + pcu_cols(g.prec) - 1) / pcu_cols(g.prec);
+    d.unpack_row_groups = (d.unpack_row_tiles + RSP_PCU_GROUP - 1) / RSP_PCU_GROUP;
+    d.unpack_wg = d.unpack_col_tiles * d.unpack_row_groups * g.B;
+    d.in_elems = (size_t)P * g.N * B;
+    d.z_elems = (size_t)B * g.nzc * g.NZ * P;
+    d.out_elems = (size_t)P * g.G * B;
+    d.mag_elems = (size_t)P * g.Gp * B;
+    if (out) *out = d;
+    return RSP_OK;
+}
+
+void rsp_fill_pc_info(const PcDesc& d, rsp_pc_info* out) {
+    const Geometry& g = d.g;
+    *out = rsp_pc_info{};
+    out->P = g.P; out->B = g.B; out->N = g.N; out->G = g.G;
+    out->nU = g.nU;
+    out->n_intervals = g.nivl;
+    out->NZ = g.NZ;
+    out->nzc = g.nzc;
+    out->z_elems = (int64_t)d.z_elems;
+    out->pack_rows = RSP_PC_NZ;
+    out->pack_cols = RSP_PCK_COLS;
+    out->unpack_rows = RSP_PCU_ROWS;
+    out->unpack_cols = pcu_cols(g.prec);
+    out->pack_wg = d.pack_wg;
+    out->k2_wg = g.nwg_k2;
+    out->unpack_wg = d.unpack_wg;
+    out->k2_wg_per_cu = k2_wg_per_cu(g);
+    out->pack_lds_bytes = (int32_t)pck_lds_bytes(g.prec);
+    out->unpack_lds_bytes = (int32_t)pcu_lds_bytes(g.prec);
+    static_assert(RSP_MAX_IVL == 4, "rsp_pc_info::ivl_lo / ivl_start");
+    for (int q = 0; q < g.nivl; ++q) {
+        out->ivl_lo[q] = g.ivl_lo[q];
+        out->ivl_start[q] = g.ivl_start[q];
+    }
+}
+
+extern "C" int32_t rsp_plan_describe_pc(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params* cluster,
+                                        const rsp_precomputed* pre, const rsp_plan_options* opt, int32_t ncu, int32_t P, int32_t B,
+                                        rsp_pc_info* info) {
+    if (!cfg) return fail(RSP_ERR_INVALID, "null argument");
+    // The base: a plan of the same waveform for the smallest frame a plan takes (two pulses, one beam).  The
+    // segments, the sample intervals and k2_pts, all this stage reads, depend on neither count.
+    rsp_sig_config c2 = *cfg;
+    c2.prtNum = 2;
+    c2.beam_num = 1;
+    int rc = rsp_plan_check_args(&c2, cfar, cluster, pre, opt);
+    if (rc) return rc;
+    PlanHost h;
+    if ((rc = rsp_plan_derive(&c2, cfar, cluster, pre, opt, ncu, &h))) return rc;
+    PcDesc d;
+    if ((rc = rsp_pc_derive(h.g, P, B, &d, nullptr)) || !info) return rc;
+    rsp_fill_pc_info(d, info);
+    return RSP_OK;
+}

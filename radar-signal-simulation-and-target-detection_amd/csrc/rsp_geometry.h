@@ -492,6 +492,46 @@ struct DetDesc {         // kernel argument of k_pairsum and k_s9
 // RSP_OK, or the refusal with its message set.
 int rsp_detect_check_sizes(int64_t V, int64_t G, int64_t B, int precision, const rsp_cfar_params* prm, XcDesc* out);
 
+// ---- pulse compression for any pulse and beam count (k_pc_pack, k2_pc, k_pc_unpack; rsp_pc.hip) ----
+// k_pc_pack turns beams [P x N x B] (pulse index fastest) into k2_pc's z input for a Geometry that carries the
+// caller's P and B; k_pc_unpack turns k2_pc's [B][P][G] result into pc [P x G x B].  Both are tiled
+// transposes through LDS with 256 threads.
+//   pack:   a workgroup takes one z chunk (RSP_PC_NZ compacted samples) of RSP_PCK_COLS pulses of one beam:
+//           NZ source rows of up to COLS contiguous pulses in, COLS NZ contiguous z elements out.  LDS rows
+//           (one per sample) are COLS + RSP_PCK_PAD elements apart.
+//   unpack: a workgroup takes RSP_PCU_ROWS pulses of pcu_cols(prec) gates of one beam (512 bytes of a result
+//           row: 64 complex singles, 32 complex doubles).  LDS rows (one per pulse) are cols + RSP_PCU_PAD
+//           elements apart: an odd stride, k_pairsum's rule.  It walks up to RSP_PCU_GROUP such tiles along the
+//           pulse axis, so that one workgroup writes a column's consecutive 512-byte runs.
+#define RSP_PC_NZ 8
+#define RSP_PCK_COLS 256
+#define RSP_PCK_PAD 4
+#define RSP_PCU_ROWS 64
+#define RSP_PCU_PAD 1
+#define RSP_PCU_GROUP 8   // pulse tiles one unpack workgroup walks: 512 pulses of its gates
+RSP_HD constexpr int pcu_cols(int prec) { return prec == RSP_PREC_F64 ? 32 : 64; }
+RSP_HD constexpr size_t pck_lds_bytes(int prec) {
+    return (size_t)RSP_PC_NZ * (RSP_PCK_COLS + RSP_PCK_PAD) * (prec == RSP_PREC_F64 ? 16 : 8);
+}
+RSP_HD constexpr size_t pcu_lds_bytes(int prec) {
+    return (size_t)RSP_PCU_ROWS * (pcu_cols(prec) + RSP_PCU_PAD) * (prec == RSP_PREC_F64 ? 16 : 8);
+}
+struct PcDesc {
+    // k2_pc's kernel argument: the base's segments, sample intervals, N, G, Gp, precision and k2_pts with
+    // the caller's P and B, NZ = RSP_PC_NZ, nzc, and the jobs of B P rows (njobs, jobs, nwg_k2)
+    Geometry g;
+    K2Rows rows;                 // {P, 0, P, 0, B P}
+    int pack_tiles, pack_wg;     // pulse tiles of a chunk; workgroups = nzc x pack_tiles x B, chunk fastest
+    int unpack_row_tiles, unpack_row_groups, unpack_col_tiles, unpack_wg;   // workgroups = col tiles x row groups x B, columns fastest
+    size_t in_elems, z_elems, out_elems, mag_elems;      // beams, z, the result (either layout), the scratch magnitude map
+};
+// The checks of the rsp_pc calls that need no device, and everything their launches are sized by.  `base` is a
+// derived plan Geometry: only what does not depend on its own P and B is read (see PcDesc::g).  rec (may be
+// null): k2_pc's record table for the B P rows.  RSP_OK, or the refusal with its message set: RSP_ERR_INVALID
+// for P < 1 or B < 1, RSP_ERR_UNSUPPORTED when the beams, z or the result reach 2 GB.
+int rsp_pc_derive(const Geometry& base, int64_t P, int64_t B, PcDesc* out, std::vector<K2Rec>* rec);
+void rsp_fill_pc_info(const PcDesc& d, rsp_pc_info* out);
+
 // The checks of rsp_plan_create_ex that need no device and come before its device checks.
 int rsp_plan_check_args(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params* cluster,
                         const rsp_precomputed* pre, const rsp_plan_options* opt);

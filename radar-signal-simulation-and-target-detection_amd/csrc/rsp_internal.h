@@ -126,6 +126,12 @@ hipError_t launch_mtd(const MtdDesc& d, int prec, const void* pc, const void* wi
 hipError_t launch_pairsum(DetDesc d, int prec, int layout, const void* x, void* S, hipStream_t s);
 hipError_t launch_s9(const DetDesc& d, int prec, int layout, const DevConsts& k, const void* x, const void* S,
                      const rsp_stage3_hit* hits, int n, DevDet* dets, hipStream_t s);
+// Pulse compression for any pulse and beam count (rsp_pc.hip), around launch_k2_set on d.g / d.rows.
+// launch_pc_pack: beams [P x N x B] (pulse fastest, beam planes `pitch` elements apart) -> z of d.z_elems,
+// 16-byte aligned; launch_pc_unpack: k2_pc's result [B][P][G] -> pc [P x G x B].  Complex of the precision;
+// either launcher takes element pairs in complex single where the caller's side is aligned for them.
+hipError_t launch_pc_pack(const PcDesc& d, const void* beams, int pitch, void* z, hipStream_t s);
+hipError_t launch_pc_unpack(const PcDesc& d, const void* res, void* pc, hipStream_t s);
 // Queue read-back: count record + the detections of nf frames (device stride dcap + 1 records) into
 // mapped pinned host memory (stride hcap + 1), only the records that exist.
 hipError_t launch_dets_to_host(const void* dets, int dcap, void* host, int hcap, int nf, hipStream_t s);

@@ -181,6 +181,12 @@ struct rsp_plan {
     // S9 records of its hits, and the caller's axes, angles and K-LUT (doubles); the plan's own
     // cluster parameters are `cl`
     DevBuf det_in, det_smap, det_dets, det_axes;
+    // pulse compression for any pulse and beam count (rsp_pc and its compositions): the call's beams, k2_pc's
+    // z input, its [B][P][G] result and the magnitude map it always stores (scratch: nothing reads it), the
+    // host forms' result in MATLAB's layout, and the record table of the (P, B) in pc_d, rebuilt only when
+    // they change (pc_d.g.P = 0: none yet)
+    DevBuf pc_in, pc_z, pc_res, pc_mag, pc_out, pc_rec;
+    PcDesc pc_d{};
     // raw-cube stage 2 (rsp_process_raw_stage2*): the plan's own weights, and the A operands of the last
     // call whose W / conj were not the plan's (K1's layout; uploaded again only when they change)
     std::vector<double> h_W;
@@ -283,7 +289,7 @@ rsp_plan::~rsp_plan() {
     if (up_stream) (void)hipStreamDestroy(up_stream);
     if (h_stage) (void)hipHostFree(h_stage);
     for (DevBuf* b : {&s3_in, &s3_amp, &s3_thr, &s3_flags, &s3_hits, &s3_count, &dbf_in, &dbf_out, &dbf_tab, &raw_tab, &mtd_in, &mtd_out,
-                      &mtd_win, &det_in, &det_smap, &det_dets, &det_axes})
+                      &mtd_win, &det_in, &det_smap, &det_dets, &det_axes, &pc_in, &pc_z, &pc_res, &pc_mag, &pc_out, &pc_rec})
         if (b->p) (void)hipFree(b->p);
     for (auto* m : {&mtd_tab, &mtd_tw})
         for (auto& kv : *m) (void)hipFree(kv.second);
@@ -2030,6 +2036,209 @@ int32_t rsp_profile_detect(rsp_plan* p, int32_t V, int32_t G, int32_t B, const r
         bytes_out[0] = (int64_t)(elems * p->esz + cells * p->rsz);
         bytes_out[1] = (int64_t)(cells * p->rsz);
         bytes_out[2] = (int64_t)sizeof(DevDet) * n;
+    }
+    return RSP_OK;
+}
+
+// ---- pulse compression for any pulse and beam count: k_pc_pack -> k2_pc -> k_pc_unpack ----
+// The sizes of a call (checked), the plan's scratch for them and the record table of (P, B) on the device
+static int pc_prepare(rsp_plan* p, int P, int B) {
+    int rc;
+    if (p->pc_d.g.P != P || p->pc_d.g.B != B || !p->pc_rec.p) {
+        PcDesc d;
+        std::vector<K2Rec> rec;
+        if ((rc = rsp_pc_derive(p->g, P, B, &d, &rec))) return rc;
+        p->pc_d.g.P = 0;   // no key while the table is being replaced
+        if ((rc = s3_reserve(p->pc_rec, std::max<size_t>(rec.size(), 1) * sizeof(K2Rec)))) return rc;
+        if (!rec.empty()) HIPCHK(hipMemcpy(p->pc_rec.p, rec.data(), rec.size() * sizeof(K2Rec), hipMemcpyHostToDevice));
+        p->pc_d = d;
+    }
+    const PcDesc& d = p->pc_d;
+    if ((rc = s3_reserve(p->pc_z, d.z_elems * p->esz)) || (rc = s3_reserve(p->pc_res, d.out_elems * p->esz))) return rc;
+    return s3_reserve(p->pc_mag, d.mag_elems * p->rsz);
+}
+
+// The three launches on device memory of the plan's precision (pc_prepare done, queue drained): beams at
+// `pitch` elements per plane -> d_pc [P x G x B].  k2_pc stores its magnitude map whatever is asked of it:
+// it goes to the scratch p->pc_mag.
+static int pc_launches(rsp_plan* p, const void* d_beams, int pitch, void* d_pc, hipStream_t s, int only = -1) {
+    const PcDesc& d = p->pc_d;
+    FramePtrs fp{};
+    fp.z[0] = p->pc_z.p;
+    fp.rdm[0] = p->pc_res.p;
+    fp.mag[0] = p->pc_mag.p;
+    if (only < 0 || only == 0) HIPCHK(launch_pc_pack(d, d_beams, pitch, p->pc_z.p, s));
+    if (only < 0 || only == 1)
+        HIPCHK(launch_k2_set(d.g, p->k, fp, 1, d.rows, static_cast<const K2Rec*>(p->pc_rec.p), d.g.nwg_k2, false, s));
+    if (only < 0 || only == 2) HIPCHK(launch_pc_unpack(d, p->pc_res.p, d_pc, s));
+    return RSP_OK;
+}
+
+static int pc_sizes(const rsp_plan* p, int64_t P, int64_t B, PcDesc* d) {
+    // without a plan the sizes cannot be judged: only the refusals that need none (P, B < 1) come first
+    if (!p) return (P < 1 || B < 1) ? fail(RSP_ERR_INVALID, "bad sizes P=%lld B=%lld (P, B >= 1)", (long long)P, (long long)B)
+                                    : fail(RSP_ERR_INVALID, "null argument");
+    if (P >= 1 && p->pc_d.g.P == P && p->pc_d.g.B == B) {   // the sizes of the last call: already derived
+        if (d) *d = p->pc_d;
+        return RSP_OK;
+    }
+    return rsp_pc_derive(p->g, P, B, d, nullptr);
+}
+
+int32_t rsp_query_pc(const rsp_plan* p, int32_t P, int32_t B, rsp_pc_info* info) {
+    PcDesc d;
+    int rc = pc_sizes(p, P, B, &d);
+    if (rc || !info) return rc;
+    rsp_fill_pc_info(d, info);
+    return RSP_OK;
+}
+
+// A host beam cube into p->pc_in and the launches into d_pc
+static int pc_from_host(rsp_plan* p, int P, int B, const void* iq, int dtype, void* d_pc, hipStream_t s) {
+    int rc = pc_prepare(p, P, B);
+    if (rc || (rc = det_upload(p, p->pc_in, iq, dtype, p->pc_d.in_elems, s))) return rc;
+    return pc_launches(p, p->pc_in.p, p->g.N * P, d_pc, s);
+}
+
+int32_t rsp_pc(rsp_plan* p, int32_t P, int32_t B, const void* iq, int32_t dtype, double* pc_out) {
+    int rc = pc_sizes(p, P, B, nullptr);
+    if (rc) return rc;   // refusals before any device work
+    if (dtype != RSP_C64 && dtype != RSP_C128) return fail(RSP_ERR_INVALID, "unknown dtype %d", dtype);
+    if (!iq || !pc_out) return fail(RSP_ERR_INVALID, "null argument");
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    hipStream_t s = p->lanes[0].stream;
+    const bool f64 = p->g.prec == RSP_PREC_F64;
+    const size_t nout = (size_t)P * p->g.G * B;
+    if ((rc = s3_reserve(p->pc_out, nout * p->esz)) || (rc = pc_from_host(p, P, B, iq, dtype, p->pc_out.p, s))) return rc;
+    std::vector<float> nar(f64 ? 0 : 2 * nout);   // widened to double for a complex-single plan
+    HIPCHK(hipMemcpyAsync(f64 ? (void*)pc_out : (void*)nar.data(), p->pc_out.p, nout * p->esz, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (!f64) rsp_convert_reals(nar.data(), RSP_C64, 2 * nout, pc_out);
+    return RSP_OK;
+}
+
+int32_t rsp_pc_device(rsp_plan* p, int32_t P, int32_t B, const void* d_beams, void* d_pc) {
+    int rc = pc_sizes(p, P, B, nullptr);
+    if (rc) return rc;
+    if (!d_beams || !d_pc) return fail(RSP_ERR_INVALID, "null argument");
+    const size_t nin = (size_t)P * p->g.N * B, nout = (size_t)P * p->g.G * B;
+    const char *a = static_cast<const char*>(d_beams), *b = static_cast<const char*>(d_pc);
+    if (a < b + nout * p->esz && b < a + nin * p->esz) return fail(RSP_ERR_INVALID, "d_beams and d_pc overlap");
+    if ((uintptr_t)d_beams % p->esz || (uintptr_t)d_pc % p->esz)
+        return fail(RSP_ERR_INVALID, "d_beams and d_pc must be aligned to a complex element (%zu bytes)", p->esz);
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    hipStream_t s = p->lanes[0].stream;
+    if ((rc = pc_prepare(p, P, B)) || (rc = pc_launches(p, d_beams, p->g.N * P, d_pc, s))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    return RSP_OK;
+}
+
+// MTD to n rows (shift = 1) of the pc cube in p->mtd_in into p->mtd_out, the detector on it, and out->rdm: the
+// back half of rsp_mtd_detect, shared by the two compositions below (sizes checked, k and mtd_out set up)
+static int pc_mtd_detect_tail(rsp_plan* p, int P, int B, int n, const XcDesc& xd, const DevConsts& k, const double* win,
+                              const rsp_detect_params* prm, rsp_frame_out* out, hipStream_t s) {
+    const int G = p->g.G;
+    const size_t nout = (size_t)G * B * n;
+    int rc = mtd_run(p, mtd_desc(P, G, B, n, 1, win != nullptr, p->g.prec), p->mtd_in.p, win, p->mtd_out.p, s);
+    if (rc) return rc;
+    const int rr = det_run(p, xd, B, DET_LAYOUT_MATLAB, p->mtd_out.p, k, prm->monopulse, prm->cluster, out);
+    if (rr && rr != RSP_ERR_OVERFLOW) return rr;
+    if (out && out->rdm) {   // the cube, widened to double for a complex-single plan
+        const bool f64 = p->g.prec == RSP_PREC_F64;
+        std::vector<float> nar(f64 ? 0 : 2 * nout);
+        HIPCHK(hipMemcpy(f64 ? (void*)out->rdm : (void*)nar.data(), p->mtd_out.p, nout * p->esz, hipMemcpyDeviceToHost));
+        if (!f64) rsp_convert_reals(nar.data(), RSP_C64, 2 * nout, out->rdm);
+    }
+    return rr;
+}
+
+// The size checks of the two compositions after the pulse compression's own: MTD and detector at G = the plan's
+static int pc_chain_sizes(const rsp_plan* p, int P, int B, int nfft, const rsp_detect_params* prm, int* n, XcDesc* xd) {
+    int rc = rsp_mtd_check_sizes(P, p->g.G, B, nfft, det_prec(p), n);
+    return rc ? rc : rsp_detect_check_sizes(*n, p->g.G, B, det_prec(p), prm ? &prm->cfar : nullptr, xd);
+}
+
+int32_t rsp_pc_mtd_detect(rsp_plan* p, int32_t P, int32_t B, int32_t nfft, const void* iq, int32_t dtype, const double* win,
+                          const rsp_detect_params* prm, rsp_frame_out* out) {
+    int n = 0;
+    XcDesc xd;
+    int rc = pc_sizes(p, P, B, nullptr);
+    if (rc || (rc = pc_chain_sizes(p, P, B, nfft, prm, &n, &xd))) return rc;
+    if (dtype != RSP_C64 && dtype != RSP_C128) return fail(RSP_ERR_INVALID, "unknown dtype %d", dtype);
+    if ((rc = det_args(p, iq, prm, out, true))) return rc;
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    hipStream_t s = p->lanes[0].stream;
+    const int G = p->g.G;
+    DevConsts k;
+    if ((rc = det_consts(p, n, G, B, prm, &k)) || (rc = s3_reserve(p->mtd_out, (size_t)G * B * n * p->esz)) ||
+        (rc = s3_reserve(p->mtd_in, (size_t)G * B * P * p->esz)))
+        return rc;
+    if ((rc = pc_from_host(p, P, B, iq, dtype, p->mtd_in.p, s))) return rc;
+    return pc_mtd_detect_tail(p, P, B, n, xd, k, win, prm, out, s);
+}
+
+int32_t rsp_raw_detect(rsp_plan* p, int32_t P, int32_t C, int32_t B, int32_t nfft, const void* cube, int32_t dtype,
+                       const double* W, int32_t conj, const double* win, const rsp_detect_params* prm, rsp_frame_out* out) {
+    int n = 0;
+    XcDesc xd;
+    int rc = pc_sizes(p, P, B, nullptr);
+    if (rc || (rc = rsp_dbf_check_sizes(P, p->g.N, C, B, det_prec(p))) || (rc = pc_chain_sizes(p, P, B, nfft, prm, &n, &xd)))
+        return rc;
+    if (dtype != RSP_C64 && dtype != RSP_C128) return fail(RSP_ERR_INVALID, "unknown dtype %d", dtype);
+    if ((rc = det_args(p, cube, prm, out, true))) return rc;
+    if (!W && (B != p->g.B || C != p->g.C))
+        return fail(RSP_ERR_INVALID, "W = NULL takes the plan's weights, %d x %d; the call has B=%d C=%d", p->g.B, p->g.C, B, C);
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    hipStream_t s = p->lanes[0].stream;
+    const bool f64 = p->g.prec == RSP_PREC_F64;
+    const int G = p->g.G;
+    const size_t S = (size_t)P * p->g.N, esz = p->esz;
+    DevConsts k;
+    DbfDesc dd;
+    if ((rc = det_consts(p, n, G, B, prm, &k)) || (rc = s3_reserve(p->mtd_out, (size_t)G * B * n * esz)) ||
+        (rc = s3_reserve(p->mtd_in, (size_t)G * B * P * esz)) || (rc = dbf_reserve(p, (int)S, C, B, &dd)) ||
+        (rc = pc_prepare(p, P, B)))
+        return rc;
+    // rsp_dbf's device half: the A operands, the channel planes at the kernel's pitch, k_dbf
+    std::vector<double> t;
+    rsp_dbf_atab(W ? W : p->h_W.data(), B, C, conj, f64 ? DBF_ROWS_SPLIT : DBF_ROWS_PAIR, t);
+    if ((rc = p->put_reals(p->dbf_tab.p, t.data(), t.size()))) return rc;
+    const void* src = cube;
+    if ((dtype == RSP_C128) != f64) {
+        if ((rc = ensure_stage(p, S * C * esz))) return rc;
+        rsp_convert_reals(cube, dtype, 2 * S * C, p->h_stage);
+        src = p->h_stage;
+    }
+    HIPCHK(hipMemcpy2DAsync(p->dbf_in.p, (size_t)dd.pitch * esz, src, S * esz, S * esz, C, hipMemcpyHostToDevice, s));
+    HIPCHK(launch_dbf(dd, p->g.prec, p->dbf_in.p, p->dbf_tab.p, p->dbf_out.p, s));
+    HIPCHK(hipStreamSynchronize(s));   // the caller's cube (or the staging buffer) is borrowed until here
+    if ((rc = pc_launches(p, p->dbf_out.p, dd.opitch, p->mtd_in.p, s))) return rc;
+    return pc_mtd_detect_tail(p, P, B, n, xd, k, win, prm, out, s);
+}
+
+int32_t rsp_profile_pc(rsp_plan* p, int32_t P, int32_t B, int32_t iters, float* ms_out, int64_t* bytes_out) {
+    int rc = pc_sizes(p, P, B, nullptr);   // sizes first, as the other calls of the section
+    if (rc) return rc;
+    if (iters < 1 || !ms_out) return fail(RSP_ERR_INVALID, "bad argument");
+    HIPCHK(hipSetDevice(p->device));
+    if ((rc = drain_all(p))) return rc;
+    hipStream_t s = p->lanes[0].stream;
+    if ((rc = pc_prepare(p, P, B))) return rc;
+    const PcDesc& d = p->pc_d;
+    if ((rc = s3_reserve(p->pc_in, d.in_elems * p->esz)) || (rc = s3_reserve(p->pc_out, d.out_elems * p->esz))) return rc;
+    HIPCHK(hipMemsetAsync(p->pc_in.p, 0, d.in_elems * p->esz, s));   // zeros: the times do not depend on the values
+    for (int st = 0; st < 3; ++st) {
+        auto run = [&]() -> int { return pc_launches(p, p->pc_in.p, p->g.N * P, p->pc_out.p, s, st); };
+        if ((rc = time_launches(s, iters, run, &ms_out[st]))) return rc;
+    }
+    if (bytes_out) {
+        bytes_out[0] = (int64_t)p->esz * ((int64_t)P * d.g.nU * B + (int64_t)d.z_elems);
+        bytes_out[1] = (int64_t)p->esz * (int64_t)(d.z_elems + d.out_elems) + (int64_t)p->rsz * (int64_t)d.mag_elems;
+        bytes_out[2] = 2 * (int64_t)p->esz * (int64_t)d.out_elems;
     }
     return RSP_OK;
 }

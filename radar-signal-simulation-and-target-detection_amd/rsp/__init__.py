@@ -16,6 +16,10 @@ Drop-in for the MATLAB reference's per-frame chain
   MTD_win, nfft, ...)`` -- fun_run_goca_cfar_8, fun_parameter_estimation_9 and the two clustering stages
   (fsf:172-407) on a range-Doppler cube of any shape, alone or behind the zero-padded MTD
   (main_simulate_echoes_with_array_v7_7.m:501-...)
+* ``pulse_compress(iq_data_13beam, config, precomputed_data)`` / ``beams_detect(iq_data_13beam, MTD_win,
+  nfft, ...)`` / ``raw_detect(raw_iq_data, DBF_coeffs_data_C, MTD_win, nfft, ...)`` -- the three-segment
+  pulse compression of any number of pulses and beams (main_simulate_echoes_with_array_v7_7.m:362-486), alone
+  or as the front of the zero-padded MTD and the detector, from the beams or from the raw frame
 * ``precompute(...)`` -- the driver's "%% 3" section (v8:79-155)
 * ``load_frame`` / ``save_frame`` -- the ``frame_sim_array_%d.mat`` load/save pair
   (main_simulate_echoes_with_array_v2.m:285, debug_simulated_data_processing_v3.m:20-22)
@@ -33,7 +37,7 @@ from .config import (named_config, make_config, default_cfar_params, default_clu
                      debug_v2_cfar_config, v3_cfar_params)
 from .precompute import precompute
 from .plan import (Plan, process_targets_multi, describe_vcfar, describe_dbf, describe_xcfar, describe_mtd, mtd_table,
-                   describe_detect)
+                   describe_detect, describe_pc)
 from ._abi import RspError
 from .matio import load_frame, save_frame
 from .music import MusicPlan, MUSIC_1D, MusicPlan2D, MUSIC_2D
@@ -211,6 +215,68 @@ def mtd_detect(pc_results, MTD_win, nfft, cfar_params, cluster_params, precomput
     return p.mtd_detect(pc_results, MTD_win, n, cfar_params, cluster_params, pre['range_axis'], velocity_axis,
                         pre['deltaR'], pre['deltaV'], pre['beam_angles_deg'], pre['k_slopes_LUT'], monopulse,
                         want_rdm=want_rdm, want_cfar=want_cfar)
+
+
+_PC_PLAN_PULSES = 16   # the pulse count of the plans behind pulse_compress / beams_detect / raw_detect
+
+
+def _pc_plan(config, precomputed_data, device, precision):
+    """The cached plan behind the three calls below: ``config``'s waveform, gate layout and filters with a
+    pulse count every plan accepts, so that a ``config`` whose prtNum a plan refuses (odd, 333) works.
+    The stage reads neither prtNum nor the per-pulse tables, which are cut or padded to that count."""
+    n = _PC_PLAN_PULSES
+    cfg = dict(config, Sig_Config=dict(config['Sig_Config'], prtNum=n))
+
+    def fit(x):
+        x = np.asarray(x, float).ravel()
+        return np.concatenate([x[:n], np.zeros(max(n - x.size, 0))])
+
+    pre = dict(precomputed_data, MTD_win=fit(precomputed_data['MTD_win']),
+               velocity_axis=fit(precomputed_data['velocity_axis']))
+    return _plan_for(cfg, default_cfar_params(), default_cluster_params(), pre, device, precision)
+
+
+def pulse_compress(iq_data_13beam, config, precomputed_data, device=0, precision='c128'):
+    """Section 6 of main_simulate_echoes_with_array_v7_7.m (:362-486; fun_process_single_frame.m:99-127):
+    the three-segment pulse compression of every pulse of every beam.  ``iq_data_13beam`` is the DBF's
+    result [prtNum, point_PRT, beam_num]; the pulse and beam counts are the array's, any number of either
+    (odd, prime, one), whatever ``config`` says.  ``config`` and ``precomputed_data`` give the waveform, the
+    gate layout and the matched filters.  Returns PC_results, complex128 [prtNum, N_total_gate, beam_num]."""
+    return _pc_plan(config, precomputed_data, device, precision).pulse_compress(iq_data_13beam)
+
+
+def _chain_velocity_axis(velocity_axis, v_max, n, pre):
+    if velocity_axis is None:
+        velocity_axis = mtd_velocity_axis(v_max, n) if v_max is not None else pre['velocity_axis']
+    return velocity_axis
+
+
+def beams_detect(iq_data_13beam, MTD_win, nfft, cfar_params, cluster_params, config, precomputed_data,
+                 velocity_axis=None, v_max=None, monopulse='amplitude', device=0, precision='c128', want_rdm=False,
+                 want_cfar=False):
+    """main_simulate_echoes_with_array_v7_7.m sections 6-10 from the beams on: ``pulse_compress``,
+    ``mtd_doppler(.., MTD_win, nfft)`` and ``detect_rdm`` without the cubes leaving the device.  The
+    arguments after ``nfft`` are ``mtd_detect``'s, with ``config`` as ``pulse_compress`` takes it."""
+    pre = precomputed_data
+    n = int(nfft) if nfft else np.asarray(iq_data_13beam).shape[0]
+    p = _pc_plan(config, pre, device, precision)
+    return p.pc_mtd_detect(iq_data_13beam, MTD_win, n, cfar_params, cluster_params, pre['range_axis'],
+                           _chain_velocity_axis(velocity_axis, v_max, n, pre), pre['deltaR'], pre['deltaV'],
+                           pre['beam_angles_deg'], pre['k_slopes_LUT'], monopulse, want_rdm=want_rdm, want_cfar=want_cfar)
+
+
+def raw_detect(raw_iq_data, DBF_coeffs_data_C, MTD_win, nfft, cfar_params, cluster_params, config, precomputed_data,
+               conj=True, velocity_axis=None, v_max=None, monopulse='amplitude', device=0, precision='c128',
+               want_rdm=False, want_cfar=False):
+    """main_simulate_echoes_with_array_v7_7.m sections 5-10 from the raw frame on: ``dbf_beams(raw_iq_data,
+    DBF_coeffs_data_C, conj)`` and ``beams_detect`` on its result without leaving the device.
+    ``raw_iq_data`` is [prtNum, point_PRT, channel_num], ``DBF_coeffs_data_C`` [beam_num, channel_num]."""
+    pre = precomputed_data
+    n = int(nfft) if nfft else np.asarray(raw_iq_data).shape[0]
+    p = _pc_plan(config, pre, device, precision)
+    return p.raw_detect(raw_iq_data, DBF_coeffs_data_C, conj, MTD_win, n, cfar_params, cluster_params, pre['range_axis'],
+                        _chain_velocity_axis(velocity_axis, v_max, n, pre), pre['deltaR'], pre['deltaV'],
+                        pre['beam_angles_deg'], pre['k_slopes_LUT'], monopulse, want_rdm=want_rdm, want_cfar=want_cfar)
 
 
 def process_frame_stage2(raw_iq_data, angle, config, DBF_coeffs_data_C, conj=True, gate_cols=None,

@@ -163,6 +163,14 @@ class DetectInfo(ct.Structure):
                [('cells_under_test', ct.c_int64), ('max_detections', ct.c_int64)]
 
 
+class PcInfo(ct.Structure):
+    _fields_ = [(n, ct.c_int32) for n in ('P', 'B', 'N', 'G', 'nU', 'n_intervals', 'NZ', 'nzc')] + \
+               [('z_elems', ct.c_int64)] + \
+               [(n, ct.c_int32) for n in ('pack_rows', 'pack_cols', 'unpack_rows', 'unpack_cols', 'pack_wg', 'k2_wg',
+                                          'unpack_wg', 'k2_wg_per_cu', 'pack_lds_bytes', 'unpack_lds_bytes')] + \
+               [('ivl_lo', ct.c_int32 * 4), ('ivl_start', ct.c_int32 * 4)]
+
+
 RSP_MTD_MAX_NFFT = 2048
 RSP_MTD_ROUTE_POW2, RSP_MTD_ROUTE_CHIRPZ, RSP_MTD_ROUTE_DIRECT = 0, 1, 2
 
@@ -388,6 +396,18 @@ PROTOTYPES = {
     'rsp_process_stage2_detect': (ct.c_int32, [_P, _P, ct.c_int32, ct.POINTER(FrameOut)]),
     'rsp_profile_detect': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, ct.POINTER(CfarParams), ct.c_int32,
                                         ct.POINTER(ct.c_float), ct.POINTER(ct.c_int64)]),
+    'rsp_query_pc': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.POINTER(PcInfo)]),
+    'rsp_plan_describe_pc': (ct.c_int32, [ct.POINTER(SigConfig), ct.POINTER(CfarParams), ct.POINTER(ClusterParams),
+                                          ct.POINTER(Precomputed), ct.POINTER(PlanOptions), ct.c_int32, ct.c_int32,
+                                          ct.c_int32, ct.POINTER(PcInfo)]),
+    'rsp_pc': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, _P, ct.c_int32, _dp]),
+    'rsp_pc_device': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, _P, _P]),
+    'rsp_pc_mtd_detect': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, _P, ct.c_int32, _dp,
+                                       ct.POINTER(DetectParams), ct.POINTER(FrameOut)]),
+    'rsp_raw_detect': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, _P, ct.c_int32, _dp, ct.c_int32,
+                                    _dp, ct.POINTER(DetectParams), ct.POINTER(FrameOut)]),
+    'rsp_profile_pc': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, ct.POINTER(ct.c_float),
+                                    ct.POINTER(ct.c_int64)]),
     'rsp_device_alloc': (ct.c_int32, [_P, ct.c_int64, ct.POINTER(_P)]),
     'rsp_device_free': (ct.c_int32, [_P, _P]),
     'rsp_device_upload': (ct.c_int32, [_P, _P, _P, ct.c_int64]),

@@ -361,6 +361,27 @@ def describe_mtd(P, G, nfft=None, precision='c128'):
     return d
 
 
+def _pc_dict(info):
+    d = {k: getattr(info, k) for k, _ in _abi.PcInfo._fields_}
+    for k in ('ivl_lo', 'ivl_start'):
+        d[k] = list(d[k])[:info.n_intervals]
+    return d
+
+
+def describe_pc(config, cfar_params, cluster_params, precomputed_data, P, B, precision='c128', ncu=256):
+    """How the stand-alone pulse compression covers ``P`` pulses of ``B`` beams of this waveform, without a
+    device (rsp_plan_describe_pc): the fields of rsp_pc_info as a dict.  The configuration's own prtNum
+    and beam_num are not read, so one that ``describe`` refuses for its pulse count is accepted.
+    Refusals raise RspError with the code and message ``Plan.pulse_compress`` gives."""
+    keep = []
+    cfg, cfar, cluster, pre = _marshal(config, cfar_params, cluster_params, precomputed_data, keep)
+    opt = _options(0, 1, precision, False, 'amplitude')
+    info = _abi.PcInfo()
+    check(lib().rsp_plan_describe_pc(ct.byref(cfg), ct.byref(cfar), ct.byref(cluster), ct.byref(pre), ct.byref(opt),
+                                     int(ncu), int(P), int(B), ct.byref(info)))
+    return _pc_dict(info)
+
+
 def mtd_table(nfft, precision='c128'):
     """The chirp-z tables of length ``nfft`` as the kernel reads them (rsp_mtd_table): ``(w, Bf)``,
     complex128 arrays that hold the values rounded to ``precision``: w[m] = exp(-i pi (m^2 mod 2 nfft) /
@@ -998,6 +1019,94 @@ class Plan:
         ms, by = (ct.c_float * 3)(), (ct.c_int64 * 3)()
         check(lib().rsp_profile_detect(self.h, int(V), int(G), int(B), ct.byref(prm), int(iters), ms, by))
         return {k: (float(ms[i]), int(by[i])) for i, k in enumerate(('k_pairsum', 'k_xcfar', 'k_s9'))}
+
+    # ---- pulse compression as a stand-alone stage: any pulse count, any beam count -----------------
+    def pc_layout(self, P, B):
+        """How the three launches of ``pulse_compress`` cover ``P`` pulses of ``B`` beams
+        (rsp_query_pc): the fields of rsp_pc_info as a dict, as ``describe_pc``."""
+        info = _abi.PcInfo()
+        check(lib().rsp_query_pc(self.h, int(P), int(B), ct.byref(info)))
+        return _pc_dict(info)
+
+    def _beams3(self, a, what='iq_beams'):
+        a = np.asarray(a)
+        if a.ndim == 2:
+            a = a[:, :, None]
+        if a.ndim != 3 or a.shape[1] != self.N:
+            raise ValueError('%s %r: expected [P, N, B] with N=%d' % (what, a.shape, self.N))
+        return a
+
+    def pulse_compress(self, iq_beams, out=None):
+        """Section 6 of main_simulate_echoes_with_array_v7_7.m (fsf:99-127) on a beam cube ``iq_beams``
+        [P, N, B] with any pulse count P and any beam count B, taken from the array's shape
+        (rsp_pc): -> PC_results [P, G, B] complex128.  The plan gives the device, the precision, N, the
+        gate layout and the filter tables; its own prtNum and beam_num play no part.  ``out``: a
+        Fortran-contiguous complex128 [P, G, B] array to write into."""
+        iq = self._beams3(iq_beams)
+        P, _, B = iq.shape
+        a, ap, dt = _complex_arg(iq)
+        shp = (P, self.G, B)
+        if out is None:
+            out = np.empty(shp, np.complex128, order='F')
+        elif out.shape != shp or out.dtype != np.complex128 or not out.flags.f_contiguous:
+            raise ValueError('out must be a Fortran-contiguous complex128 array of shape %r' % (shp,))
+        check(lib().rsp_pc(self.h, P, B, ap, dt, _dptr(out)))
+        return out
+
+    def pulse_compress_device(self, d_beams, d_pc, P, B):
+        """The same on device memory in the plan's precision (rsp_pc_device): ``d_beams`` [P, N, B] ->
+        ``d_pc`` [P, G, B], pulse index fastest on both sides (what ``mtd_device`` reads); the two must
+        not overlap."""
+        check(lib().rsp_pc_device(self.h, int(P), int(B), ct.c_void_p(d_beams), ct.c_void_p(d_pc)))
+
+    def pc_mtd_detect(self, iq_beams, win=None, nfft=None, cfar=None, cluster=None, range_axis=None, velocity_axis=None,
+                      deltaR=None, deltaV=None, beam_angles_deg=None, k_slopes_LUT=None, monopulse=None, want_rdm=False,
+                      want_cfar=False):
+        """``mtd_detect(pulse_compress(iq_beams), ...)`` without leaving the device (rsp_pc_mtd_detect; v7_7
+        sections 6-10): ``iq_beams`` [P, N, B], the rest as ``mtd_detect``."""
+        iq = self._beams3(iq_beams)
+        P, _, B = iq.shape
+        G, n = self.G, int(nfft) if nfft else P
+        prm, keep = self._detect_params(n, G, B, cfar, cluster, range_axis, velocity_axis, deltaR, deltaV,
+                                        beam_angles_deg, k_slopes_LUT, monopulse)
+        wk, wp = self._mtd_win(win, P)
+        a, ap, dt = _complex_arg(iq)
+        o, bufs = self._detect_out(n, G, B, want_cfar, (n, G, B) if want_rdm else None)
+        check(lib().rsp_pc_mtd_detect(self.h, P, B, n, ap, dt, wp, ct.byref(prm), ct.byref(o)))
+        return self._collect(o, bufs, None, None)
+
+    def raw_detect(self, cube, W=None, conj=True, win=None, nfft=None, cfar=None, cluster=None, range_axis=None,
+                   velocity_axis=None, deltaR=None, deltaV=None, beam_angles_deg=None, k_slopes_LUT=None,
+                   monopulse=None, want_rdm=False, want_cfar=False):
+        """``pc_mtd_detect(dbf(cube, W, conj), ...)`` without leaving the device (rsp_raw_detect; v7_7
+        sections 5-10): ``cube`` [P, N, C] raw, ``W`` [B, C] (None: the plan's DBF_coeffs_data_C, for a
+        cube of the plan's C channels)."""
+        cube = self._beams3(cube, 'cube')
+        P, _, C = cube.shape
+        if W is None:
+            B, wk, wp = self.B, None, None
+        else:
+            W = np.asarray(W, np.complex128)
+            if W.ndim != 2 or W.shape[1] != C:
+                raise ValueError('cube %r and W %r: expected [P, N, C] and [B, C]' % (cube.shape, W.shape))
+            B = W.shape[0]
+            wk = np.asfortranarray(W).ravel(order='F').view(np.float64)   # B x C column-major (MATLAB)
+            wp = _dptr(wk)
+        G, n = self.G, int(nfft) if nfft else P
+        prm, keep = self._detect_params(n, G, B, cfar, cluster, range_axis, velocity_axis, deltaR, deltaV,
+                                        beam_angles_deg, k_slopes_LUT, monopulse)
+        mk, mp = self._mtd_win(win, P)
+        a, ap, dt = _complex_arg(cube)
+        o, bufs = self._detect_out(n, G, B, want_cfar, (n, G, B) if want_rdm else None)
+        check(lib().rsp_raw_detect(self.h, P, C, B, n, ap, dt, wp, 1 if conj else 0, mp, ct.byref(prm), ct.byref(o)))
+        return self._collect(o, bufs, None, None)
+
+    def profile_pc(self, P, B, iters=20):
+        """HIP-event times of the three launches of ``pulse_compress`` on zeros (rsp_profile_pc):
+        {'k_pc_pack' | 'k2_pc' | 'k_pc_unpack': (ms, bytes)}."""
+        ms, by = (ct.c_float * 3)(), (ct.c_int64 * 3)()
+        check(lib().rsp_profile_pc(self.h, int(P), int(B), int(iters), ms, by))
+        return {k: (float(ms[i]), int(by[i])) for i, k in enumerate(('k_pc_pack', 'k2_pc', 'k_pc_unpack'))}
 
     def _raw_weights(self, W):
         """(array kept alive, pointer) of the weights of a raw-cube call; None: the plan's own."""
