@@ -2,7 +2,7 @@
 // maps a call returns, the precision conversions, the re-insertion of a gated stage-2 input, the
 // result lists and rows, the synthesis constants of a target list and the profilers' byte counts.
 // Plain C++17 like rsp_geometry.h: rsp_frame_host.cpp builds, runs and is sanitized without a GPU;
-// rsp_plan.cpp keeps the hipMemcpy on either side of these.
+// the plan units (rsp_plan*.cpp) keep the hipMemcpy on either side of these.
 #pragma once
 #include "rsp_geometry.h"   // rsp.h, Geometry, SynthTargets
 

@@ -32,7 +32,7 @@
 #include <thread>
 #include <vector>
 
-__attribute__((visibility("hidden"))) int rsp_set_error(int code, const char* fmt, ...);   // rsp_plan.cpp
+__attribute__((visibility("hidden"))) int rsp_set_error(int code, const char* fmt, ...);   // rsp_host.cpp
 
 namespace {
 
