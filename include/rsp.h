@@ -52,7 +52,9 @@ typedef enum rsp_status {
 
 typedef enum rsp_dtype {
     RSP_C64 = 1,   /* interleaved complex float  */
-    RSP_C128 = 2   /* interleaved complex double (MATLAB) */
+    RSP_C128 = 2,  /* interleaved complex double (MATLAB) */
+    RSP_R32 = 3,   /* real float: rsp_ddc's input only   */
+    RSP_R64 = 4    /* real double: rsp_ddc's input only  */
 } rsp_dtype;
 
 typedef enum rsp_layout {
@@ -913,6 +915,90 @@ int32_t rsp_raw_detect(rsp_plan* plan, int32_t P, int32_t C, int32_t B, int32_t 
  * k_pc_pack, [1] the k2_pc launch, [2] k_pc_unpack.  bytes_out[0] = element bytes x (P nU B read + z written),
  * [1] = z + the result + the scratch magnitude map, [2] = 2 x element bytes x P G B. */
 int32_t rsp_profile_pc(rsp_plan* plan, int32_t P, int32_t B, int32_t iters, float* ms_out, int64_t* bytes_out);
+
+/* ---- digital down-conversion as a stand-alone stage: NCO mixer, FIR, decimator ----
+ * simulation_learn.m:79-102 (xrt = xt .* sin(2*pi*f*t2); firxrt = filter(Num, 1, xrt); downsample(firxrt, 4)):
+ * the receiver's front end, from sampled real IF data to the baseband cube every other call here starts from.
+ * The plan gives only the device, the stream and the precision.
+ *
+ * Input x is real, [P x N x C] in MATLAB's layout (pulse index fastest), dtype RSP_R32 or RSP_R64, converted
+ * to the plan's precision as rsp_process_cube converts.
+ * NCO: a 64-bit phase accumulator.  With uint64 wrap-around phase(n) = w0 + n w; u_n = floor(phase(n) / 2^11)
+ * 2^-53 and theta_n = 2 pi u_n; the phase restarts at w0 in every pulse and every channel.
+ *   RSP_DDC_NCO_IQ    m[n] = cos theta_n - i sin theta_n
+ *   RSP_DDC_NCO_SIN   m[n] = sin theta_n   (the reference's single real mixer, :79)
+ * sin and cos are computed in double by the restricted-domain routine of the synthesis (2 pi u, u in [0, 1];
+ * rsp_noise_math.h) and rounded once to the plan's precision.
+ * Mixer: v[p,n,c] = x[p,n,c] m[n] for 0 <= n < N and 0 elsewhere; each part of v is one product, rounded once.
+ * Filter and decimation: taps h[0..L) are real doubles, rounded once to the plan's precision, 1 <= L <=
+ * RSP_DDC_MAX_TAPS;
+ *   y[p,k,c] = sum_{j=0}^{L-1} h[j] v[p, off + k D - j, c],   k = 0 .. No - 1,  No = ceil((N - off) / D),
+ * 1 <= D <= RSP_DDC_MAX_D, 0 <= off < D (MATLAB's downsample phase): filter(h, 1, .) with zero initial state
+ * followed by downsample(., D, off).  The sum is a chain of fused multiply-adds in ascending j that starts from
+ * 0, separately for the real and the imaginary part; that order is part of the contract and makes the result
+ * independent of the kernel's tiling.
+ * Output: complex [P x No x C] in the same layout (what rsp_dbf and rsp_raw_detect read); in SIN mode the
+ * imaginary part is +0.
+ * Out of scope: complex input, a per-pulse phase step, the FFT pulse compression of simulation_learn.m:112-130
+ * (rsp_pc is the library's pulse compression). */
+#define RSP_DDC_MAX_TAPS 512
+#define RSP_DDC_MAX_D 64
+#define RSP_DDC_NCO_IQ 0
+#define RSP_DDC_NCO_SIN 1
+typedef struct rsp_ddc_params {
+    uint64_t w, w0;           /* phase step per sample and start phase, in 2^-64 turns (rsp_ddc_phase_word) */
+    int32_t mode;             /* RSP_DDC_NCO_*                                                      */
+    int32_t D, off;           /* decimation factor and phase                                        */
+    int32_t L;                /* taps                                                               */
+    const double* h;          /* L taps                                                             */
+} rsp_ddc_params;
+/* How k_ddc covers a cube (rsp_ddc_describe).  A workgroup takes TP pulses x TK outputs of one channel, threads
+ * mapped pulse-fastest and then along k; it stages in_rows = (TK - 1) D + tap_chunk input rows (x as it is read,
+ * and the row's NCO value, once) in LDS.  tap_chunk = L wherever the rows of all L taps fit the LDS budget of a
+ * workgroup (40 KiB); a longer filter is staged tap_chunk taps at a time, the accumulators kept in registers. */
+typedef struct rsp_ddc_info {
+    int32_t P, N, C, L, D, off;
+    int32_t No;               /* outputs per pulse: ceil((N - off) / D)                    */
+    int32_t TP, TK;           /* the tile: TP = least power of two >= min(P, 64) pulses x TK outputs */
+    int32_t in_rows;          /* input rows staged at a time: (TK - 1) D + tap_chunk       */
+    int32_t k_tiles, p_tiles; /* tiles along k and along pulses                            */
+    int32_t workgroups;       /* k_tiles x p_tiles x C                                     */
+    int32_t lds_bytes;        /* dynamic LDS of a workgroup: rows, NCO values and the taps */
+    int32_t tap_chunk;        /* taps whose rows are staged at a time                      */
+    int32_t threads;          /* threads of a workgroup: TP x k lanes, at least one wave   */
+    int32_t k_per_thread;     /* outputs a thread accumulates: TK / (k lanes)              */
+    int64_t in_bytes, out_bytes;   /* the cube and the result in the plan's precision      */
+} rsp_ddc_info;
+/* The size checks of the calls below, with the same refusals and messages, and the kernel's tiling, for a plan
+ * of `precision` (RSP_C128 / RSP_C64).  RSP_ERR_INVALID: P, N or C < 1, L outside 1..RSP_DDC_MAX_TAPS, D
+ * outside 1..RSP_DDC_MAX_D, off outside 0..D-1, unknown precision; RSP_ERR_UNSUPPORTED: 2 GB or more of input
+ * or output (the kernel addresses each with 32-bit byte offsets).  `info` may be NULL.  No HIP call is made. */
+int32_t rsp_ddc_describe(int32_t P, int32_t N, int32_t C, int32_t L, int32_t D, int32_t off, int32_t precision,
+                         rsp_ddc_info* info);
+/* *w = round(f0 / fs 2^64) mod 2^64, computed in long double (a negative f0 wraps).  RSP_ERR_INVALID: f0 or fs
+ * not finite, fs <= 0, w NULL.  No HIP call is made. */
+int32_t rsp_ddc_phase_word(double f0, double fs, uint64_t* w);
+/* x [P x N x C] real (dtype RSP_R32 / RSP_R64) -> out, complex double [P x No x C].  Synchronous; drains the
+ * queue first.  Refusals (sizes, dtype, null pointers and mode, in that order) come before any device work.
+ * Scratch buffers are the plan's, grow on demand and are kept. */
+int32_t rsp_ddc(rsp_plan* plan, int32_t P, int32_t N, int32_t C, const void* x, int32_t dtype,
+                const rsp_ddc_params* params, double* out);
+/* The same on device memory in the plan's precision: d_x [P x N x C] reals -> d_out [P x No x C] complex, which
+ * must not overlap and are aligned to a real and a complex element.  Nothing outside those P No C elements is
+ * written. */
+int32_t rsp_ddc_device(rsp_plan* plan, int32_t P, int32_t N, int32_t C, const void* d_x, const rsp_ddc_params* params,
+                       void* d_out);
+/* rsp_ddc_device into the plan's scratch and then the device chain of rsp_raw_detect on the result (k_dbf,
+ * pulse compression, MTD, detection): the IQ cube never leaves the device.  No must be the plan's point_PRT
+ * (RSP_ERR_INVALID otherwise, with the two numbers).  The arguments are rsp_ddc's followed by rsp_raw_detect's;
+ * the outputs are rsp_raw_detect's. */
+int32_t rsp_ddc_raw_detect(rsp_plan* plan, int32_t P, int32_t N, int32_t C, const void* x, int32_t dtype,
+                           const rsp_ddc_params* params, int32_t B, int32_t nfft, const double* W, int32_t conj,
+                           const double* win, const rsp_detect_params* dparams, rsp_frame_out* out);
+/* Device time of k_ddc alone on a cube of zeros (taps of zero, IQ mode, w = 2^64 / 10), by HIP events on the
+ * plan's stream, averaged over `iters` launches; *bytes_out = the input plus the output in the plan's precision. */
+int32_t rsp_profile_ddc(rsp_plan* plan, int32_t P, int32_t N, int32_t C, int32_t L, int32_t D, int32_t off,
+                        int32_t iters, float* ms_out, int64_t* bytes_out);
 
 /* ---- measurement ----
  * Time each device stage `iters` times on the plan's stream with HIP events.  Each launch

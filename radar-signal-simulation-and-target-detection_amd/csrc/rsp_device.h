@@ -1,5 +1,5 @@
 // rsp_device.h -- what every device translation unit of the frame chain shares (rsp_k1.hip,
-// rsp_k2.hip, rsp_k3.hip, rsp_frame_aux.hip, rsp_stage3.hip, rsp_vcfar.hip, rsp_xcfar.hip, rsp_dbf.hip, rsp_mtd.hip, rsp_detect.hip, rsp_pc.hip): the complex types and
+// rsp_k2.hip, rsp_k3.hip, rsp_frame_aux.hip, rsp_stage3.hip, rsp_vcfar.hip, rsp_xcfar.hip, rsp_dbf.hip, rsp_mtd.hip, rsp_detect.hip, rsp_pc.hip, rsp_ddc.hip): the complex types and
 // arithmetic, the raw buffer-resource loads and stores, the dynamic LDS block, the z addressing and
 // the host-side launch helper.  No kernel.  Everything is in the anonymous namespace or static, so
 // each unit gets its own copy and no unit exports a helper.

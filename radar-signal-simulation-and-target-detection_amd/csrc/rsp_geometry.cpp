@@ -1322,3 +1322,86 @@ extern "C" int32_t rsp_plan_describe_pc(const rsp_sig_config* cfg, const rsp_cfa
     rsp_fill_pc_info(d, info);
     return RSP_OK;
 }
+
+// ---- digital down-conversion (k_ddc) ----
+int rsp_ddc_derive(int64_t P, int64_t N, int64_t C, int64_t L, int64_t D, int64_t off, int precision, DdcDesc* out) {
+    if (precision != RSP_C64 && precision != RSP_C128)
+        return fail(RSP_ERR_INVALID, "precision must be RSP_C128 or RSP_C64, got %d", precision);
+    if (P < 1 || N < 1 || C < 1)
+        return fail(RSP_ERR_INVALID, "bad sizes P=%lld N=%lld C=%lld (P, N, C >= 1)", (long long)P, (long long)N, (long long)C);
+    if (L < 1 || L > RSP_DDC_MAX_TAPS)
+        return fail(RSP_ERR_INVALID, "L=%lld taps: 1 <= L <= RSP_DDC_MAX_TAPS = %d", (long long)L, RSP_DDC_MAX_TAPS);
+    if (D < 1 || D > RSP_DDC_MAX_D) return fail(RSP_ERR_INVALID, "D=%lld: 1 <= D <= RSP_DDC_MAX_D = %d", (long long)D, RSP_DDC_MAX_D);
+    if (off < 0 || off >= D) return fail(RSP_ERR_INVALID, "off=%lld: 0 <= off < D = %lld", (long long)off, (long long)D);
+    // the input (reals) and the output (complex) each under 2 GB: the kernel's buffer resources take 32-bit
+    // byte offsets.  No <= N, so the three counts and P N C bound every product below.
+    const int64_t rs = precision == RSP_C128 ? 8 : 4, lim = (int64_t)1 << 31;
+    const int64_t No = off < N ? (N - off + D - 1) / D : 0;
+    if (P >= lim || N >= lim || C >= lim || P * N >= lim || P * N * C >= lim || P * N * C * rs >= lim ||
+        P * No * C * 2 * rs >= lim)
+        return fail(RSP_ERR_UNSUPPORTED,
+                    "%lld pulses x %lld samples x %lld channels, %lld outputs a pulse: the kernel addresses the input and the result with 32-bit offsets (< 2 GB each)",
+                    (long long)P, (long long)N, (long long)C, (long long)No);
+    DdcDesc d{};
+    d.P = (int)P; d.N = (int)N; d.C = (int)C; d.No = (int)No;
+    d.L = (int)L; d.D = (int)D; d.off = (int)off;
+    d.TP = 1;
+    while (d.TP < 64 && d.TP < d.P) d.TP *= 2;
+    d.lgTP = ilog2i(d.TP);
+    // rows of TP reals and one complex NCO value that fit the budget beside the taps
+    const int row_bytes = (int)rs * (d.TP + 2), R = (int)((RSP_DDC_LDS_BUDGET - 16 - L * rs) / row_bytes);
+    d.KL = RSP_DDC_THREADS / d.TP;
+    while (d.KL > 1 && (d.KL - 1) * d.D + std::min(d.L, 16) > R) d.KL /= 2;
+    d.LC = std::min(d.L, R - (d.KL - 1) * d.D);
+    d.KPT = 1;
+    while (d.KPT < RSP_DDC_MAX_KPT && d.KL * d.KPT < d.No && (d.KL * (d.KPT + 1) - 1) * d.D + d.LC <= R) ++d.KPT;
+    d.TK = d.KL * d.KPT;
+    d.rows = (d.TK - 1) * d.D + d.LC;
+    d.k_tiles = (d.No + d.TK - 1) / d.TK;   // No = 0 (N <= off): nothing to launch
+    d.p_tiles = (d.P + d.TP - 1) / d.TP;
+    d.threads = std::max(64, d.TP * d.KL);
+    d.in_bytes = (unsigned)(P * N * C * rs);
+    ddc_set_opitch(&d, (unsigned)(P * No), (unsigned)(2 * rs));
+    d.ms_bytes = ((unsigned)d.rows * 2u * (unsigned)rs + 15u) & ~15u;
+    d.lds_bytes = d.ms_bytes + (unsigned)d.rows * (unsigned)d.TP * (unsigned)rs + (unsigned)d.L * (unsigned)rs;
+    if (out) *out = d;
+    return RSP_OK;
+}
+
+void rsp_fill_ddc_info(const DdcDesc& d, int precision, rsp_ddc_info* out) {
+    *out = rsp_ddc_info{};
+    out->P = d.P; out->N = d.N; out->C = d.C; out->L = d.L; out->D = d.D; out->off = d.off;
+    out->No = d.No;
+    out->TP = d.TP; out->TK = d.TK;
+    out->in_rows = d.rows;
+    out->k_tiles = d.k_tiles; out->p_tiles = d.p_tiles;
+    out->workgroups = d.k_tiles * d.p_tiles * d.C;
+    out->lds_bytes = (int32_t)d.lds_bytes;
+    out->tap_chunk = d.LC;
+    out->threads = d.threads;
+    out->k_per_thread = d.KPT;
+    out->in_bytes = d.in_bytes;
+    out->out_bytes = d.out_bytes;
+}
+
+extern "C" int32_t rsp_ddc_describe(int32_t P, int32_t N, int32_t C, int32_t L, int32_t D, int32_t off, int32_t precision,
+                                    rsp_ddc_info* info) {
+    DdcDesc d;
+    const int rc = rsp_ddc_derive(P, N, C, L, D, off, precision, &d);
+    if (rc || !info) return rc;
+    rsp_fill_ddc_info(d, precision, info);
+    return RSP_OK;
+}
+
+extern "C" int32_t rsp_ddc_phase_word(double f0, double fs, uint64_t* w) {
+    if (!w) return fail(RSP_ERR_INVALID, "null argument");
+    if (!std::isfinite(f0) || !std::isfinite(fs) || !(fs > 0))
+        return fail(RSP_ERR_INVALID, "f0=%g fs=%g: both finite, fs > 0", f0, fs);
+    // the fraction of a turn per sample in [0, 1), then 64 bits of it: the product is below 2^64 + 1/2, and a
+    // value that rounds to 2^64 is the word 0
+    long double t = (long double)f0 / (long double)fs;
+    t -= std::floor(t);
+    const long double s = std::nearbyint(std::ldexp(t, 64));
+    *w = s >= 18446744073709551616.0L ? 0 : (uint64_t)s;
+    return RSP_OK;
+}

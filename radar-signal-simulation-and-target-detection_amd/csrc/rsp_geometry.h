@@ -532,6 +532,40 @@ struct PcDesc {
 int rsp_pc_derive(const Geometry& base, int64_t P, int64_t B, PcDesc* out, std::vector<K2Rec>* rec);
 void rsp_fill_pc_info(const PcDesc& d, rsp_pc_info* out);
 
+// ---- digital down-conversion (k_ddc, rsp_ddc.hip) ----
+// A workgroup takes TP pulses x TK outputs of one channel, TP = the least power of two >= min(P, 64); thread t
+// has pulse t mod TP and k lane t / TP of KL, and accumulates KPT outputs, k lane + i KL: TK = KL KPT.  It
+// stages rows = (TK - 1) D + LC input rows at a time: x as it is read, TP reals a row, and the row's NCO value,
+// one complex; the L taps lie behind them.  RSP_DDC_LDS_BUDGET bounds the three together (four workgroups a CU).
+// The host chooses KL (256 / TP, halved while KL lanes and 16 taps do not fit), then LC (L, or what fits: a
+// longer filter is staged LC taps at a time) and then KPT (up to RSP_DDC_MAX_KPT, while the rows fit and the
+// tile is not longer than the outputs).
+#define RSP_DDC_THREADS 256
+#define RSP_DDC_MAX_KPT 8
+#define RSP_DDC_LOADS 8   // 16-byte loads a thread keeps in flight while it stages a tile
+constexpr size_t RSP_DDC_LDS_BUDGET = 40 * 1024;
+struct DdcDesc {          // kernel argument
+    int P, N, C, No;
+    int L, D, off, mode;
+    int TP, lgTP, KL, KPT, TK, LC, rows;
+    int k_tiles, p_tiles, threads;
+    unsigned opitch;                // complex elements between the output's channel planes: P No, or k_dbf's pitch
+    unsigned in_bytes, out_bytes;   // the buffer resources' ranges: P N C reals, C opitch complex elements
+    unsigned ms_bytes;              // LDS: the NCO values, rounded up to 16 bytes; x follows, then the taps
+    unsigned lds_bytes;
+    uint64_t w, w0;
+};
+static_assert(sizeof(DdcDesc) == 112, "kernel-argument layout");
+// The checks of the rsp_ddc calls and rsp_ddc_describe that need no device, and the kernel argument (mode, w
+// and w0 left 0, the output contiguous).  precision: RSP_C128 / RSP_C64.  RSP_OK, or the refusal with its message set.
+int rsp_ddc_derive(int64_t P, int64_t N, int64_t C, int64_t L, int64_t D, int64_t off, int precision, DdcDesc* out);
+// The output's channel planes `opitch` >= P No complex elements apart (C opitch elements under 2 GB: the caller's check)
+inline void ddc_set_opitch(DdcDesc* d, unsigned opitch, unsigned esz) {
+    d->opitch = opitch;
+    d->out_bytes = (unsigned)d->C * opitch * esz;
+}
+void rsp_fill_ddc_info(const DdcDesc& d, int precision, rsp_ddc_info* out);
+
 // The checks of rsp_plan_create_ex that need no device and come before its device checks.
 int rsp_plan_check_args(const rsp_sig_config* cfg, const rsp_cfar_params* cfar, const rsp_cluster_params* cluster,
                         const rsp_precomputed* pre, const rsp_plan_options* opt);

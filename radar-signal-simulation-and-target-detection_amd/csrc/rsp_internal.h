@@ -132,6 +132,11 @@ hipError_t launch_s9(const DetDesc& d, int prec, int layout, const DevConsts& k,
 // either launcher takes element pairs in complex single where the caller's side is aligned for them.
 hipError_t launch_pc_pack(const PcDesc& d, const void* beams, int pitch, void* z, hipStream_t s);
 hipError_t launch_pc_unpack(const PcDesc& d, const void* res, void* pc, hipStream_t s);
+// Digital down-conversion (rsp_ddc.hip): x [P x N x C] reals of the precision -> y [P x No x C] complex of the
+// precision, its channel planes d.opitch elements apart; h = d.L taps as reals of the precision (device memory);
+// d.mode, d.w and d.w0 are the call's.  y is aligned to a complex element; x takes 16-byte loads where it is
+// aligned for them.  d.No = 0: no launch.
+hipError_t launch_ddc(const DdcDesc& d, int prec, const void* x, const void* h, void* y, hipStream_t s);
 // Queue read-back: count record + the detections of nf frames (device stride dcap + 1 records) into
 // mapped pinned host memory (stride hcap + 1), only the records that exist.
 hipError_t launch_dets_to_host(const void* dets, int dcap, void* host, int hcap, int nf, hipStream_t s);

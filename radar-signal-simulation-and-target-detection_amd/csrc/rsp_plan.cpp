@@ -90,7 +90,8 @@ rsp_plan::~rsp_plan() {
     if (up_stream) (void)hipStreamDestroy(up_stream);
     if (h_stage) (void)hipHostFree(h_stage);
     for (DevBuf* b : {&s3_in, &s3_amp, &s3_thr, &s3_flags, &s3_hits, &s3_count, &dbf_in, &dbf_out, &dbf_tab, &raw_tab, &mtd_in, &mtd_out,
-                      &mtd_win, &det_in, &det_smap, &det_dets, &det_axes, &pc_in, &pc_z, &pc_res, &pc_mag, &pc_out, &pc_rec})
+                      &mtd_win, &det_in, &det_smap, &det_dets, &det_axes, &pc_in, &pc_z, &pc_res, &pc_mag, &pc_out, &pc_rec,
+                      &ddc_in, &ddc_out, &ddc_h})
         if (b->p) (void)hipFree(b->p);
     for (auto* m : {&mtd_tab, &mtd_tw})
         for (auto& kv : *m) (void)hipFree(kv.second);
@@ -443,14 +444,18 @@ int ensure_stage(rsp_plan* p, size_t bytes) {
 
 }  // namespace
 
-int host_in_plan_prec(rsp_plan* p, const void* h, int dtype, size_t elems, const void** src) {
+int host_reals_in_plan_prec(rsp_plan* p, const void* h, bool f64, size_t reals, const void** src) {
     *src = h;
-    if ((dtype == RSP_C128) == (p->g.prec == RSP_PREC_F64)) return RSP_OK;
-    int rc = ensure_stage(p, elems * p->esz);
+    if (f64 == (p->g.prec == RSP_PREC_F64)) return RSP_OK;
+    int rc = ensure_stage(p, reals * p->rsz);
     if (rc) return rc;
-    rsp_convert_reals(h, dtype, 2 * elems, p->h_stage);
+    rsp_convert_reals(h, f64 ? RSP_C128 : RSP_C64, reals, p->h_stage);
     *src = p->h_stage;
     return RSP_OK;
+}
+
+int host_in_plan_prec(rsp_plan* p, const void* h, int dtype, size_t elems, const void** src) {
+    return host_reals_in_plan_prec(p, h, dtype == RSP_C128, 2 * elems, src);
 }
 
 int download_widened(rsp_plan* p, const void* d_src, size_t elems, double* out, hipStream_t s) {

@@ -1,7 +1,7 @@
 // rsp_plan.h -- what the units of the host runtime share (private: not installed): struct rsp_plan with
 // its lanes, and the helpers more than one of rsp_plan.cpp (the plan, the queue, the synchronous frame
 // paths), rsp_plan_cfar.cpp (stage 2 and the CFAR call family) and rsp_plan_calls.cpp (the stand-alone
-// DBF, MTD, detection and pulse-compression calls) uses.
+// DBF, MTD, detection, pulse-compression and down-conversion calls) uses.
 #pragma once
 #include "rsp.h"
 #include "rsp_frame_host.h"
@@ -121,6 +121,8 @@ struct rsp_plan {
     // they change (pc_d.g.P = 0: none yet)
     DevBuf pc_in, pc_z, pc_res, pc_mag, pc_out, pc_rec;
     PcDesc pc_d{};
+    // digital down-conversion (rsp_ddc and its composition): the call's real cube, its complex result and taps
+    DevBuf ddc_in, ddc_out, ddc_h;
     // raw-cube stage 2 (rsp_process_raw_stage2*): the plan's own weights, and the A operands of the last
     // call whose W / conj were not the plan's (K1's layout; uploaded again only when they change)
     std::vector<double> h_W;
@@ -222,6 +224,8 @@ int dev_reserve(rsp_plan::DevBuf& b, size_t bytes);
 // *src = h when the dtypes agree, else the plan's pinned staging buffer after rsp_convert_reals.  Either is
 // borrowed until the caller has waited for its copy.
 int host_in_plan_prec(rsp_plan* p, const void* h, int dtype, size_t elems, const void** src);
+// The same for `reals` real values, doubles (f64) or floats
+int host_reals_in_plan_prec(rsp_plan* p, const void* h, bool f64, size_t reals, const void** src);
 // `elems` complex values of the plan's precision, device to host on stream s and waited for, widened to double
 int download_widened(rsp_plan* p, const void* d_src, size_t elems, double* out, hipStream_t s);
 // Copy a host cube (complex64 or complex128, nch channel slabs of N x P) into d_dst in the

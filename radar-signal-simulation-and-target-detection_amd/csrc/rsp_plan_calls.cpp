@@ -1,7 +1,7 @@
 // rsp_plan_calls.cpp -- the stand-alone calls of librsp's host runtime on arrays of any size within the plan's
 // envelope, and their compositions: DBF (k_dbf), MTD of any length (k_mtd_any), detection on any RD cube
-// (k_pairsum -> k_xcfar -> k_s9 -> S10 / S11) and pulse compression for any pulse and beam count
-// (k_pc_pack -> k2_pc -> k_pc_unpack).
+// (k_pairsum -> k_xcfar -> k_s9 -> S10 / S11), pulse compression for any pulse and beam count
+// (k_pc_pack -> k2_pc -> k_pc_unpack) and the digital down-converter in front of them (k_ddc).
 #include "rsp_plan.h"
 
 extern "C" {
@@ -16,20 +16,28 @@ static int dbf_reserve(rsp_plan* p, int S, int C, int B, DbfDesc* d) {
     return dev_reserve(p->dbf_tab, (size_t)kc.MB * kc.NJ * 2 * 64 * p->rsz);
 }
 
+// k_dbf on stream s from the channel planes in p->dbf_in into p->dbf_out (dbf_reserve done), after the A
+// operands of W
+static int dbf_launch_planes(rsp_plan* p, const DbfDesc& d, int C, int B, const double* W, int conj, hipStream_t s) {
+    std::vector<double> t;
+    rsp_dbf_atab(W, B, C, conj, p->g.prec == RSP_PREC_F64 ? DBF_ROWS_SPLIT : DBF_ROWS_PAIR, t);
+    const int rc = p->put_reals(p->dbf_tab.p, t.data(), t.size());
+    if (rc) return rc;
+    HIPCHK(launch_dbf(d, p->g.prec, p->dbf_in.p, p->dbf_tab.p, p->dbf_out.p, s));
+    return RSP_OK;
+}
+
 // The device half of a DBF call on stream s, into p->dbf_out (dbf_reserve done): the A operands of W, the
 // host cube's S x C channel planes at the kernel's pitch, k_dbf.  No wait: the caller's cube (or the staging
 // buffer) is borrowed until the caller has waited for s.
 static int dbf_launch_host(rsp_plan* p, const DbfDesc& d, size_t S, int C, int B, const void* cube, int dtype,
                            const double* W, int conj, hipStream_t s) {
     const size_t esz = p->esz;
-    std::vector<double> t;
-    rsp_dbf_atab(W, B, C, conj, p->g.prec == RSP_PREC_F64 ? DBF_ROWS_SPLIT : DBF_ROWS_PAIR, t);
     const void* src;
-    int rc = p->put_reals(p->dbf_tab.p, t.data(), t.size());
-    if (rc || (rc = host_in_plan_prec(p, cube, dtype, S * C, &src))) return rc;
+    const int rc = host_in_plan_prec(p, cube, dtype, S * C, &src);
+    if (rc) return rc;
     HIPCHK(hipMemcpy2DAsync(p->dbf_in.p, (size_t)d.pitch * esz, src, S * esz, S * esz, C, hipMemcpyHostToDevice, s));
-    HIPCHK(launch_dbf(d, p->g.prec, p->dbf_in.p, p->dbf_tab.p, p->dbf_out.p, s));
-    return RSP_OK;
+    return dbf_launch_planes(p, d, C, B, W, conj, s);
 }
 
 int32_t rsp_dbf(rsp_plan* p, int32_t P, int32_t N, int32_t C, int32_t B, const void* cube, int32_t dtype, const double* W,
@@ -506,27 +514,47 @@ int32_t rsp_pc_mtd_detect(rsp_plan* p, int32_t P, int32_t B, int32_t nfft, const
     return mtd_detect_tail(p, P, p->g.G, B, n, xd, k, win, prm, out, s);
 }
 
+// The checks of rsp_raw_detect for a cube `in` of P x the plan's N x C, in three steps (the entry's dtype check
+// lies between the first two), and its buffers: the sizes of the three stages ...
+static int raw_sizes(const rsp_plan* p, int P, int C, int B, int nfft, const rsp_detect_params* prm, int* n, XcDesc* xd) {
+    int rc = pc_sizes(p, P, B, nullptr);
+    if (rc || (rc = rsp_dbf_check_sizes(P, p->g.N, C, B, plan_dtype(p)))) return rc;
+    return pc_chain_sizes(p, P, B, nfft, prm, n, xd);
+}
+// ... the pointers and the weights ...
+static int raw_args(const rsp_plan* p, const void* in, int C, int B, const double* W, const rsp_detect_params* prm,
+                    const rsp_frame_out* out) {
+    const int rc = det_args(p, in, prm, out, true);
+    if (rc) return rc;
+    if (!W && (B != p->g.B || C != p->g.C))
+        return fail(RSP_ERR_INVALID, "W = NULL takes the plan's weights, %d x %d; the call has B=%d C=%d", p->g.B, p->g.C, B, C);
+    return RSP_OK;
+}
+// ... and, the queue drained, the detector's constants and the scratch of every stage
+static int raw_reserve(rsp_plan* p, int P, int C, int B, int n, const rsp_detect_params* prm, DevConsts* k, DbfDesc* dd) {
+    const int G = p->g.G;
+    const size_t S = (size_t)P * p->g.N, esz = p->esz;
+    int rc;
+    if ((rc = det_consts(p, n, G, B, prm, k)) || (rc = dev_reserve(p->mtd_out, (size_t)G * B * n * esz)) ||
+        (rc = dev_reserve(p->mtd_in, (size_t)G * B * P * esz)) || (rc = dbf_reserve(p, (int)S, C, B, dd)))
+        return rc;
+    return pc_prepare(p, P, B);
+}
+
 int32_t rsp_raw_detect(rsp_plan* p, int32_t P, int32_t C, int32_t B, int32_t nfft, const void* cube, int32_t dtype,
                        const double* W, int32_t conj, const double* win, const rsp_detect_params* prm, rsp_frame_out* out) {
     int n = 0;
     XcDesc xd;
-    int rc = pc_sizes(p, P, B, nullptr);
-    if (rc || (rc = rsp_dbf_check_sizes(P, p->g.N, C, B, plan_dtype(p))) || (rc = pc_chain_sizes(p, P, B, nfft, prm, &n, &xd)))
-        return rc;
+    int rc = raw_sizes(p, P, C, B, nfft, prm, &n, &xd);
+    if (rc) return rc;
     if (dtype != RSP_C64 && dtype != RSP_C128) return fail(RSP_ERR_INVALID, "unknown dtype %d", dtype);
-    if ((rc = det_args(p, cube, prm, out, true))) return rc;
-    if (!W && (B != p->g.B || C != p->g.C))
-        return fail(RSP_ERR_INVALID, "W = NULL takes the plan's weights, %d x %d; the call has B=%d C=%d", p->g.B, p->g.C, B, C);
+    if ((rc = raw_args(p, cube, C, B, W, prm, out))) return rc;
     if ((rc = begin_sync(p))) return rc;
     hipStream_t s = p->lanes[0].stream;
-    const int G = p->g.G;
-    const size_t S = (size_t)P * p->g.N, esz = p->esz;
+    const size_t S = (size_t)P * p->g.N;
     DevConsts k;
     DbfDesc dd;
-    if ((rc = det_consts(p, n, G, B, prm, &k)) || (rc = dev_reserve(p->mtd_out, (size_t)G * B * n * esz)) ||
-        (rc = dev_reserve(p->mtd_in, (size_t)G * B * P * esz)) || (rc = dbf_reserve(p, (int)S, C, B, &dd)) ||
-        (rc = pc_prepare(p, P, B)))
-        return rc;
+    if ((rc = raw_reserve(p, P, C, B, n, prm, &k, &dd))) return rc;
     if ((rc = dbf_launch_host(p, dd, S, C, B, cube, dtype, W ? W : p->h_W.data(), conj, s))) return rc;
     HIPCHK(hipStreamSynchronize(s));   // the caller's cube (or the staging buffer) is borrowed until here
     if ((rc = pc_launches(p, p->dbf_out.p, dd.opitch, p->mtd_in.p, s))) return rc;
@@ -552,6 +580,129 @@ int32_t rsp_profile_pc(rsp_plan* p, int32_t P, int32_t B, int32_t iters, float* 
         bytes_out[1] = (int64_t)p->esz * (int64_t)(d.z_elems + d.out_elems) + (int64_t)p->rsz * (int64_t)d.mag_elems;
         bytes_out[2] = 2 * (int64_t)p->esz * (int64_t)d.out_elems;
     }
+    return RSP_OK;
+}
+
+// ---- digital down-conversion: k_ddc ----
+// The size checks of a call and its kernel argument.  Without a parameter block the filter cannot be judged:
+// only the refusals of P, N and C come first, the null check follows.
+static int ddc_sizes(const rsp_plan* p, int64_t P, int64_t N, int64_t C, const rsp_ddc_params* prm, DdcDesc* d) {
+    const int rc = prm ? rsp_ddc_derive(P, N, C, prm->L, prm->D, prm->off, plan_dtype(p), d)
+                       : rsp_ddc_derive(P, N, C, 1, 1, 0, plan_dtype(p), d);
+    if (rc || !prm) return rc;
+    d->mode = prm->mode;
+    d->w = prm->w;
+    d->w0 = prm->w0;
+    return RSP_OK;
+}
+
+// ... and of its pointers and mode
+static int ddc_args(const rsp_plan* p, const void* x, const rsp_ddc_params* prm, const void* out) {
+    if (!p || !x || !prm || !prm->h || !out) return fail(RSP_ERR_INVALID, "null argument");
+    if (prm->mode != RSP_DDC_NCO_IQ && prm->mode != RSP_DDC_NCO_SIN)
+        return fail(RSP_ERR_INVALID, "mode must be RSP_DDC_NCO_IQ or RSP_DDC_NCO_SIN, got %d", prm->mode);
+    return RSP_OK;
+}
+
+// The taps in the plan's precision and one k_ddc launch on device memory (sizes checked, queue drained)
+static int ddc_run(rsp_plan* p, const DdcDesc& d, const double* h, const void* d_x, void* d_y, hipStream_t s) {
+    int rc = dev_reserve(p->ddc_h, (size_t)d.L * p->rsz);
+    if (rc || (rc = p->put_reals(p->ddc_h.p, h, d.L))) return rc;
+    HIPCHK(launch_ddc(d, p->g.prec, d_x, p->ddc_h.p, d_y, s));
+    return RSP_OK;
+}
+
+// A host cube of reals into p->ddc_in in the plan's precision on stream s (borrowed until the sync)
+static int ddc_upload(rsp_plan* p, const DdcDesc& d, const void* x, int dtype, hipStream_t s) {
+    const size_t reals = (size_t)d.P * d.N * d.C;
+    const void* src;
+    int rc = dev_reserve(p->ddc_in, reals * p->rsz);
+    if (rc || (rc = host_reals_in_plan_prec(p, x, dtype == RSP_R64, reals, &src))) return rc;
+    HIPCHK(hipMemcpyAsync(p->ddc_in.p, src, reals * p->rsz, hipMemcpyHostToDevice, s));
+    return RSP_OK;
+}
+
+int32_t rsp_ddc(rsp_plan* p, int32_t P, int32_t N, int32_t C, const void* x, int32_t dtype, const rsp_ddc_params* prm,
+                double* out) {
+    DdcDesc d;
+    int rc = ddc_sizes(p, P, N, C, prm, &d);
+    if (rc) return rc;   // refusals before any device work
+    if (dtype != RSP_R32 && dtype != RSP_R64) return fail(RSP_ERR_INVALID, "unknown dtype %d (RSP_R32 or RSP_R64)", dtype);
+    if ((rc = ddc_args(p, x, prm, out))) return rc;
+    if ((rc = begin_sync(p))) return rc;
+    hipStream_t s = p->lanes[0].stream;
+    const size_t nout = (size_t)P * d.No * C;
+    if ((rc = dev_reserve(p->ddc_out, std::max<size_t>(nout, 1) * p->esz)) || (rc = ddc_upload(p, d, x, dtype, s)) ||
+        (rc = ddc_run(p, d, prm->h, p->ddc_in.p, p->ddc_out.p, s)))
+        return rc;
+    return download_widened(p, p->ddc_out.p, nout, out, s);   // its wait: the caller's cube (or the staging buffer) is borrowed for the call
+}
+
+int32_t rsp_ddc_device(rsp_plan* p, int32_t P, int32_t N, int32_t C, const void* d_x, const rsp_ddc_params* prm, void* d_out) {
+    DdcDesc d;
+    int rc = ddc_sizes(p, P, N, C, prm, &d);
+    if (rc || (rc = ddc_args(p, d_x, prm, d_out))) return rc;
+    const size_t nin = (size_t)P * N * C, nout = (size_t)P * d.No * C;
+    const char *a = static_cast<const char*>(d_x), *b = static_cast<const char*>(d_out);
+    if (a < b + nout * p->esz && b < a + nin * p->rsz) return fail(RSP_ERR_INVALID, "d_x and d_out overlap");
+    if ((uintptr_t)d_x % p->rsz || (uintptr_t)d_out % p->esz)
+        return fail(RSP_ERR_INVALID, "d_x must be aligned to a real (%zu bytes) and d_out to a complex element (%zu bytes)", p->rsz,
+                    p->esz);
+    if ((rc = begin_sync(p))) return rc;
+    hipStream_t s = p->lanes[0].stream;
+    if ((rc = ddc_run(p, d, prm->h, d_x, d_out, s))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    return RSP_OK;
+}
+
+int32_t rsp_ddc_raw_detect(rsp_plan* p, int32_t P, int32_t N, int32_t C, const void* x, int32_t dtype, const rsp_ddc_params* prm,
+                           int32_t B, int32_t nfft, const double* W, int32_t conj, const double* win,
+                           const rsp_detect_params* dprm, rsp_frame_out* out) {
+    DdcDesc d;
+    int n = 0;
+    XcDesc xd;
+    int rc = ddc_sizes(p, P, N, C, prm, &d);
+    if (rc) return rc;
+    if (dtype != RSP_R32 && dtype != RSP_R64) return fail(RSP_ERR_INVALID, "unknown dtype %d (RSP_R32 or RSP_R64)", dtype);
+    if ((rc = ddc_args(p, x, prm, x))) return rc;
+    if (d.No != p->g.N)
+        return fail(RSP_ERR_INVALID, "the down-converter gives No = %d samples a pulse, the plan's point_PRT is %d", d.No, p->g.N);
+    if ((rc = raw_sizes(p, P, C, B, nfft, dprm, &n, &xd)) || (rc = raw_args(p, x, C, B, W, dprm, out))) return rc;
+    if ((rc = begin_sync(p))) return rc;
+    hipStream_t s = p->lanes[0].stream;
+    DevConsts k;
+    DbfDesc dd;
+    if ((rc = raw_reserve(p, P, C, B, n, dprm, &k, &dd)) || (rc = ddc_upload(p, d, x, dtype, s))) return rc;
+    ddc_set_opitch(&d, (unsigned)dd.pitch, (unsigned)p->esz);   // the IQ cube straight into k_dbf's channel planes
+    if ((rc = ddc_run(p, d, prm->h, p->ddc_in.p, p->dbf_in.p, s))) return rc;
+    if ((rc = dbf_launch_planes(p, dd, C, B, W ? W : p->h_W.data(), conj, s))) return rc;
+    HIPCHK(hipStreamSynchronize(s));   // the caller's cube (or the staging buffer) is borrowed until here
+    if ((rc = pc_launches(p, p->dbf_out.p, dd.opitch, p->mtd_in.p, s))) return rc;
+    return mtd_detect_tail(p, P, p->g.G, B, n, xd, k, win, dprm, out, s);
+}
+
+int32_t rsp_profile_ddc(rsp_plan* p, int32_t P, int32_t N, int32_t C, int32_t L, int32_t D, int32_t off, int32_t iters,
+                        float* ms_out, int64_t* bytes_out) {
+    DdcDesc d;
+    int rc = rsp_ddc_derive(P, N, C, L, D, off, plan_dtype(p), &d);   // sizes first, as the other calls of the section
+    if (rc) return rc;
+    if (!p || iters < 1 || !ms_out) return fail(RSP_ERR_INVALID, "bad argument");
+    if (d.No < 1) return fail(RSP_ERR_INVALID, "N=%d, off=%d: no output to time", N, off);
+    if ((rc = begin_sync(p))) return rc;
+    hipStream_t s = p->lanes[0].stream;
+    d.mode = RSP_DDC_NCO_IQ;
+    d.w = 0x199999999999999Aull;   // 2^64 / 10
+    if ((rc = dev_reserve(p->ddc_in, d.in_bytes)) || (rc = dev_reserve(p->ddc_out, d.out_bytes)) ||
+        (rc = dev_reserve(p->ddc_h, (size_t)L * p->rsz)))
+        return rc;
+    HIPCHK(hipMemsetAsync(p->ddc_in.p, 0, d.in_bytes, s));   // zeros, and zero taps: the time does not depend on the values
+    HIPCHK(hipMemsetAsync(p->ddc_h.p, 0, (size_t)L * p->rsz, s));
+    auto run = [&]() -> int {
+        HIPCHK(launch_ddc(d, p->g.prec, p->ddc_in.p, p->ddc_h.p, p->ddc_out.p, s));
+        return RSP_OK;
+    };
+    if ((rc = time_launches(s, iters, run, ms_out))) return rc;
+    if (bytes_out) *bytes_out = (int64_t)d.in_bytes + (int64_t)d.out_bytes;
     return RSP_OK;
 }
 }  // extern "C"

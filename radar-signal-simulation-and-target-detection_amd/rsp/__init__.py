@@ -20,6 +20,8 @@ Drop-in for the MATLAB reference's per-frame chain
   nfft, ...)`` / ``raw_detect(raw_iq_data, DBF_coeffs_data_C, MTD_win, nfft, ...)`` -- the three-segment
   pulse compression of any number of pulses and beams (main_simulate_echoes_with_array_v7_7.m:362-486), alone
   or as the front of the zero-padded MTD and the detector, from the beams or from the raw frame
+* ``mix_filter_downsample(xt, f, fs, Num, D)`` -- the digital down-converter in front of all of it: NCO
+  mixer, FIR and decimator of the real IF samples (simulation_learn.m:79-102)
 * ``precompute(...)`` -- the driver's "%% 3" section (v8:79-155)
 * ``load_frame`` / ``save_frame`` -- the ``frame_sim_array_%d.mat`` load/save pair
   (main_simulate_echoes_with_array_v2.m:285, debug_simulated_data_processing_v3.m:20-22)
@@ -37,7 +39,7 @@ from .config import (named_config, make_config, default_cfar_params, default_clu
                      debug_v2_cfar_config, v3_cfar_params)
 from .precompute import precompute
 from .plan import (Plan, process_targets_multi, describe_vcfar, describe_dbf, describe_xcfar, describe_mtd, mtd_table,
-                   describe_detect, describe_pc)
+                   describe_detect, describe_pc, describe_ddc, ddc_phase_word)
 from ._abi import RspError
 from .matio import load_frame, save_frame
 from .music import MusicPlan, MUSIC_1D, MusicPlan2D, MUSIC_2D
@@ -161,6 +163,18 @@ def mtd_doppler(pc_results, MTD_win, nfft=None, device=0, precision='c128'):
     cfg, cfar, cluster, W, ang, k = named_config('plumbing')   # the plan gives the device and the precision only
     p = _plan_for(cfg, cfar, cluster, precompute(cfg, W, ang, k, V8_FIR), device, precision)
     return p.mtd(pc_results, MTD_win, nfft=nfft)
+
+
+def mix_filter_downsample(xt, f, fs, Num, D, device=0, precision='c128'):
+    """The receiver front end of simulation_learn.m:79-102: ``xrt = xt .* sin(2*pi*f*t2)`` with
+    ``t2 = (0:N-1)/fs``, ``firxrt = filter(Num, 1, xrt)`` and ``xrtdown = downsample(firxrt, D)``.  ``xt`` is
+    the real IF line [N] (or lines [P, N], [P, N, C], the fast-time axis second), ``Num`` the FIR taps
+    (FIR.mat's 12), ``D`` the decimation factor (4).  Returns the real baseband samples, float64 with
+    ceil(N / D) along the fast-time axis.  The mixer is the library's 64-bit NCO at ``ddc_phase_word(f, fs)``
+    (``Plan.ddc`` with ``nco='sin'``; include/rsp.h has the arithmetic)."""
+    cfg, cfar, cluster, W, ang, k = named_config('plumbing')   # the plan gives the device and the precision only
+    p = _plan_for(cfg, cfar, cluster, precompute(cfg, W, ang, k, V8_FIR), device, precision)
+    return np.ascontiguousarray(p.ddc(xt, Num, D, f0=f, fs=fs, nco='sin').real)
 
 
 def mtd_velocity_axis(v_max, nfft):

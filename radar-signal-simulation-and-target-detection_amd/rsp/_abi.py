@@ -13,6 +13,7 @@ _INTREE = LIB_PATH
 
 RSP_OK, RSP_ERR_INVALID, RSP_ERR_UNSUPPORTED, RSP_ERR_DEVICE, RSP_ERR_NOMEM, RSP_ERR_OVERFLOW = 0, -1, -2, -3, -4, -5
 RSP_C64, RSP_C128 = 1, 2
+RSP_R32, RSP_R64 = 3, 4   # real float / double: rsp_ddc's input
 RSP_LAYOUT_PNC = 0
 
 _dp = ct.POINTER(ct.c_double)
@@ -170,6 +171,20 @@ class PcInfo(ct.Structure):
                                           'unpack_wg', 'k2_wg_per_cu', 'pack_lds_bytes', 'unpack_lds_bytes')] + \
                [('ivl_lo', ct.c_int32 * 4), ('ivl_start', ct.c_int32 * 4)]
 
+
+class DdcParams(ct.Structure):
+    _fields_ = [('w', ct.c_uint64), ('w0', ct.c_uint64), ('mode', ct.c_int32), ('D', ct.c_int32), ('off', ct.c_int32),
+                ('L', ct.c_int32), ('h', _dp)]
+
+
+class DdcInfo(ct.Structure):
+    _fields_ = [(n, ct.c_int32) for n in ('P', 'N', 'C', 'L', 'D', 'off', 'No', 'TP', 'TK', 'in_rows', 'k_tiles', 'p_tiles',
+                                          'workgroups', 'lds_bytes', 'tap_chunk', 'threads', 'k_per_thread')] + \
+               [('in_bytes', ct.c_int64), ('out_bytes', ct.c_int64)]
+
+
+RSP_DDC_MAX_TAPS, RSP_DDC_MAX_D = 512, 64
+RSP_DDC_NCO_IQ, RSP_DDC_NCO_SIN = 0, 1
 
 RSP_MTD_MAX_NFFT = 2048
 RSP_MTD_ROUTE_POW2, RSP_MTD_ROUTE_CHIRPZ, RSP_MTD_ROUTE_DIRECT = 0, 1, 2
@@ -408,6 +423,14 @@ PROTOTYPES = {
                                     _dp, ct.POINTER(DetectParams), ct.POINTER(FrameOut)]),
     'rsp_profile_pc': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, ct.POINTER(ct.c_float),
                                     ct.POINTER(ct.c_int64)]),
+    'rsp_ddc_describe': (ct.c_int32, [ct.c_int32] * 7 + [ct.POINTER(DdcInfo)]),
+    'rsp_ddc_phase_word': (ct.c_int32, [ct.c_double, ct.c_double, ct.POINTER(ct.c_uint64)]),
+    'rsp_ddc': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, _P, ct.c_int32, ct.POINTER(DdcParams), _dp]),
+    'rsp_ddc_device': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, _P, ct.POINTER(DdcParams), _P]),
+    'rsp_ddc_raw_detect': (ct.c_int32, [_P, ct.c_int32, ct.c_int32, ct.c_int32, _P, ct.c_int32, ct.POINTER(DdcParams),
+                                        ct.c_int32, ct.c_int32, _dp, ct.c_int32, _dp, ct.POINTER(DetectParams),
+                                        ct.POINTER(FrameOut)]),
+    'rsp_profile_ddc': (ct.c_int32, [_P] + [ct.c_int32] * 7 + [ct.POINTER(ct.c_float), ct.POINTER(ct.c_int64)]),
     'rsp_device_alloc': (ct.c_int32, [_P, ct.c_int64, ct.POINTER(_P)]),
     'rsp_device_free': (ct.c_int32, [_P, _P]),
     'rsp_device_upload': (ct.c_int32, [_P, _P, _P, ct.c_int64]),

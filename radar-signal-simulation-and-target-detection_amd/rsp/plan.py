@@ -382,6 +382,52 @@ def describe_pc(config, cfar_params, cluster_params, precomputed_data, P, B, pre
     return _pc_dict(info)
 
 
+def describe_ddc(P, N, C, L, D, off=0, precision='c128'):
+    """How k_ddc covers a real cube [P, N, C] with ``L`` taps, decimation ``D`` and phase ``off`` in a plan of
+    ``precision``, without a device (rsp_ddc_describe): the fields of rsp_ddc_info as a dict -- ``No``, the
+    tile ``TP`` x ``TK``, ``in_rows``, ``k_tiles``, ``p_tiles``, ``workgroups``, ``lds_bytes``, ``tap_chunk``,
+    ``threads``, ``k_per_thread``, ``in_bytes`` and ``out_bytes``.  Refusals raise RspError with the code and
+    message ``Plan.ddc`` gives."""
+    info = _abi.DdcInfo()
+    check(lib().rsp_ddc_describe(int(P), int(N), int(C), int(L), int(D), int(off), _prec_code(precision), ct.byref(info)))
+    return {k: getattr(info, k) for k, _ in _abi.DdcInfo._fields_}
+
+
+def ddc_phase_word(f0, fs):
+    """The NCO's phase step for a carrier ``f0`` sampled at ``fs``: round(f0 / fs 2^64) mod 2^64
+    (rsp_ddc_phase_word)."""
+    w = ct.c_uint64()
+    check(lib().rsp_ddc_phase_word(float(f0), float(fs), ct.byref(w)))
+    return int(w.value)
+
+
+DDC_MODES = {'iq': _abi.RSP_DDC_NCO_IQ, 'sin': _abi.RSP_DDC_NCO_SIN}
+
+
+def _ddc_params(h, D, f0, fs, w, w0, nco, off):
+    """rsp_ddc_params and the tap array it borrows; the phase step is ``w`` or, from ``f0`` and ``fs``,
+    ``ddc_phase_word``'s."""
+    if nco not in DDC_MODES:
+        raise ValueError("nco must be 'iq' or 'sin', got %r" % (nco,))
+    if (w is None) != (f0 is not None and fs is not None) or (w is not None and (f0 is not None or fs is not None)):
+        raise ValueError('give either w or both f0 and fs')
+    if w is None:
+        w = ddc_phase_word(f0, fs)
+    taps = np.ascontiguousarray(np.asarray(h, np.float64).ravel())
+    keep = taps if taps.size else np.zeros(1)
+    prm = _abi.DdcParams(w=int(w) % 2 ** 64, w0=int(w0) % 2 ** 64, mode=DDC_MODES[nco], D=int(D), off=int(off),
+                         L=int(taps.size), h=_dptr(keep))
+    return prm, keep
+
+
+def _real_arg(x):
+    """A real array as rsp_ddc takes it: (Fortran-ordered array, its void pointer, dtype code).  float32
+    stays; everything else becomes float64."""
+    r32 = np.asarray(x).dtype == np.float32
+    a = np.asfortranarray(x, None if r32 else np.float64)
+    return a, a.ctypes.data_as(ct.c_void_p), _abi.RSP_R32 if r32 else _abi.RSP_R64
+
+
 def mtd_table(nfft, precision='c128'):
     """The chirp-z tables of length ``nfft`` as the kernel reads them (rsp_mtd_table): ``(w, Bf)``,
     complex128 arrays that hold the values rounded to ``precision``: w[m] = exp(-i pi (m^2 mod 2 nfft) /
@@ -1107,6 +1153,83 @@ class Plan:
         ms, by = (ct.c_float * 3)(), (ct.c_int64 * 3)()
         check(lib().rsp_profile_pc(self.h, int(P), int(B), int(iters), ms, by))
         return {k: (float(ms[i]), int(by[i])) for i, k in enumerate(('k_pc_pack', 'k2_pc', 'k_pc_unpack'))}
+
+    # ---- digital down-conversion as a stand-alone stage: NCO mixer, FIR, decimator -----------------
+    @staticmethod
+    def _real3(x, what='x'):
+        x = np.asarray(x)
+        if np.iscomplexobj(x):
+            raise ValueError('%s is complex: the down-converter takes real samples' % what)
+        shape = x.shape
+        if x.ndim == 1:
+            x = x[None, :, None]
+        elif x.ndim == 2:
+            x = x[:, :, None]
+        if x.ndim != 3:
+            raise ValueError('%s %r: expected [N], [P, N] or [P, N, C]' % (what, shape))
+        return x, shape
+
+    def ddc(self, x, h, D, *, f0=None, fs=None, w=None, w0=0, nco='iq', off=0):
+        """The receiver's digital down-converter (rsp_ddc; simulation_learn.m:79-102): real samples ``x``
+        [P, N, C] (or [P, N], or one line [N]; float32 stays, everything else is taken as float64) times the
+        NCO ``nco`` -- 'iq': cos - i sin, 'sin': the reference's single real mixer -- of phase step ``w``
+        (2^-64 turns per sample; or ``f0`` and ``fs``, ``ddc_phase_word``) from start phase ``w0``, through
+        ``filter(h, 1, .)`` and ``downsample(., D, off)`` -> complex128 of the input's shape with
+        No = ceil((N - off) / D) samples.  The plan gives the device and the precision only;
+        include/rsp.h has the arithmetic."""
+        x3, shape = self._real3(x)
+        P, N, C = x3.shape
+        prm, keep = _ddc_params(h, D, f0, fs, w, w0, nco, off)
+        a, ap, dt = _real_arg(x3)
+        No = max(0, -(-(N - prm.off) // prm.D)) if prm.D >= 1 else 0
+        out = np.empty((P, No, C), np.complex128, order='F')
+        buf = out if out.size else np.empty(1, np.complex128)
+        check(lib().rsp_ddc(self.h, P, N, C, ap, dt, ct.byref(prm), _dptr(buf)))
+        return out.reshape({1: (No,), 2: (P, No), 3: (P, No, C)}[len(shape)], order='F')
+
+    def ddc_device(self, d_x, d_out, P, N, C, h, D, *, f0=None, fs=None, w=None, w0=0, nco='iq', off=0):
+        """The same on device memory in the plan's precision (rsp_ddc_device): ``d_x`` [P, N, C] reals ->
+        ``d_out`` [P, No, C] complex, pulse index fastest on both sides; the two must not overlap."""
+        prm, keep = _ddc_params(h, D, f0, fs, w, w0, nco, off)
+        check(lib().rsp_ddc_device(self.h, int(P), int(N), int(C), ct.c_void_p(d_x), ct.byref(prm), ct.c_void_p(d_out)))
+
+    def ddc_raw_detect(self, x, h, D, *, f0=None, fs=None, w=None, w0=0, nco='iq', off=0, W=None, conj=True, win=None,
+                       nfft=None, cfar=None, cluster=None, range_axis=None, velocity_axis=None, deltaR=None, deltaV=None,
+                       beam_angles_deg=None, k_slopes_LUT=None, monopulse=None, want_rdm=False, want_cfar=False):
+        """``raw_detect(ddc(x, ...), ...)`` without leaving the device (rsp_ddc_raw_detect): ``x`` [P, N, C]
+        real IF samples whose down-converted length No is the plan's point_PRT; the arguments are ``ddc``'s
+        followed by ``raw_detect``'s, the result is ``raw_detect``'s."""
+        x3, shape = self._real3(x)
+        if len(shape) != 3:
+            raise ValueError('x %r: expected [P, N, C]' % (shape,))
+        P, N, C = x3.shape
+        dprm, dkeep = _ddc_params(h, D, f0, fs, w, w0, nco, off)
+        if W is None:
+            B, wk, wp = self.B, None, None
+        else:
+            W = np.asarray(W, np.complex128)
+            if W.ndim != 2 or W.shape[1] != C:
+                raise ValueError('x %r and W %r: expected [P, N, C] and [B, C]' % (shape, W.shape))
+            B = W.shape[0]
+            wk = np.asfortranarray(W).ravel(order='F').view(np.float64)   # B x C column-major (MATLAB)
+            wp = _dptr(wk)
+        G, n = self.G, int(nfft) if nfft else P
+        prm, keep = self._detect_params(n, G, B, cfar, cluster, range_axis, velocity_axis, deltaR, deltaV,
+                                        beam_angles_deg, k_slopes_LUT, monopulse)
+        mk, mp = self._mtd_win(win, P)
+        a, ap, dt = _real_arg(x3)
+        o, bufs = self._detect_out(n, G, B, want_cfar, (n, G, B) if want_rdm else None)
+        check(lib().rsp_ddc_raw_detect(self.h, P, N, C, ap, dt, ct.byref(dprm), B, n, wp, 1 if conj else 0, mp,
+                                       ct.byref(prm), ct.byref(o)))
+        return self._collect(o, bufs, None, None)
+
+    def profile_ddc(self, P, N, C, L, D, off=0, iters=20):
+        """HIP-event time of k_ddc alone on a [P, N, C] cube of zeros (rsp_profile_ddc): {'stage', 'ms',
+        'bytes'}, bytes = the input plus the output in the plan's precision."""
+        ms, by = ct.c_float(), ct.c_int64()
+        check(lib().rsp_profile_ddc(self.h, int(P), int(N), int(C), int(L), int(D), int(off), int(iters), ct.byref(ms),
+                                    ct.byref(by)))
+        return {'stage': 'k_ddc', 'ms': float(ms.value), 'bytes': int(by.value)}
 
     def _raw_weights(self, W):
         """(array kept alive, pointer) of the weights of a raw-cube call; None: the plan's own."""
