@@ -424,6 +424,40 @@ int32_t rsp_process_stage2(rsp_plan* plan, const void* iq_beams, int32_t dtype,
 int32_t rsp_process_stage2_gated(rsp_plan* plan, const void* iq_gated, int32_t dtype, int32_t n_gated,
                                  const int32_t* cols, double* mtd_out, double* pc_out);
 
+/* ---- Value domain of the magnitudes and of the three map detectors ----
+ * Holds for rsp_process_cube / rsp_process_targets (K2's magnitudes, K3), rsp_detect and its
+ * compositions, rsp_stage3_cfar, rsp_vcfar, rsp_xcfar and their fused stage-2 forms.  Each statement
+ * names the test that asserts it.
+ *   Inputs are finite.  The result for a NaN anywhere in the input is unspecified.
+ *   Magnitudes |x| of a complex value (x, y): q = RN(RN(x x) + RN(y y)), then the square root to one
+ *     ulp.  While q is a normal, finite number -- |x| from about 2^-511 to 2^511 in complex double,
+ *     2^-63 to 2^63 in complex single -- the result is within 3u of hypot(x, y), u = 2^-53 or 2^-24,
+ *     and a pair sum RN(|a| + |b|) within 4u of |a| + |b|; 0 gives +0 whatever the signs.  Asserted
+ *     per element at 2^-500 .. 2^500 (double) and 2^-60 .. 2^60 (single), on axis cells and on cells
+ *     whose smaller square is lost, and on the device's own maps with a dynamic range above 1e3
+ *     (tests/test_cmag.py).  Outside that interval q under- or overflows and nothing is promised.
+ *   Every stage up to the magnitudes is linear and every detector homogeneous: an input scaled by a
+ *     power of two inside the interval gives scaled maps and thresholds and the same flags, hits,
+ *     detections, Range and Velocity, bit for bit (tests/test_scale_invariance.py: 2^+-300 in complex
+ *     double, 2^+-24 in complex single).  Angle holds the reference's absolute eps.
+ *   rsp_stage3_cfar and rsp_vcfar are defined to the bit over all finite amplitudes: subnormal cells,
+ *     sums and thresholds, and window sums that overflow, whose threshold is +Inf (a cell is then
+ *     flagged by >= only if it is +Inf itself, never by >).  A complex-single plan narrows the caller's
+ *     doubles first: cells below the float subnormals are 0, cells above FLT_MAX are +Inf, and the
+ *     definition applies to those.  T_CFAR is rounded to the plan's precision first
+ *     (tests/test_cfar_value_range.py, cases tiny, sub, huge, narrowed, wide, const, zero, T-edge).
+ *   rsp_xcfar, rsp_detect and K3: the same in complex single.  In complex double the quotient
+ *     sum / n is k3_quot's FMA form, which equals RN(sum / n) wherever that quotient is a normal
+ *     number, sum >= n 2^-1022.  Below, where the quotient is subnormal, an exact tie (n even and no
+ *     power of two) may round to the other neighbour (tests/test_xcfar_ref.py::
+ *     test_fma_quotient_domain, in exact rational arithmetic for n = 1 .. 64).  A window sum of +Inf
+ *     gives a threshold of +Inf, as the division's, in the map detector k_xcfar (rsp_xcfar, rsp_detect,
+ *     rsp_last_cfar_threshold and the fused forms).  K3, inside rsp_process_cube, forms no threshold
+ *     output and does not saturate; its sums are sums of magnitudes inside the interval above and
+ *     cannot overflow.  The map detector is asserted to the bit on maps from Rayleigh x 2^-900 upwards
+ *     and on overflowing sums; the two cases below the bound are listed as not compared
+ *     (tests/_cfar_value_cases.py LEFT_OUT). */
+
 /* ---- stage-3 range CFAR of the stage-2 path ----
  * local_execute_cfar / executeCFAR_2D / Function_CFAR1D_sub of
  * debug_simulated_data_processing_v2.m:419-511, the detector every caller of process_stage2_mtd
@@ -720,7 +754,8 @@ int32_t rsp_profile_mtd(rsp_plan* plan, int32_t P, int32_t G, int32_t n_maps, in
  *   each sum one rounded add per cell in ascending index order starting from +0 (k3_map_sums); no
  *   sliding-sum updates;
  *   complex-double plans: nR = RN(max(lr, tr) / rR), nV = RN(max(lv, tv) / rV), the correctly
- *     rounded quotients (k3_quot's FMA form gives exactly that);
+ *     rounded quotients (k3_quot's FMA form gives exactly that wherever the quotient is a normal
+ *     number or +Inf: "Value domain" above);
  *   complex-single plans: nR = RN(max(lr, tr) RN(1 / rR)), nV likewise: K3's float form, part of the
  *     definition and not an approximation of the double one;
  *   noise = max(nR, nV); threshold = RN(T_CFAR noise); flag = A > threshold (strict, :209).

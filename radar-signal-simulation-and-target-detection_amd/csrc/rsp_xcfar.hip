@@ -139,7 +139,7 @@ __global__ __launch_bounds__(RSP_THREADS) void k_xcfar(XcDesc d, const void* __r
                 for (int q = 0; q < d.rR; ++q) tr += trp[q];
                 for (int q = 0; q < d.rV; ++q) lv += xc_row(S, v - hV + q, v0, W, hRa, hV)[lane];
                 for (int q = 0; q < d.rV; ++q) tv += xc_row(S, v + d.gV + 1 + q, v0, W, hRa, hV)[lane];
-                t = Tc * k3_noise2<false>(lr, tr, lv, tv, fR, iR, fV, iV);
+                t = Tc * k3_noise2<false, true>(lr, tr, lv, tv, fR, iR, fV, iV);   // SAT: a sum of +Inf gives +Inf
                 hit = a > t;
                 td = (double)t;
             }

@@ -167,3 +167,20 @@ def test_describe_refuses_a_window_beyond_the_tile():
     with pytest.raises(_abi.RspError) as e:
         describe_stage3(16, (200, 200, 200), dict(CFAR, refCells_R=16, saveCells_R=top - 15))
     assert e.value.code == _abi.RSP_ERR_INVALID and "exceeds the kernel's tile halo %d" % top in str(e.value)
+
+
+# ------------------------------------------------------------------ the value cases (tests/_cfar_value_cases.py)
+import _cfar_value_cases as vc   # noqa: E402
+
+_VC = [(v, p, c) for v in vc.VARIANTS['stage3'] for p in ('c128', 'c64') for c in vc.cases(p)]
+
+
+@pytest.mark.parametrize('variant, prec, case', _VC, ids=['%s-%s-%s' % x for x in _VC])
+def test_value_case_preconditions(variant, prec, case):
+    """No value case is hollow: the restatement has the property the case is named for."""
+    vc.check_preconditions('stage3', variant, case, prec)
+
+
+def test_value_case_shape_spans_two_range_chunks():
+    d = describe_stage3(vc.S3_P, vc.S3_SEGS, vc.params('stage3', 'go', 1.5))
+    assert d['chunk'] < d['G'] < 2 * d['chunk'] and vc.S3_SEGS[0] == 2 * d['halo']

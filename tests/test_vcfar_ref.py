@@ -170,3 +170,15 @@ def test_literal_mirror_ignores_method(monkeypatch):
     for det, thr in outs:
         assert det.dtype == bool and thr.dtype == np.float64 and det.shape == thr.shape == a.shape
         assert np.array_equal(thr[:, 2], HAND_CA)
+
+
+# ------------------------------------------------------------------ the value cases (tests/_cfar_value_cases.py)
+import _cfar_value_cases as vc   # noqa: E402
+
+_VC = [(v, p, c) for v in vc.VARIANTS['vcfar'] for p in ('c128', 'c64') for c in vc.cases(p)]
+
+
+@pytest.mark.parametrize('variant, prec, case', _VC, ids=['%s-%s-%s' % x for x in _VC])
+def test_value_case_preconditions(variant, prec, case):
+    """No value case is hollow: the restatement has the property the case is named for."""
+    vc.check_preconditions('vcfar', variant, case, prec)

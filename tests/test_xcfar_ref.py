@@ -105,3 +105,76 @@ def test_planted_ties(win, dtype):
     ties = np.argwhere(strict != loose)
     assert [tuple(x) for x in ties] == [(hV, hR, 1), (P - hV - 1, G - hR - 1, 1)]
     assert t[hV, hR, 1] == 3.0 and a[hV, hR, 1] == 3.0
+
+
+# ------------------------------------------------------------------ the value cases (tests/_cfar_value_cases.py)
+import _cfar_value_cases as vc   # noqa: E402
+
+_VC = [(v, p, c) for v in vc.VARIANTS['xcfar'] for p in ('c128', 'c64') for c in vc.cases(p)]
+
+
+@pytest.mark.parametrize('variant, prec, case', _VC, ids=['%d-%d-%d-%d-%s-%s' % (v + (p, c)) for v, p, c in _VC])
+def test_value_case_preconditions(variant, prec, case):
+    """No value case is hollow: the restatement has the property the case is named for (the left-out
+    complex-double cases included: the restatement itself is defined there)."""
+    vc.check_preconditions('xcfar', variant, case, prec)
+
+
+def test_left_out_list_is_the_two_out_of_domain_cases():
+    assert vc.LEFT_OUT == {('xcfar', 'c128', 'sub'), ('xcfar', 'c128', 'tiny')}
+    for det in vc.DETECTORS:
+        for prec in ('c128', 'c64'):
+            want = [c for c in vc.cases(prec) if not (det == 'xcfar' and prec == 'c128' and c in ('sub', 'tiny'))]
+            assert list(vc.compared(det, prec)) == want
+    assert 'x900' in vc.compared('xcfar', 'c128') and 'narrowed' in vc.compared('xcfar', 'c64')
+
+
+def test_fma_quotient_domain():
+    """k3_quot's complex-double form in exact rational arithmetic against RN(x / n), n = 1 .. 64.
+    Where the quotient is a normal number (x >= n 2^-1022) the two agree, at every scale up to the
+    largest finite x; the residual is exact everywhere, subnormal or not.  Below, they differ on exact
+    ties between two subnormals, which need an even n that is no power of two; odd n and powers of two
+    agree at every scale.  The sums x are sums of a few random amplitudes, as a window forms them."""
+    rng = np.random.default_rng(ref.SEED)
+    fm = float(np.finfo(np.float64).max)
+    above = below = 0
+    bad_above, bad_below = [], {}
+    for n in range(1, 65):
+        lo = n * 2.0 ** -1022                   # the smallest x whose quotient is normal
+        xs = [lo, float(np.nextafter(lo, 1.0)), lo * 1.5, fm, fm / 3, 1.0, 0.1 * n]
+        for e in (-1016, -1000, -900, -300, -60, 0, 60, 300, 1000):
+            xs += [float(x) for x in np.ldexp(rng.rayleigh(1.0, (25, 5)).sum(axis=1), e)]
+        for x in xs:
+            assert x >= lo
+            q, exact = vc.fma_quotient(x, n)
+            above += 1
+            if q != vc.true_quotient(x, n) or not exact:
+                bad_above.append((x, n))
+        sub = [float(np.nextafter(lo, 0.0)), 2.0 ** -1074, 3 * 2.0 ** -1074]
+        for e in (-1030, -1045, -1060, -1072):
+            sub += [float(x) for x in np.ldexp(rng.rayleigh(1.0, (25, 5)).sum(axis=1), e)]
+        for x in sub:
+            if not 0 < x < lo:
+                continue
+            q, exact = vc.fma_quotient(x, n)
+            assert exact, 'the residual of x = %r, n = %d is not exact' % (x, n)
+            below += 1
+            if q != vc.true_quotient(x, n):
+                bad_below[n] = bad_below.get(n, 0) + 1
+    print('quotient normal: %d mismatches of %d; quotient subnormal: %d of %d, by n: %r'
+          % (len(bad_above), above, sum(bad_below.values()), below, sorted(bad_below.items())))
+    assert not bad_above, bad_above[:5]
+    assert sum(bad_below.values()) >= 20
+    assert all(n % 2 == 0 and n & (n - 1) for n in bad_below), 'a mismatch at an odd n or a power of two'
+    assert {6, 10} <= set(bad_below)
+
+
+def test_fma_quotient_of_infinity_is_the_select():
+    """fma(-Inf, n, +Inf) is NaN: the FMA form alone gives NaN for a sum that overflowed, the division
+    +Inf.  k3_quot returns q0 = +Inf when the refined quotient is NaN; the restatement divides."""
+    inf = np.float64(np.inf)
+    with np.errstate(invalid='ignore'):
+        q0 = inf * np.float64(1.0 / 5)
+        r = -q0 * 5.0 + inf
+    assert np.isposinf(q0) and np.isnan(r)
+    assert np.isposinf(ref.quotient(np.array([inf]), 5, np.float64)).all()
